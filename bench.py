@@ -9,7 +9,10 @@ Default workload = the configuration BASELINE.json's metric is quoted on:
     with f32 accumulate / residual stream / master weights, both encoders trained, synthetic data,
     random-init weights N(0, 0.02).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes the last timed step's loss and a fixed, seeded sample of the updated parameters and of the
+gradients to DIR/*.npy (dump_outputs()); inputs and initial weights are seeded, so two builds can be compared.
 
 N > 1 without a torch.distributed environment: this process starts N fresh ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`) BEFORE any HIP call
@@ -93,7 +96,15 @@ def parse_args():
     ap.add_argument("--all-kernel-timers", action="store_true",
                     help="HIP events around EVERY kernel launch of the timed region (costs ~1 %% of the step); "
                          "default: only the dominant kernel, clipk_gemm_nt")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2 / c4: after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                         "(dump_outputs()), so that two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.config not in ("c2", "c4"):
+        ap.error("--dump-outputs is implemented for --config c2 / c4")
+    return args
 
 
 def self_launch(args) -> int:
@@ -307,6 +318,39 @@ def load_traffic(workload_key):
     return e, False
 
 
+DUMP_SAMPLE = 1 << 22                # entries per sampled array: 2 x 16 MB of f32, well under the 64 MB cap
+DUMP_SEED = 20240
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, model) -> dict:
+    """--dump-outputs: what the last timed training step handed its caller, as DIR/<name>.npy (float32).
+      loss.npy           [1]  the step's loss
+      params_sample.npy  [n]  the updated trainable parameters (module.parameters() order, flattened, concatenated)
+      grads_sample.npy   [n]  the step's gradients (what p.grad holds after the optimiser step), same entries
+    Both parameter-sized arrays hold the same fixed, seeded sample of DUMP_SAMPLE positions (sorted, duplicates
+    dropped) when there are more entries than that, else every entry.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    params = [p for p in model.parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                        for p in params])
+    n = flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+        idx = torch.from_numpy(idx).to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "params_sample": flat_p.cpu().numpy(),
+              "grads_sample": flat_g.cpu().numpy()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(np.float32))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 # ====================================================================================================== c2 / c4
 def bench_clip(args):
     import torch
@@ -425,6 +469,8 @@ def bench_clip(args):
         dist.barrier()
     dt = time.perf_counter() - t0
     ops.set_kernel_timer(None)
+    # the last timed step's outputs, before the breakdown steps below move the weights on
+    dumped = dump_outputs(args.dump_outputs, loss, model) if (args.dump_outputs and rank == 0) else None
     # Two more steps OUTSIDE the timed region, one HIP stream, HIP events around every launch: the per-class breakdown
     # (`kernels`) without taxing the timed region (~1 % when every launch is timed).
     timer_alone = None
@@ -475,6 +521,8 @@ def bench_clip(args):
     }
     if coll is not None:
         out["rccl"] = coll
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if ragged:
         out["config"]["lengths"] = (f"{args.lengths}: lengths uniform in [L/4, L]; {real_tokens} real tokens of "
                                     f"{B * (Lp + Lr)} padded positions ({real_tokens / (B * (Lp + Lr)):.3f})")

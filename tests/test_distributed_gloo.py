@@ -18,13 +18,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
-def _install_emulator():
+def _install_emulator(set_attr=setattr):
+    """Route clip_dplm_amd.ops.* to the emulator.  A spawned rank keeps it for its lifetime; the pytest process passes
+    monkeypatch.setattr, so that the kernels are back for the tests that run after this one."""
     sys.path[:0] = [ROOT, HERE]
     import ops_emulator
     from clip_dplm_amd import ops
     for n in ops_emulator._NAMES:
         if hasattr(ops, n) and n != "KernelTimer":
-            setattr(ops, n, getattr(ops_emulator, n))
+            set_attr(ops, n, getattr(ops_emulator, n))
 
 
 def _unit(n, p, seed):
@@ -114,7 +116,7 @@ def _worker(rank, world, initfile, results):
 
 
 @pytest.mark.timeout(300)
-def test_world2_matches_single_process():
+def test_world2_matches_single_process(monkeypatch):
     world = 2
     mp.set_sharing_strategy("file_system")
     with tempfile.TemporaryDirectory() as d:
@@ -123,7 +125,7 @@ def test_world2_matches_single_process():
         mp.spawn(_worker, args=(world, os.path.join(d, "init"), results), nprocs=world, join=True)
         res = [results[r] for r in range(world)]
     # ---- single-process references (same emulated kernels, no process group)
-    _install_emulator()
+    _install_emulator(monkeypatch.setattr)
     from types import SimpleNamespace as NS
 
     import clip_dplm_amd as K

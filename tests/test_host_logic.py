@@ -205,12 +205,14 @@ def test_dropout_training_mode_runs_and_is_seeded(monkeypatch):
 
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` outside torch.distributed.run starts two fresh ranks itself (before any HIP call) and
-    returns the launcher's exit code.  Here there is no GPU, so each rank stops at the 'needs an MI355X' check: the
-    test asserts the launch happened (both ranks reported) and that the failure propagated."""
+    returns the launcher's exit code.  The ranks see no GPU (any device is hidden from them, so the test means the
+    same on a GPU machine), so each rank stops at the 'needs an MI355X' check: the test asserts the launch happened
+    (both ranks reported) and that the failure propagated."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode != 0
