@@ -135,6 +135,7 @@ def refresh_weight_caches() -> int:
             _BATCH_DESC.clear()              # pointers changed (new model / reallocated flat buffer)
             desc = torch.tensor(rows, dtype=torch.int64).to(dev)
             _BATCH_DESC[(dev, rows)] = desc
+        ops.keep_for_capture(desc)
         with torch.cuda.device(dev):
             ops.cast_transpose_batched(desc)
         for c, w, key in items:
@@ -482,6 +483,7 @@ def _ln_defer_buffer(gamma, x):
             _LN_PART.clear()
         blocks, nfloat = ops.layernorm_bwd_partial_shape(rows, cols)
         part = _LN_PART[key] = (torch.empty(nfloat, dtype=torch.float32, device=x.device), blocks, cols, key)
+    ops.keep_for_capture(part[0])
     return part
 
 

@@ -444,7 +444,8 @@ class GraphedTransport:
                 maps(*self.static_in)
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        self._owned = []                                   # cached workspaces the graph's launches hold (ops.owned_by_capture)
+        with ops.owned_by_capture(self._owned), torch.cuda.graph(self.graph):
             self.static_out = maps(*self.static_in)
 
     @torch.no_grad()

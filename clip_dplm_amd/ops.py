@@ -119,6 +119,41 @@ def _need_cuda(*ts):
             raise _ffi.ClipkError(f"tensors on different devices: {dev} and {t.device}")
 
 
+# hipGraph capture (training.GraphedTrainStep, icnn.GraphedTransport): a captured launch holds the raw pointers of the
+# host-cached buffers it was given - workspaces, descriptor tables - and the caches below replace (grow) or clear them
+# later.  A buffer the eager warm-up allocated (the model's persistent branch streams: same cache key in warm-up, capture
+# and later eager calls) would then go back to the caching allocator while replays still write into it.  While a
+# capture is open every such buffer handed out is also appended to the list of the graph object that captures
+# (`owned_by_capture`): the cache may drop its reference, the memory lives as long as the graph.
+_CAPTURE_KEEP: Optional[list] = None
+
+
+class owned_by_capture:
+    """`with ops.owned_by_capture(keep): with torch.cuda.graph(g): ...` - `keep` (a list the graph's owner holds for the
+    graph's lifetime) receives every cached buffer handed out to a capturing stream meanwhile."""
+
+    def __init__(self, keep: list):
+        self.keep = keep
+
+    def __enter__(self):
+        global _CAPTURE_KEEP
+        self._prev, _CAPTURE_KEEP = _CAPTURE_KEEP, self.keep
+        return self.keep
+
+    def __exit__(self, *exc):
+        global _CAPTURE_KEEP
+        _CAPTURE_KEEP = self._prev
+        return False
+
+
+def keep_for_capture(t: torch.Tensor) -> torch.Tensor:
+    """Register a host-cached buffer with the open capture, if the current stream is capturing (branch streams forked
+    into the capture included).  Returns t."""
+    if _CAPTURE_KEEP is not None and torch.cuda.is_current_stream_capturing():
+        _CAPTURE_KEEP.append(t)
+    return t
+
+
 def workspace(nbytes: int, device, tag: str = "ws") -> torch.Tensor:
     """Grow-only per-(device, stream, tag) scratch buffer (kernels never allocate)."""
     key = (str(device), _stream(), tag)
@@ -126,7 +161,7 @@ def workspace(nbytes: int, device, tag: str = "ws") -> torch.Tensor:
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 1 << 16), dtype=torch.uint8, device=device)
         _WS[key] = buf
-    return buf
+    return keep_for_capture(buf)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -527,6 +562,7 @@ def colreduce_entries(entries) -> None:
             if len(_COLRED_DESC) > 32:
                 _COLRED_DESC.clear()
             desc = _COLRED_DESC[(dev, rows)] = torch.tensor(rows, dtype=torch.int64).to(dev)
+        keep_for_capture(desc)
         with torch.cuda.device(dev):
             colreduce_batched(desc, len(es), max(int(c) for _, _, c, _, _ in es))
 

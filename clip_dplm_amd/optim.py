@@ -152,7 +152,9 @@ class FusedAdamW:
         # hipGraph replay (training.GraphedTrainStep): what changes from step to step - lr and the two bias corrections -
         # is read by the kernel from this device array instead of from launch arguments
         self.hyper = None
-        self._hyper_host = None
+        self._hyper_host = None          # [slots, 4] host rows of prepare_step's uploads (pinned: a ring, see there)
+        self._hyper_done = None          # per slot: event recorded after the slot's upload was enqueued
+        self._hyper_slot = 0
         self._graph_body = False
         if self.overlap:
             for b, (_, _, root) in enumerate(self.flat.buckets):
@@ -205,15 +207,29 @@ class FusedAdamW:
                     dst.copy_(out)
         self._reduced[b] = True
 
+    # host rows prepare_step() may have in flight: with this many replays issued ahead of the GPU the host waits for the
+    # oldest upload (one 16-byte row each)
+    HYPER_SLOTS = 64
+
     def enable_device_hyper(self) -> None:
         """Keep {lr, 1 - beta1^t, sqrt(1 - beta2^t)} in device memory (see prepare_step)."""
         if self.hyper is None:
             self.hyper = torch.zeros(3, dtype=torch.float32, device=self.flat.data.device)
-            self._hyper_host = torch.zeros(3, dtype=torch.float32).pin_memory() if self.flat.data.is_cuda else torch.zeros(3)
+            if self.flat.data.is_cuda:
+                self._hyper_host = torch.zeros(self.HYPER_SLOTS, 4, dtype=torch.float32).pin_memory()
+                self._hyper_done = [None] * self.HYPER_SLOTS
+            else:
+                self._hyper_host = torch.zeros(1, 4)
+            self._hyper_slot = 0
 
     def prepare_step(self, lr: Optional[float] = None) -> None:
         """Host side of one optimiser step when the step itself is a hipGraph replay: count the step and upload its
-        hyper-parameters (bias corrections in double, as torch.optim.AdamW computes them)."""
+        hyper-parameters (bias corrections in double, as torch.optim.AdamW computes them).
+
+        The upload is an asynchronous copy from pinned host memory, and the DMA reads that memory when the copy RUNS: a
+        host that issues replays ahead of the GPU must not rewrite a row an earlier copy has yet to read.  Each step
+        writes the next row of a ring and records an event after its copy; the host waits on a row's event only when
+        the ring comes round to it again, i.e. when it is HYPER_SLOTS steps ahead of the GPU."""
         self.enable_device_hyper()
         self.step_count += 1
         lr = self.lr if lr is None else lr
@@ -221,10 +237,20 @@ class FusedAdamW:
         # exactly what clipk_adamw_step computes from its (float) arguments: betas rounded to f32 first, pow / sqrt in double
         b1 = struct.unpack("f", struct.pack("f", self.betas[0]))[0]
         b2 = struct.unpack("f", struct.pack("f", self.betas[1]))[0]
-        self._hyper_host[0] = lr
-        self._hyper_host[1] = 1.0 - math.pow(b1, float(t))
-        self._hyper_host[2] = math.sqrt(1.0 - math.pow(b2, float(t)))
-        self.hyper.copy_(self._hyper_host, non_blocking=True)
+        i = self._hyper_slot
+        self._hyper_slot = (i + 1) % self._hyper_host.shape[0]
+        done = self._hyper_done[i] if self._hyper_done is not None else None
+        if done is not None:
+            done.synchronize()                   # (only when HYPER_SLOTS uploads are still queued)
+        row = self._hyper_host[i]
+        row[0] = lr
+        row[1] = 1.0 - math.pow(b1, float(t))
+        row[2] = math.sqrt(1.0 - math.pow(b2, float(t)))
+        self.hyper.copy_(row[:3], non_blocking=True)
+        if self._hyper_done is not None:
+            if done is None:
+                done = self._hyper_done[i] = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(self.hyper.device))
 
     @torch.no_grad()
     def step(self, lr: Optional[float] = None) -> torch.Tensor:

@@ -171,6 +171,8 @@ class GraphedTrainStep:
     captured kernel its Philox offset through device memory and advances it per replay.
 
     Inputs of another shape than the example (the short last batch of an epoch) run the same step eagerly (`eager_step`).
+    __call__ never waits for the GPU: the host may issue many replays ahead of it (see FusedAdamW.prepare_step), and the
+    host-cached buffers the captured launches use stay allocated for the graph's lifetime (`ops.owned_by_capture`).
     Restrictions: single process (no collectives).  The returned loss of a replay is a static device tensor overwritten by
     the next replay (`.item()` / `.clone()` it to keep it)."""
 
@@ -197,7 +199,8 @@ class GraphedTrainStep:
         try:
             optimizer.prepare_step()                       # the captured step is a real one, too
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            self._owned = []                               # cached workspaces / tables the graph's launches hold
+            with ops.owned_by_capture(self._owned), torch.cuda.graph(self.graph):
                 self.static_loss = self._body()
                 if self.drop_epoch is not None:
                     self.drop_epoch.add_(1)                # after the backward: the next replay draws new masks
@@ -247,4 +250,8 @@ class GraphedTrainStep:
             dst.copy_(src, non_blocking=True)
         self.opt.prepare_step(lr)
         self.graph.replay()
+        # the replay updated the weights behind the host's back, and the copies it rebuilt at their point of use (padded /
+        # concatenated operands, fused views) hold the weights from BEFORE its update: the next eager forward (an
+        # evaluation) must rebuild its own.  A host counter - no sync, the replays themselves are unaffected.
+        KF.mark_weights_dirty()
         return self.static_loss

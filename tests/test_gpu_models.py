@@ -627,6 +627,301 @@ def test_graphed_train_step_with_active_dropout_draws_new_masks_per_replay(dev, 
         assert abs(no_drop(rna, rbp)[2].item() - want[0]) > 1e-4       # the dropout was really active
 
 
+# ---- GraphedTrainStep / GraphedTransport the way a training loop drives them: no host sync between replays, eager
+# evaluations between epochs, host caches that let go of buffers a captured graph still uses
+
+def _notebook_model(dev, precision, dual=False, dims=(40, 128, 64)):
+    import clip_dplm_amd as K
+    torch.manual_seed(1)
+    m = K.RNARBPCLIPModel(rna_dim=dims[0], rbp_dim=dims[1], projection_dim=dims[2], dropout=0.0, precision=precision)
+    for mod in m.modules():
+        if isinstance(mod, torch.nn.Dropout):
+            mod.p = 0.0
+    m.dual_stream = dual
+    return m.to(dev).train()
+
+
+def _notebook_batches(dev, n, B=32, seed=3, dims=(40, 128)):
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for _ in range(n):
+        rna, rbp = torch.randn(B, 6, dims[0], generator=g), torch.randn(B, 9, dims[1], generator=g)
+        rna[5, 4:] = float("nan")
+        rbp[7, 3:] = float("nan")
+        out.append((rna.to(dev), rbp.to(dev)))
+    return out
+
+
+def _gate(ms: float = 100.0):
+    """Hold the current stream back by about `ms` behind a spin kernel and return an event recorded after it: while it
+    has not completed, nothing enqueued later has started.  torch.cuda._sleep counts GPU clock cycles at a rate that
+    is not documented for gfx950, so it is timed here first."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda._sleep(1 << 16)
+    cycles, elapsed = 1 << 20, 0.0
+    for _ in range(4):
+        torch.cuda.synchronize()
+        e0.record()
+        torch.cuda._sleep(cycles)
+        e1.record()
+        e1.synchronize()
+        elapsed = e0.elapsed_time(e1)
+        if elapsed >= 2.0:
+            break
+        cycles *= 8
+    assert elapsed > 0.0, "torch.cuda._sleep did not spin"
+    torch.cuda._sleep(int(cycles * ms / elapsed))
+    gate = torch.cuda.Event()
+    gate.record()
+    return gate
+
+
+@pytest.mark.parametrize("lr_mode", ["schedule", "constant"])
+@pytest.mark.parametrize("precision,two_streams", [("f32", False), ("bf16", False), ("f32", True), ("bf16", True)])
+def test_graphed_train_step_without_host_syncs_equals_eager_steps(dev, precision, two_streams, lr_mode):
+    """GraphedTrainStep driven as a training loop (and bench.py's timed loops) drive it: the host issues every replay
+    without waiting for the GPU.  A spin kernel holds the GPU back (~100 ms) so that the replays - inputs copied in,
+    AdamW's per-step scalars uploaded from pinned host memory (FusedAdamW.prepare_step), graph launched - are queued
+    before the first of them runs; the event after the spin must still be pending after at least the first 4 of the 24
+    replays were issued (all 24 in f32), or the test did not cover the run-ahead case.  Then, bit for bit against the same
+    steps issued eagerly: every loss, the weights, both
+    Adam moments and the step count.  lr_mode "schedule": the learning rate changes every step; "constant": lr=None
+    (bench.py's pattern), where only the bias corrections change."""
+    import clip_dplm_amd as K
+    from clip_dplm_amd.training import GraphedTrainStep
+    n = 24
+    batches = _notebook_batches(dev, n)
+    lrs = [1e-3 * (1 + i % 7) for i in range(n)] if lr_mode == "schedule" else [None] * n
+    me = _notebook_model(dev, precision)
+    oe = K.FusedAdamW(me, lr=1e-3, weight_decay=0.01, max_grad_norm=1.0)
+    eager = []
+    for (rna, rbp), lr in zip(batches, lrs):
+        oe.zero_grad()
+        loss = me(rna, rbp)[2]
+        loss.backward()
+        oe.step(lr=lr)
+        eager.append(loss.detach().clone())
+    mg = _notebook_model(dev, precision, two_streams)
+    og = K.FusedAdamW(mg, lr=1e-3, weight_decay=0.01, max_grad_norm=1.0)
+    step = GraphedTrainStep(mg, og, lambda a, b: mg(a, b)[2], batches[0])
+    torch.cuda.synchronize()
+    gate = _gate(100.0)
+    got, closed = [], []
+    for (rna, rbp), lr in zip(batches, lrs):          # no .item(), no synchronize, no .cpu() in here
+        got.append(step(rna, rbp, lr=lr).clone())
+        closed.append(not gate.query())                # (an event query does not wait)
+    torch.cuda.synchronize()
+    # replays the host issued while the GPU was still held back.  The runtime's queue takes a bounded number of launches:
+    # measured on MI355X, a bf16 replay fills it after 8 replays on one stream (16 with two branches), and the host then
+    # waits inside the graph launch until the GPU drains it; f32 replays queue all 24
+    lead = closed.index(False) if False in closed else n
+    assert lead >= 4, f"the GPU passed the gate after {lead} replays had been issued: run-ahead not covered ({closed})"
+    assert og.step_count == oe.step_count == n
+    bad = [i for i in range(n) if not torch.equal(got[i], eager[i])]
+    assert not bad, [(i, got[i].item(), eager[i].item()) for i in bad[:6]]
+    assert torch.equal(og.flat.data, oe.flat.data)
+    assert torch.equal(og.m, oe.m) and torch.equal(og.v, oe.v)
+
+
+@pytest.mark.parametrize("model_name", ["trimodal", "protein_rna"])
+def test_eager_evaluation_after_graph_replays_sees_the_current_weights(dev, model_name):
+    """The notebook's epoch loop (rna_clip_codes.ipynb:2040-2089): train with replays of the captured step, evaluate
+    eagerly, train again, evaluate again.  The bf16 models rebuild some weight operands at their point of use inside the
+    graph - the padded first Linears of ContrastiveModel (gene_dim + 1 is odd), ESM's fused qkv view - so after a replay
+    those copies hold the weights from before its update, and the eager forward that follows must not reuse them.  Both
+    evaluations (embeddings and loss) bit-identical to an eager twin that made the same steps and evaluations."""
+    import clip_dplm_amd as K
+    from clip_dplm_amd.training import GraphedTrainStep
+    if model_name == "trimodal":
+        z, _ = load("trimodal_model.npz")
+        inputs = tuple(t(z, k, dev) for k in ("cell_state", "connectivity", "gene_esm", "gene_values", "protein_emb"))
+
+        def build():
+            torch.manual_seed(2)
+            return K.ContrastiveModel(21, 64, projection_dim=64, esm_dim=40, dropout=0.0, precision="bf16")
+        loss_of = lambda m: (lambda *x: m(*x)["loss"])
+
+        def evaluate(m):
+            o = m(*inputs)
+            return [o[k] for k in ("cell_embed", "pert_embed", "protein_embed", "loss")]
+    else:
+        from clip_dplm_amd.encoders import ESM2_SHAPES
+        ESM2_SHAPES["test_tiny"] = (2, 96, 4, 384)
+        g = torch.Generator().manual_seed(7)
+        ids = torch.randint(4, 24, (16, 32), generator=g)
+        ids[:, 0], ids[:, -1] = 0, 2
+        inputs = (torch.randn(16, 32, 64, generator=g).to(dev), ids.to(dev))
+
+        def build():
+            torch.manual_seed(2)
+            return K.ProteinRNACLIP(esm="test_tiny", rna_dim=64, rna_layers=1, rna_heads=8, rna_ffn=128, projection_dim=64)
+        loss_of = lambda m: (lambda rna, ids: m.loss(rna, ids))
+
+        def evaluate(m):
+            return [*m.embed(*inputs), m.loss(*inputs)]
+
+    def prepared():
+        m = build()
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.Dropout):
+                mod.p = 0.0
+        m = m.to(dev).train()
+        return m, K.FusedAdamW(m, lr=1e-3, weight_decay=0.01, max_grad_norm=1.0)
+
+    def run(m, step):
+        evals = []
+        for _ in range(2):
+            for _ in range(3):
+                step()
+            m.eval()
+            with torch.no_grad():
+                evals.append([x.clone() for x in evaluate(m)])
+            m.train()
+        torch.cuda.synchronize()
+        return evals
+
+    me, oe = prepared()
+
+    def eager_step():
+        oe.zero_grad()
+        loss_of(me)(*inputs).backward()
+        oe.step()
+    want = run(me, eager_step)
+    mg, og = prepared()
+    graphed = GraphedTrainStep(mg, og, loss_of(mg), inputs)
+    got = run(mg, lambda: graphed(*inputs))
+    for e, (a, b) in enumerate(zip(got, want)):
+        diff = [i for i, (x, y) in enumerate(zip(a, b)) if not torch.equal(x, y)]
+        assert not diff, (f"evaluation {e}: outputs {diff} differ", [(a[i] - b[i]).abs().max().item() for i in diff])
+    assert torch.equal(og.flat.data, oe.flat.data)
+
+
+def _drop_and_refill(snap, streams, dev):
+    """After a host cache let go of buffers: which entries of the `ops._WS` snapshot `snap` (key -> (pointer, bytes,
+    weakref)) were replaced or removed, which of those are no longer referenced anywhere (back in the caching allocator),
+    and sentinels - filled with 0x5A, allocated on the stream the buffer belonged to, at its size - until one covers the
+    first byte of each such freed buffer.  torch.cuda.empty_cache() is never called: freed blocks stay mapped."""
+    from clip_dplm_amd import ops
+    by_handle = {s.cuda_stream: s for s in streams}
+    dropped = [(k, p, n, r) for k, (p, n, r) in snap.items() if k not in ops._WS or ops._WS[k].data_ptr() != p]
+    freed = [(k, p, n) for k, p, n, r in dropped if r() is None and k[1] in by_handle]
+    sentinels, covered = [], []
+    for k, p, n in freed:
+        with torch.cuda.stream(by_handle[k[1]]):
+            for _ in range(64):
+                x = torch.full((n,), 0x5A, dtype=torch.uint8, device=dev)
+                sentinels.append(x)
+                if x.data_ptr() <= p < x.data_ptr() + n:
+                    covered.append(k)
+                    break
+    torch.cuda.synchronize()
+    return [k for k, _, _, _ in dropped if k[1] in by_handle], freed, sentinels, covered
+
+
+def _ws_snapshot():
+    import weakref
+    from clip_dplm_amd import ops
+    return {k: (v.data_ptr(), v.numel(), weakref.ref(v)) for k, v in ops._WS.items()}
+
+
+def _clear_host_caches():
+    """What the caches do by themselves when they reach their size limits."""
+    from clip_dplm_amd import functional as KF
+    from clip_dplm_amd import ops
+    ops._WS.clear()
+    ops._COLRED_DESC.clear()
+    KF._LN_PART.clear()
+    KF._BATCH_DESC.clear()
+
+
+@pytest.mark.parametrize("variant", ["bigger_eval_batch", "caches_cleared"])
+def test_graphed_train_step_survives_its_host_caches_letting_go(dev, variant):
+    """The benchmarked notebook configuration (RNARBPCLIPModel at the notebook's widths 120 / 1280 / 512, exact f32,
+    towers on two branch streams) captured at B = 32.  The branch streams persist: warm-up, capture and later eager calls
+    all take their `ops.workspace` buffers under the same keys, so the graph's launches hold pointers to buffers the eager
+    warm-up allocated.  Then the host caches let go of them - "bigger_eval_batch": eager no_grad evaluations at B = 256
+    and B = 64 (the exact-f32 products of up to 64 rows keep partial tiles in a workspace, which grows at 64 rows);
+    "caches_cleared": `ops._WS`, `ops._COLRED_DESC`,
+    `functional._LN_PART` and `functional._BATCH_DESC` emptied, as at their size limits.  Memory that went back to the
+    allocator is handed to sentinels; three replays must leave them untouched and give the losses, evaluations and weights
+    of an eager twin that made the same calls."""
+    import clip_dplm_amd as K
+    from clip_dplm_amd.training import GraphedTrainStep
+    dims = (120, 1280, 512)
+    batches = _notebook_batches(dev, 3, dims=dims[:2])
+    evals = _notebook_batches(dev, 1, B=256, seed=5, dims=dims[:2]) + _notebook_batches(dev, 1, B=64, seed=6, dims=dims[:2])
+
+    def evaluate(m):
+        if variant != "bigger_eval_batch":
+            return []
+        m.eval()
+        with torch.no_grad():
+            out = [[x.clone() for x in m(*e)] for e in evals]
+        m.train()
+        return out
+    me = _notebook_model(dev, "f32", dims=dims)
+    oe = K.FusedAdamW(me, lr=1e-3, weight_decay=0.01, max_grad_norm=1.0)
+    want_evals = evaluate(me)
+    want = []
+    for rna, rbp in batches:
+        oe.zero_grad()
+        loss = me(rna, rbp)[2]
+        loss.backward()
+        oe.step()
+        want.append(loss.detach().clone())
+    mg = _notebook_model(dev, "f32", dual=True, dims=dims)
+    og = K.FusedAdamW(mg, lr=1e-3, weight_decay=0.01, max_grad_norm=1.0)
+    step = GraphedTrainStep(mg, og, lambda a, b: mg(a, b)[2], batches[0])
+    torch.cuda.synchronize()
+    snap = _ws_snapshot()
+    got_evals = evaluate(mg)
+    if variant == "caches_cleared":
+        _clear_host_caches()
+    dropped, freed, sentinels, covered = _drop_and_refill(snap, mg._streams, dev)
+    assert dropped, "no workspace of the branch streams was let go: the test did not reach the hazard"
+    assert len(covered) == len(freed), ("freed workspaces never handed out again", freed, covered)
+    got = [step(rna, rbp).clone() for rna, rbp in batches]
+    torch.cuda.synchronize()
+    assert all(bool((s == 0x5A).all()) for s in sentinels), "a replay wrote into memory its graph no longer owned"
+    assert all(torch.equal(a, b) for a, b in zip(got, want)), ([x.item() for x in got], [x.item() for x in want])
+    assert torch.equal(og.flat.data, oe.flat.data)
+    for a, b in zip(got_evals, want_evals):
+        assert all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("variant", ["bigger_eval_batch", "caches_cleared"])
+def test_graphed_transport_survives_its_host_caches_letting_go(dev, variant):
+    """icnn.GraphedTransport with the three maps on branch streams (`multi_stream`), captured at B = 64: its launches hold
+    the branch streams' LayerNorm-backward workspaces from the eager warm-up.  An eager evaluation at B = 4096 grows them
+    ("bigger_eval_batch"), or the caches are emptied ("caches_cleared"); memory that went back to the allocator is handed
+    to sentinels, and replays on two batches must leave them untouched and equal the one-stream eager outputs."""
+    from clip_dplm_amd import icnn
+    torch.manual_seed(4)
+    model = icnn.create_transport_system(96, 96, 96, hidden_dims=[96, 96, 48]).to(dev).eval()
+    g = torch.Generator().manual_seed(5)
+    mk = lambda B: tuple(torch.randn(B, 96, generator=g).to(dev) for _ in range(3))
+    x1, x2, big = mk(64), mk(64), mk(4096)
+    with torch.no_grad():
+        ref = [{k: v.clone() for k, v in model(*x).items()} for x in (x1, x2, big)]
+    model.multi_stream = True
+    graphed = icnn.GraphedTransport(model, *x1)
+    torch.cuda.synchronize()
+    snap = _ws_snapshot()
+    if variant == "bigger_eval_batch":
+        with torch.no_grad():
+            out = model(*big)
+            assert all(torch.equal(out[k], ref[2][k]) for k in ref[2])
+    else:
+        _clear_host_caches()
+    dropped, freed, sentinels, covered = _drop_and_refill(snap, model._streams, dev)
+    assert dropped, "no workspace of the branch streams was let go: the test did not reach the hazard"
+    assert len(covered) == len(freed), ("freed workspaces never handed out again", freed, covered)
+    for x, r in ((x1, ref[0]), (x2, ref[1]), (x1, ref[0])):
+        o = graphed(*x)
+        torch.cuda.synchronize()
+        assert all(torch.equal(o[k], r[k]) for k in r), [k for k in r if not torch.equal(o[k], r[k])]
+    assert all(bool((s == 0x5A).all()) for s in sentinels), "a replay wrote into memory its graph no longer owned"
+
 @pytest.mark.parametrize("model_name", ["notebook", "trimodal", "pair_clip"])
 def test_towers_on_side_streams_give_the_same_step(dev, model_name):
     """`RNARBPCLIPModel.dual_stream` / `ContrastiveModel.multi_stream`: the towers (independent up to the loss,
