@@ -20,6 +20,8 @@ from .optim import FlatParams, FusedAdamW, cosine_annealing_lr
 from .training import (CosineAnnealingLR, EarlyStopping, GraphedTrainStep, evaluate_model, load_checkpoint, save_checkpoint,
                        train_epoch)
 from . import training
+from .retrieval import EmbeddingIndex, evaluate_retrieval, metrics_from_ranks, retrieval_metrics
+from . import retrieval
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -31,4 +33,5 @@ __all__ = [
     "cosine_annealing_lr", "CosineAnnealingLR", "GraphedTrainStep", "EarlyStopping", "train_epoch", "evaluate_model", "save_checkpoint",
     "load_checkpoint", "ESMConfig", "ESMIntegration", "ESMOutput", "BiologicalDataType", "ProteinProjection",
     "GeneProjection", "create_esm_integration", "get_embeddings_batch", "MemoryQueue", "contrastive_loss", "set_linear_precision",
+    "retrieval", "EmbeddingIndex", "evaluate_retrieval", "retrieval_metrics", "metrics_from_ranks",
 ]

@@ -65,6 +65,10 @@ SIGNATURES = {
     "clipk_simce_grad_pairs": (_i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _vp, _f, _f, _f, _vp, _vp,
                                     _vp, _sz, _vp]),
     "clipk_sim_logits": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i64, _vp]),
+    "clipk_sim_topk_workspace": (_sz, [_i, _i, _i, _i]),
+    "clipk_sim_topk": (_i, [_vp, _i, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_sim_rank_workspace": (_sz, [_i, _i, _i]),
+    "clipk_sim_rank": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "clipk_ce_logits_lse": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "clipk_ce_logits_bwd": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp]),
     "clipk_transpose_scale_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
@@ -117,7 +121,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 6          # CLIPK_ABI_VERSION of the library these signatures / the GemmArgs layout were written for
+ABI_VERSION = 7          # CLIPK_ABI_VERSION of the library these signatures / the GemmArgs layout were written for
 
 
 def load() -> C.CDLL:

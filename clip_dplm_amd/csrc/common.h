@@ -5,7 +5,7 @@
 #include <stdint.h>
 #include "../../include/clipk.h"
 
-#define CLIPK_ABI_VERSION 6
+#define CLIPK_ABI_VERSION 7
 #define WAVE 64
 
 // Kernel-selection options (core.hip): set explicitly through clipk_set_option(), never read from the environment.
@@ -28,6 +28,7 @@ enum clipk_opt {
   OPT_GEMM_ABL,            // CLIPK_EXPERIMENTS builds only: timing ablations that change results
   OPT_ATTN_ROW_STORES,     // whole-head forward: 2 = rotated q / k rows written back four lanes to a row from LDS (measured slower; default off)
   OPT_GEMM_F32_SPLITS,     // skinny exact-f32 Linear: cross-workgroup splits of the contraction (0 = auto, 1 .. 8)
+  OPT_RETRIEVAL_SPLITS,    // clipk_sim_topk / clipk_sim_rank: key-range splits (0 = auto, n > 0: n, capped by the tile count)
   OPT_COUNT
 };
 int clipk_opt_get(int which);      // core.hip

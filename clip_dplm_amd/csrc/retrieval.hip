@@ -1,0 +1,392 @@
+// retrieval.hip — cross-modal retrieval over an embedding gallery without materialising the logits:
+//   clipk_sim_topk : the k best keys of every query,  S[i,j] = scale <X_i, Y_j>
+//   clipk_sim_rank : the 0-based rank of every query's labelled positive, and its score
+// Both walk the tiled exact-f32 similarity block of the fused softmax statistics (sim_tile.h: 64 queries per workgroup,
+// 64-key tiles, keys on the MFMA rows, queries on the lanes, key-range splits on grid y) and replace its epilogue.
+//
+// Ordering contract: score descending, equal scores (IEEE: -0 == +0) by the lower key index.  It is a total order, so the
+// top-k set, its order and every rank are bitwise independent of the split plan.
+//
+// Top-k: lane (li, h) of key-wave wm owns 16 of every 64-key tile for its query and meets its keys in ascending index
+// order; it keeps the best KP (k rounded up to 1 / 8 / 16 / 32 / 64) in registers, sorted.  Per tile the common case is
+// one max over the 16 scores and one compare with the list's last entry; only a lane whose tile holds a better score
+// takes the insertion path.  Each of the four owners of a query writes its list to the workspace and topk_merge_kernel
+// reduces the 4 x ksplit lists per query in a fixed tree (16 lists per workgroup, rank of every candidate by binary search
+// in the other sorted lists).
+//
+// Rank: one extra tile per workgroup computes S[i, l_i] from a gathered tile whose key rows are the labels' rows, with
+// the same K-loop and the same query rows, so it has the bits the counting loop sees at that key; every score then costs
+// one compare pair against it.  Per-split counts are summed by sim_rank_finalize.
+#include "common.h"
+#include "sim_tile.h"
+#include <limits.h>
+#include <math.h>
+
+namespace {
+
+constexpr int RQ = 64, RK = 64;          // queries per workgroup, keys per tile
+constexpr int RBK = 32;                  // K-step of the tile loop (as the LSE pass: 16 MFMAs per wave between barriers)
+constexpr int MG = 16;                   // lists merged by one workgroup of the finalize tree
+constexpr int EMPTY = INT_MAX;           // key index of an unfilled list slot (its score is -inf)
+
+__device__ __forceinline__ int key_off(int r) { return (r & 3) + 8 * (r >> 2); }   // keyrow32(r, h) - 4 h
+
+// stage rows of the workgroup's 64 queries (clamped: rows past Mx are computed and dropped)
+__device__ __forceinline__ void query_rows(const float* (&xrows)[RBK / 16], const float* X, int Mx, int P, int q0, int tid) {
+#pragma unroll
+  for (int i = 0; i < RBK / 16; ++i) {
+    int q = q0 + (tid + i * 256) / (RBK / 4); q = q < Mx ? q : Mx - 1;
+    xrows[i] = X + (long)q * P;
+  }
+}
+__device__ __forceinline__ void key_rows(const float* (&yrows)[RBK / 16], const float* Y, int Ny, int P, int j0, int tid) {
+#pragma unroll
+  for (int i = 0; i < RBK / 16; ++i) {
+    int j = j0 + (tid + i * 256) / (RBK / 4); j = j < Ny ? j : Ny - 1;
+    yrows[i] = Y + (long)j * P;
+  }
+}
+
+// sorted insert of (v, j), v > s[KP - 1]; j is larger than every index in the list, so v goes after its equals
+template <int KP>
+__device__ __forceinline__ void list_insert(float (&s)[KP], int (&ix)[KP], float v, int j) {
+#pragma unroll
+  for (int t = KP - 1; t > 0; --t) {
+    if (s[t - 1] < v) { s[t] = s[t - 1]; ix[t] = ix[t - 1]; }
+    else if (s[t] < v) { s[t] = v; ix[t] = j; }
+  }
+  if (s[0] < v) { s[0] = v; ix[0] = j; }
+}
+
+struct TKP {
+  const float* X; int Mx;
+  const float* Y; int Ny;
+  int P; float scale;
+  float* part_s; int* part_i;            // [4 ksplit][Mx][KP]
+  int tiles_per_split, ntiles;
+};
+
+template <int KP>
+__global__ __launch_bounds__(256, 2) void sim_topk_kernel(const TKP p) {
+  __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (RBK + 4)];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid >> 1, wn = wid & 1;
+  const int li = lane & 31, h = lane >> 5;
+  const int q0 = blockIdx.x * RQ, ks = blockIdx.y;
+  const int P = p.P, Ny = p.Ny;
+  const float scale = p.scale;
+  const float* xrows[RBK / 16];
+  query_rows(xrows, p.X, p.Mx, P, q0, tid);
+  float s[KP];
+  int ix[KP];
+#pragma unroll
+  for (int t = 0; t < KP; ++t) { s[t] = -INFINITY; ix[t] = EMPTY; }
+  const int t_beg = ks * p.tiles_per_split;
+  int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
+
+  for (int kt = t_beg; kt < t_end; ++kt) {
+    const int j0 = kt * RK;
+    const float* yrows[RBK / 16];
+    key_rows(yrows, p.Y, Ny, P, j0, tid);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    s_tile<RBK>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
+    const int kb = j0 + wm * 32 + 4 * h;                                  // key of accumulator row r: kb + key_off(r)
+    float tmax = -INFINITY;
+    if (j0 + RK <= Ny) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, scale * acc[r]);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) if (kb + key_off(r) < Ny) tmax = fmaxf(tmax, scale * acc[r]);
+    }
+    if (tmax > s[KP - 1]) {                                               // rare once the list is full
+      unsigned m = 0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (kb + key_off(r) < Ny && scale * acc[r] > s[KP - 1]) m |= 1u << r;
+      while (m) {                                                         // ascending r = ascending key
+        const int r = __builtin_ctz(m);
+        m &= m - 1;
+        float a = acc[0];
+#pragma unroll
+        for (int rr = 1; rr < 16; ++rr) a = (r == rr) ? acc[rr] : a;     // no dynamic register indexing
+        const float v = scale * a;
+        if (v > s[KP - 1]) list_insert<KP>(s, ix, v, kb + key_off(r));
+      }
+    }
+  }
+
+  const int qg = q0 + wn * 32 + li;
+  if (qg < p.Mx) {
+    const long o = ((long)(ks * 4 + wm * 2 + h) * p.Mx + qg) * KP;
+#pragma unroll
+    for (int t = 0; t < KP; ++t) { p.part_s[o + t] = s[t]; p.part_i[o + t] = ix[t]; }
+  }
+}
+
+// One round of the finalize tree: workgroup (q, g) merges lists [g MG, g MG + MG) of query q (each sorted, KP entries)
+// into list g of `out_*`, or - last round, one group - into the k results.  The rank of a candidate is the number of
+// candidates that precede it in the order, summed over the lists by binary search; real keys are distinct, so the
+// ranks of real candidates are exactly 0 .. R - 1.
+template <int KP>
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float* in_s, const int* in_i, int L, int Mx,
+                                                         float* out_s, int* out_i, float* fin_s, int64_t* fin_i,
+                                                         int k, int Ny) {
+  __shared__ float ss[MG * KP];
+  __shared__ int si[MG * KP];
+  __shared__ int nreal;
+  const int tid = threadIdx.x, q = blockIdx.x, g = blockIdx.y;
+  const int l0 = g * MG, nl = (L - l0) < MG ? (L - l0) : MG, n = nl * KP;
+  if (tid == 0) nreal = 0;
+  for (int e = tid; e < n; e += 256) {
+    const long o = ((long)(l0 + e / KP) * Mx + q) * KP + e % KP;
+    ss[e] = in_s[o]; si[e] = in_i[o];
+  }
+  __syncthreads();
+  int mine = 0;
+  for (int e = tid; e < n; e += 256) mine += si[e] != EMPTY;
+  if (mine) atomicAdd(&nreal, mine);
+  __syncthreads();
+  const int R = nreal, kout = fin_s ? k : KP;
+  for (int e = tid; e < n; e += 256) {
+    const int j = si[e];
+    if (j == EMPTY) continue;
+    const float v = ss[e];
+    int rank = 0;
+    for (int l = 0; l < nl; ++l) {
+      int lo = 0, hi = KP;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const float w = ss[l * KP + mid];
+        if (w > v || (w == v && si[l * KP + mid] < j)) lo = mid + 1; else hi = mid;
+      }
+      rank += lo;
+    }
+    if (rank < kout) {
+      if (fin_s) { fin_s[(long)q * k + rank] = v; fin_i[(long)q * k + rank] = j; }
+      else { const long o = ((long)g * Mx + q) * KP + rank; out_s[o] = v; out_i[o] = j; }
+    }
+  }
+  for (int t = R + tid; t < kout; t += 256) {                             // fewer than k real keys: NaN inputs only
+    if (fin_s) { fin_s[(long)q * k + t] = -INFINITY; fin_i[(long)q * k + t] = t < Ny ? t : Ny - 1; }
+    else { const long o = ((long)g * Mx + q) * KP + t; out_s[o] = -INFINITY; out_i[o] = EMPTY; }
+  }
+}
+
+struct RKP {
+  const float* X; int Mx;
+  const float* Y; int Ny;
+  int P; float scale;
+  const int64_t* labels; int64_t label_offset;
+  int* part_cnt;                         // [ksplit][Mx]
+  float* pos;                            // [Mx]
+  int tiles_per_split, ntiles;
+};
+
+__device__ __forceinline__ int label_of(const int64_t* labels, int64_t label_offset, int q, int Ny) {
+  const int64_t l = labels ? labels[q] : label_offset + q;
+  return (l >= 0 && l < Ny) ? (int)l : -1;                                // -1: out of range, reported as rank -1
+}
+
+__global__ __launch_bounds__(256, 2) void sim_rank_kernel(const RKP p) {
+  __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (RBK + 4)];
+  __shared__ int labl[RQ];
+  __shared__ float posl[RQ];
+  __shared__ int cntl[RQ];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid >> 1, wn = wid & 1;
+  const int li = lane & 31, h = lane >> 5;
+  const int q0 = blockIdx.x * RQ, ks = blockIdx.y;
+  const int P = p.P, Ny = p.Ny;
+  const float scale = p.scale;
+  const float* xrows[RBK / 16];
+  query_rows(xrows, p.X, p.Mx, P, q0, tid);
+  if (tid < RQ) {
+    const int q = q0 + tid;
+    labl[tid] = label_of(p.labels, p.label_offset, q < p.Mx ? q : p.Mx - 1, Ny);
+  }
+  __syncthreads();
+
+  // ---- S[q, l_q]: the gathered tile whose key row kl is the label row of query q0 + kl; its diagonal lies in the
+  // waves with wm == wn, key row li of lane (li, h = (li >> 2) & 1) at accumulator row (li & 3) + 4 (li >> 3)
+  {
+    const float* yrows[RBK / 16];
+#pragma unroll
+    for (int i = 0; i < RBK / 16; ++i) {
+      const int l = labl[(tid + i * 256) / (RBK / 4)];
+      yrows[i] = p.Y + (long)(l < 0 ? 0 : l) * P;
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    s_tile<RBK>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
+    if (wm == wn) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (keyrow32(r, h) == li) posl[wn * 32 + li] = scale * acc[r];
+    }
+    __syncthreads();
+  }
+  const float pv = posl[wn * 32 + li];
+  const int lab = labl[wn * 32 + li];
+  int cnt = 0;
+  const int t_beg = ks * p.tiles_per_split;
+  int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
+
+  for (int kt = t_beg; kt < t_end; ++kt) {
+    const int j0 = kt * RK;
+    const float* yrows[RBK / 16];
+    key_rows(yrows, p.Y, Ny, P, j0, tid);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    s_tile<RBK>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
+    const int kb = j0 + wm * 32 + 4 * h;
+    if (j0 + RK <= Ny) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float sv = scale * acc[r];
+        cnt += (sv > pv) | ((sv == pv) & (kb + key_off(r) < lab));
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float sv = scale * acc[r];
+        const int key = kb + key_off(r);
+        cnt += (key < Ny) & ((sv > pv) | ((sv == pv) & (key < lab)));
+      }
+    }
+  }
+
+  // ---- the four owners of a query: lane halves, then the two key-waves
+  cnt += __shfl_xor(cnt, 32, 64);
+  if (wm == 1 && h == 0) cntl[wn * 32 + li] = cnt;
+  __syncthreads();
+  const int qg = q0 + wn * 32 + li;
+  if (wm == 0 && h == 0 && qg < p.Mx) {
+    p.part_cnt[(long)ks * p.Mx + qg] = cnt + cntl[wn * 32 + li];
+    if (ks == 0) p.pos[qg] = lab >= 0 ? pv : __builtin_nanf("");
+  }
+}
+
+__global__ void sim_rank_finalize(const int* part_cnt, int ksplit, int Mx, const int64_t* labels, int64_t label_offset,
+                                  int Ny, int64_t* rank) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= Mx) return;
+  int64_t r = 0;
+  for (int s = 0; s < ksplit; ++s) r += part_cnt[(long)s * Mx + q];
+  rank[q] = label_of(labels, label_offset, q, Ny) >= 0 ? r : -1;
+}
+
+// plan: one workgroup per (64-query block, key split), >= 2 workgroups per CU (the LSE pass's plan); the option
+// retrieval_splits (> 0) fixes the split count instead
+void plan(int Mx, int Ny, int* nqb, int* ksplit, int* tps, int* ntiles) {
+  *nqb = (Mx + RQ - 1) / RQ;
+  *ntiles = (Ny + RK - 1) / RK;
+  const int opt = clipk_opt_get(OPT_RETRIEVAL_SPLITS);
+  int ks = opt > 0 ? opt : (512 + *nqb - 1) / *nqb;
+  if (ks > 65535) ks = 65535;
+  if (ks > *ntiles) ks = *ntiles;
+  if (ks < 1) ks = 1;
+  *tps = (*ntiles + ks - 1) / ks;
+  *ksplit = (*ntiles + *tps - 1) / *tps;
+}
+
+int kpad(int k) { return k <= 1 ? 1 : k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64; }
+
+bool shape_ok(int Mx, int Ny, int P) { return Mx > 0 && Ny > 0 && P > 0 && Ny <= INT_MAX - RK; }
+
+template <int KP>
+int topk_launch(const float* X, int Mx, const float* Y, int Ny, int P, float scale, int k, float* scores, int64_t* idx,
+                char* ws, hipStream_t st) {
+  TKP p;
+  p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale;
+  int nqb, ksplit;
+  plan(Mx, Ny, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  const int la = 4 * ksplit, lb = (la + MG - 1) / MG;
+  const size_t per_list = (size_t)Mx * KP;
+  float* a_s = reinterpret_cast<float*>(ws);
+  int* a_i = reinterpret_cast<int*>(a_s + la * per_list);
+  float* b_s = reinterpret_cast<float*>(a_i + la * per_list);
+  int* b_i = reinterpret_cast<int*>(b_s + lb * per_list);
+  p.part_s = a_s; p.part_i = a_i;
+  hipLaunchKernelGGL(sim_topk_kernel<KP>, dim3(nqb, ksplit), dim3(256), 0, st, p);
+  int rc = clipk_check_launch();
+  if (rc) return rc;
+  const float* src_s = a_s; const int* src_i = a_i;
+  float* dst_s = b_s; int* dst_i = b_i;
+  for (int L = la;;) {
+    const int groups = (L + MG - 1) / MG;
+    if (groups == 1) {
+      hipLaunchKernelGGL(topk_merge_kernel<KP>, dim3(Mx, 1), dim3(256), 0, st, src_s, src_i, L, Mx,
+                         (float*)nullptr, (int*)nullptr, scores, idx, k, Ny);
+      return clipk_check_launch();
+    }
+    hipLaunchKernelGGL(topk_merge_kernel<KP>, dim3(Mx, groups), dim3(256), 0, st, src_s, src_i, L, Mx, dst_s, dst_i,
+                       (float*)nullptr, (int64_t*)nullptr, k, Ny);
+    if ((rc = clipk_check_launch())) return rc;
+    L = groups;
+    float* ts = const_cast<float*>(src_s); int* ti = const_cast<int*>(src_i);  // ping-pong: A holds >= every later L
+    src_s = dst_s; src_i = dst_i; dst_s = ts; dst_i = ti;
+  }
+}
+
+}  // namespace
+
+extern "C" size_t clipk_sim_topk_workspace(int Mx, int Ny, int P, int k) {
+  if (!shape_ok(Mx, Ny, P) || k < 1 || k > 64 || k > Ny) return 0;
+  int nqb, ksplit, tps, nt;
+  plan(Mx, Ny, &nqb, &ksplit, &tps, &nt);
+  const size_t la = 4 * (size_t)ksplit, lb = (la + MG - 1) / MG;
+  return (la + lb) * (size_t)Mx * kpad(k) * (sizeof(float) + sizeof(int));
+}
+
+extern "C" int clipk_sim_topk(const float* X, int Mx, const float* Y, int Ny, int P, float scale, int k, float* scores,
+                              int64_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!X || !Y || !scores || !idx || !workspace) return CLIPK_ERR_BAD_ARG;
+  if (Mx <= 0 || Ny <= 0 || P <= 0 || k <= 0 || k > Ny) return CLIPK_ERR_BAD_ARG;
+  if (k > 64 || P % 4 || !shape_ok(Mx, Ny, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (!aligned16(X) || !aligned16(Y)) return CLIPK_ERR_BAD_ARG;
+  if (workspace_bytes < clipk_sim_topk_workspace(Mx, Ny, P, k)) return CLIPK_ERR_BAD_ARG;
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  switch (kpad(k)) {
+    case 1: return topk_launch<1>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st);
+    case 8: return topk_launch<8>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st);
+    case 16: return topk_launch<16>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st);
+    case 32: return topk_launch<32>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st);
+    default: return topk_launch<64>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st);
+  }
+}
+
+extern "C" size_t clipk_sim_rank_workspace(int Mx, int Ny, int P) {
+  if (!shape_ok(Mx, Ny, P)) return 0;
+  int nqb, ksplit, tps, nt;
+  plan(Mx, Ny, &nqb, &ksplit, &tps, &nt);
+  return (size_t)ksplit * Mx * sizeof(int);
+}
+
+extern "C" int clipk_sim_rank(const float* X, int Mx, const float* Y, int Ny, int P, float scale, const int64_t* labels,
+                              int64_t label_offset, int64_t* rank, float* pos, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  if (!X || !Y || !rank || !pos || !workspace) return CLIPK_ERR_BAD_ARG;
+  if (Mx <= 0 || Ny <= 0 || P <= 0) return CLIPK_ERR_BAD_ARG;
+  if (P % 4 || !shape_ok(Mx, Ny, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (!labels && (label_offset < 0 || label_offset + Mx > Ny)) return CLIPK_ERR_BAD_ARG;
+  if (!aligned16(X) || !aligned16(Y)) return CLIPK_ERR_BAD_ARG;
+  if (workspace_bytes < clipk_sim_rank_workspace(Mx, Ny, P)) return CLIPK_ERR_BAD_ARG;
+  RKP p;
+  p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale; p.labels = labels; p.label_offset = label_offset;
+  p.part_cnt = static_cast<int*>(workspace); p.pos = pos;
+  int nqb, ksplit;
+  plan(Mx, Ny, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(sim_rank_kernel, dim3(nqb, ksplit), dim3(256), 0, st, p);
+  int rc = clipk_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(sim_rank_finalize, dim3((Mx + 255) / 256), dim3(256), 0, st, (const int*)p.part_cnt, ksplit, Mx,
+                     labels, label_offset, Ny, rank);
+  return clipk_check_launch();
+}

@@ -363,6 +363,61 @@ def sim_logits(x, y, scale):
     return s
 
 
+def _retrieval_args(x, y):
+    for name, t in (("queries", x), ("gallery", y)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 2-D tensor, got shape {tuple(t.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"queries have {x.shape[1]} columns, the gallery {y.shape[1]}")
+    Mx, P = x.shape
+    Ny = y.shape[0]
+    if Mx == 0 or Ny == 0 or P == 0 or P % 4:
+        raise ValueError(f"need non-empty inputs and P % 4 == 0 (Mx={Mx}, Ny={Ny}, P={P})")
+    return Mx, Ny, P
+
+
+def sim_topk(x, y, k: int, scale: Optional[float] = None):
+    """(scores f32 [Mx, k], idx int64 [Mx, k]): the k best keys of S = scale * x y^T per row, score descending, equal
+    scores by the lower index (include/clipk.h: clipk_sim_topk).  scale: host number, None = 1."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    k = int(k)
+    if not 1 <= k <= 64:
+        raise ValueError(f"k must be in [1, 64], got {k}")
+    if k > Ny:
+        raise ValueError(f"k = {k} exceeds the gallery size {Ny}")
+    _need_cuda(x, y)
+    scores = torch.empty((Mx, k), dtype=torch.float32, device=x.device)
+    idx = torch.empty((Mx, k), dtype=torch.int64, device=x.device)
+    lib = _lib()
+    ws = workspace(lib.clipk_sim_topk_workspace(Mx, Ny, P, k), x.device, "retrieval")
+    check(lib.clipk_sim_topk(x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale), k,
+                             scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipk_sim_topk")
+    return scores, idx
+
+
+def sim_rank(x, y, labels=None, label_offset: int = 0, scale: Optional[float] = None):
+    """(rank int64 [Mx], pos f32 [Mx]): 0-based rank of key l_i in row i of S = scale * x y^T under the same order as
+    sim_topk, and S[i, l_i] (include/clipk.h: clipk_sim_rank).  l_i = labels[i] (device int64 [Mx]) or label_offset + i.
+    A label outside [0, Ny) gives rank -1 and pos NaN."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    if labels is not None:
+        if labels.dtype != torch.int64 or labels.shape != (Mx,) or not labels.is_contiguous():
+            raise ValueError(f"labels must be a contiguous int64 tensor of shape ({Mx},)")
+    elif not (0 <= int(label_offset) and int(label_offset) + Mx <= Ny):
+        raise ValueError(f"labels label_offset + i = {label_offset} .. {int(label_offset) + Mx - 1} outside [0, {Ny})")
+    _need_cuda(x, y, labels)
+    rank = torch.empty(Mx, dtype=torch.int64, device=x.device)
+    pos = torch.empty(Mx, dtype=torch.float32, device=x.device)
+    lib = _lib()
+    ws = workspace(lib.clipk_sim_rank_workspace(Mx, Ny, P), x.device, "retrieval")
+    check(lib.clipk_sim_rank(x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale),
+                             ptr(labels), int(label_offset), rank.data_ptr(), pos.data_ptr(), ws.data_ptr(), ws.numel(),
+                             _stream()), "clipk_sim_rank")
+    return rank, pos
+
+
 def ce_logits_lse(S, S2=None, columns=False, label_offset=0):
     """LSE over the rows (optionally of [S | S2]) or the columns of materialised f32 logits + the diagonal logit."""
     _need_cuda(S, S2)

@@ -45,7 +45,7 @@ const char* clipk_status_string(int status);
  * of every option computes the same results: they pick between kernels / schedules that tests and tools/ compare.
  * Names: gemm_kernel (-1 auto, 1 generic, 2 128x128, 3 persistent 256x256, 4 persistent 128x256 with two workgroups per CU), gemm_epi_generic, gemm_bm, gemm_stages,
  * gemm_nwg, gemm_stagger, epi_nt, wgrad_kernel (-1 auto, 2, 3), attn_whole_fwd, attn_fused_bwd (-1 auto, 0, 1),
- * attn_fused_waves (0 auto: 4 waves for head dims <= 32, 8 for 96; 4; 8), attn_row_stores (0, 2: forward write-back of rotated rows from LDS), gemm_f32_splits (0 auto, 1 .. 8: cross-workgroup splits of the skinny f32 Linear), simce_kernel (-1 auto, 1 first-generation, 2 tiled LSE pass).  Unknown name -> CLIPK_ERR_BAD_ARG.  (The reference has no counterpart: its kernels are
+ * attn_fused_waves (0 auto: 4 waves for head dims <= 32, 8 for 96; 4; 8), attn_row_stores (0, 2: forward write-back of rotated rows from LDS), gemm_f32_splits (0 auto, 1 .. 8: cross-workgroup splits of the skinny f32 Linear), simce_kernel (-1 auto, 1 first-generation, 2 tiled LSE pass), retrieval_splits (0 auto, n > 0: key-range splits of clipk_sim_topk / clipk_sim_rank).  Unknown name -> CLIPK_ERR_BAD_ARG.  (The reference has no counterpart: its kernels are
  * ATen's.) */
 int clipk_set_option(const char* name, int value);
 int clipk_get_option(const char* name, int* value);
@@ -186,6 +186,33 @@ int clipk_simce_grad_pairs(const float* E, int nmod, int B, int P, const int* pa
  *   S[Mx,Ny] = scale * X·Y^T, exact f32. */
 int clipk_sim_logits(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale,
                      float* S, int64_t lds, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Retrieval over an embedding gallery, exact-f32 MFMA on the tiling of clipk_simce_lse; the logits never reach HBM.
+ *   S[i,j] = scale * <X[i,:], Y[j,:]>      (X: Mx queries, Y: Ny gallery rows, P columns; scale is a host float)
+ * Order: score descending, equal scores (compared as IEEE values, -0 == +0) by the lower index j.  It is a total order,
+ * so results are bitwise independent of the split plan (option retrieval_splits).  Inputs must be finite; with NaN the
+ * order is unspecified, but indices stay in [0, Ny).
+ * Requirements (both): Mx, Ny, P > 0, P % 4 == 0, X / Y 16-byte aligned; offsets are 64-bit (Ny * P >= 2^31 works).
+ * Anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED; the workspace helpers return 0 for such shapes.
+ *
+ * clipk_sim_topk: scores[i, 0..k) / idx[i, 0..k) = the k best (S[i,j], j) of row i in that order; 1 <= k <= 64, k <= Ny.
+ * Replaces the full cosine-similarity matrix of run1/full.py:157 followed by a top-k / argmax over it, and
+ * logits.argmax(dim=1) at run1/full.py:138,152 (k = 1).  workspace: clipk_sim_topk_workspace(Mx, Ny, P, k) bytes. */
+size_t clipk_sim_topk_workspace(int Mx, int Ny, int P, int k);
+int clipk_sim_topk(const float* X, int Mx, const float* Y, int Ny, int P, float scale, int k,
+                   float* scores /*[Mx,k]*/, int64_t* idx /*[Mx,k]*/, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* clipk_sim_rank: rank[i] = #{j != l_i : S[i,j] > S[i,l_i]} + #{j < l_i : S[i,j] == S[i,l_i]}, pos[i] = S[i,l_i], with
+ * l_i = labels[i] (device int64 [Mx]) or label_offset + i when labels is NULL (then label_offset >= 0 and
+ * label_offset + Mx <= Ny).  rank[i] == 0 exactly when the first-occurrence argmax of row i is l_i: the accuracy
+ * (logits.argmax(dim=1) == arange(B)) of run1/full.py:138,152, the confusion-matrix entries of run1/full.py:265.
+ * pos has the bits the count compares against.  A device label outside [0, Ny) gives rank -1 and pos NaN.
+ * workspace: clipk_sim_rank_workspace(Mx, Ny, P) bytes. */
+size_t clipk_sim_rank_workspace(int Mx, int Ny, int P);
+int clipk_sim_rank(const float* X, int Mx, const float* Y, int Ny, int P, float scale, const int64_t* labels,
+                   int64_t label_offset, int64_t* rank /*[Mx]*/, float* pos /*[Mx]*/, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* Cross-entropy on MATERIALISED logits — the reference's loss call sites take the logits tensor its modules return:
  * F.cross_entropy(logits, arange(B)) at old/ablation.py:16 / run1/full.py:133, the symmetric pair at
