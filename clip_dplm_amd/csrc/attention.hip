@@ -995,32 +995,12 @@ __device__ __forceinline__ bf16x8 tr_frag_off(const char* tile, int off) {
 }
 
 constexpr int FUSED_LMAX = 256;
-#ifdef CLIPK_ATTN_TRACE
-// experiment builds (tools/exp_attn_trace.py): shader-clock stamps (s_memtime) between the phases of the whole-head
-// backward, summed over the heads of workgroup 0 (thread 0) -> cycles per phase and head.  No output depends on them.
-__device__ unsigned long long* g_attn_trace = nullptr;
-__device__ int g_attn_stagger = 0;       // experiment: the second workgroup of each CU starts this x ~3.9 us late
-// (the sums live in 11 x 8 bytes of LDS behind the kernel's own allocation: the sweep has no registers to spare)
-#define ATTN_STAMP(i)                                                                   \
-  do {                                                                                  \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();                         \
-    if (tr_on) atomicAdd(&tr_lds[i], t_ - tr_t);                                        \
-    tr_t = t_;                                                                          \
-  } while (0)
-#else
-#define ATTN_STAMP(i) do { } while (0)
-#endif
 __host__ __device__ constexpr size_t lds_fused(int D) {
   // the bf16 dV image of the epilogue sits behind the dK image inside the dead Q / dO / dS^T region when both fit
   // (D <= 24), behind everything otherwise
   return (size_t)2 * FUSED_LMAX * 64 + 4 * 4096 + (size_t)FUSED_LMAX * (D + 4) * 4 + 2 * FUSED_LMAX * 4 +
          (D > 24 ? (size_t)FUSED_LMAX * 64 : 0);
 }
-#ifdef CLIPK_ATTN_TRACE
-constexpr size_t FUSED_TRACE_LDS = 128;
-#else
-constexpr size_t FUSED_TRACE_LDS = 0;
-#endif
 
 // one head's rows as this thread holds them between the loads and the LDS staging: chunk (tid & 3) of rows
 // (tid >> 2) + (threads / 4) * pass of K, V, Q, dO and O, this thread's lse and the mask bytes of its key columns
@@ -1075,24 +1055,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
     // no branch around the loads (a lane whose chunk is the zero pad re-reads the last real chunk and drops it at
     // staging time): loads under a divergent branch make every later s_waitcnt assume they may not have been issued
     const unsigned int cc = 8u * (ci < cpr ? ci : cpr - 1);
-#ifdef CLIPK_ATTN_HM_PROBE
-    // TIMING-ONLY experiment (tools/exp_attn_headmajor.py): q, k, v and dO addressed as if they were stored head-major
-    // ([B][H][3][L][D] / [B][H][L][D]: a head's rows contiguous).  The bytes read are not the head's: results garbage.
-    const unsigned short* qh = p.qkv + (long)(b_ * H + h_) * 3 * p.L * D;
-    const unsigned short* dh = p.dout + (long)(b_ * H + h_) * p.L * D;
-    const unsigned int LD = (unsigned int)(p.L * D);
-#pragma unroll
-    for (int ps = 0; ps < NPS; ++ps) {
-      int row = ps * (NT / 4) + r0; row = row < L ? row : L - 1;
-      const unsigned int ho = (unsigned int)row * D + cc, oo = (unsigned int)row * HD + cc;
-      R.q[ps] = *reinterpret_cast<const u32x4*>(qh + ho);
-      R.k[ps] = *reinterpret_cast<const u32x4*>(qh + (ho + LD));
-      R.v[ps] = *reinterpret_cast<const u32x4*>(qh + (ho + 2u * LD));
-      R.d[ps] = *reinterpret_cast<const u32x4*>(dh + ho);
-      R.o[ps] = *reinterpret_cast<const u32x4*>(ob + oo);
-    }
-    (void)qb; (void)dob;
-#else
 #pragma unroll
     for (int ps = 0; ps < NPS; ++ps) {
       int row = ps * (NT / 4) + r0; row = row < L ? row : L - 1;
@@ -1103,7 +1065,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
       R.d[ps] = *reinterpret_cast<const u32x4*>(dob + oo);
       R.o[ps] = *reinterpret_cast<const u32x4*>(ob + oo);
     }
-#endif
     R.lse = p.lse[stat_at(p, b_, h_, H, L, row0_, t < L ? t : L - 1)];
     const int lane_ = t & 63, wid_ = t >> 6;
 #pragma unroll
@@ -1134,23 +1095,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
   Regs R;
   int w = blockIdx.x;
   if (w < nheads) issue(w, R);
-#ifdef CLIPK_ATTN_TRACE
-  const bool tr_on = blockIdx.x == 0 && tid == 0 && g_attn_trace != nullptr;
-  unsigned long long* tr_lds = reinterpret_cast<unsigned long long*>(smem + lds_fused(D));
-  if (tid < 16) tr_lds[tid] = 0;
-  __syncthreads();
-  if (g_attn_stagger > 0 && (__builtin_amdgcn_s_getreg((3 << 11) | 4) & 0xF) != 0)     // HW_REG_HW_ID[3:0]: wave slot in the SIMD
-    for (int i = 0; i < g_attn_stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  unsigned long long tr_t = __builtin_amdgcn_s_memtime();
-  const unsigned long long tr_r0 = __builtin_amdgcn_s_memrealtime(), tr_c0 = tr_t;
-#endif
 
   for (; w < nheads; w += gridDim.x) {
     int blk, h, b;
     work_item_at(w, 1, H, p.B, blk, h, b);
     int L = p.L;
     const long row0 = seq_rows(p, b, L);
-    ATTN_STAMP(7);                                         // (loop bookkeeping)
     if (L <= 0) {                                          // (workgroup-uniform) empty sequence of a packed batch
       issue(w + (int)gridDim.x < nheads ? w + (int)gridDim.x : w, R);
       continue;
@@ -1186,7 +1136,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
     if (tid < LQ)
       for (int i = 0; i < ILD; i += 4) *reinterpret_cast<f32x4*>(img + tid * ILD + i) = f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();
-    ATTN_STAMP(0);                                         // wait for the prefetched rows + K / V staging + delta + image zero
 
     bf16x8 kf[KTW], vf[KTW], ktf[DT][NCK];
     float kbias[KTW];
@@ -1210,7 +1159,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
     // under the sweep.  (Unconditional, see below; the last head of a workgroup re-requests its own rows.)
     if constexpr (NW == 8) issue(w + (int)gridDim.x < nheads ? w + (int)gridDim.x : w, R);
     __syncthreads();
-    ATTN_STAMP(1);                                         // fragments + Q / dO staging
 
     f32x4 dk[DT][KTW], dv[DT][KTW];
 #pragma unroll
@@ -1309,12 +1257,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
     // nobody consumes - because a branch here makes the compiler wait for vmcnt(0) at the first use of the tables
     // (on the not-taken path they are the youngest loads), which waits for the whole prefetch as well.
     // (Eight waves: the rows were requested before the sweep and have landed; the tables simply come now.)
-    ATTN_STAMP(2);                                         // the sweep
     RopeRow<D> T;
     if (ROPE) load_rope_row<D>(T, p.cosT, p.sinT, tq < L ? tq : L - 1);
     // (asking for the head in two instalments around the LDS work of the write-out changed nothing: 850 vs 853 us)
     if constexpr (NW == 4) issue(w + (int)gridDim.x < nheads ? w + (int)gridDim.x : w, R);
-    ATTN_STAMP(3);                                         // issuing the next head's loads
 
     // ---- dQ rows from the image; dK~ (f32, RoPE^T wants f32 pairs) and dV (bf16) through images over the now dead
     // Q / dO / dS^T region
@@ -1333,7 +1279,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
           *reinterpret_cast<u32x2*>(dvimg + key * 64 + d * 2) = wv;
         }
     __syncthreads();
-    ATTN_STAMP(4);                                         // dK / dV images + barrier
     // RoPE^T, scale and rounding by the row's owner, IN PLACE (the bf16 row over the start of its own f32 row; the
     // row is read whole before it is written) ...
     if (tq < L) {
@@ -1360,31 +1305,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
         }
       }
     }
-    ATTN_STAMP(5);                                         // gradient rows: RoPE^T in place, barrier, row stores issued
     __syncthreads();                                       // the images are read; the next head may stage over them
-    ATTN_STAMP(6);                                         // the closing barrier
-#ifdef CLIPK_ATTN_TRACE
-    if (tr_on) atomicAdd(&tr_lds[8], 1ull);
-#endif
   }
-#ifdef CLIPK_ATTN_TRACE
-  if (tr_on) {
-    for (int i = 0; i < 9; ++i) g_attn_trace[i] = tr_lds[i];
-    g_attn_trace[9] = __builtin_amdgcn_s_memtime() - tr_c0;
-    g_attn_trace[10] = __builtin_amdgcn_s_memrealtime() - tr_r0;
-  }
-#endif
 }
-#ifdef CLIPK_ATTN_TRACE
-}  // namespace
-extern "C" int clipk_attn_set_trace(void* buf) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_attn_trace), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
-}
-extern "C" int clipk_attn_set_stagger(int n) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_attn_stagger), &n, sizeof(n)) == hipSuccess ? 0 : -1;
-}
-namespace {
-#endif
 
 // =================================================================================================
 // backward, whole head in one workgroup, head dim 96 (the 6 x 768 RNA encoder: 8 heads of 96), 128 < L <= 256, rows
@@ -1833,19 +1756,10 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused96w8_kernel(const AP p) 
 
   int w = blockIdx.x;
   if (w < nheads) issue_head(w);
-#ifdef CLIPK_ATTN_TRACE
-  const bool tr_on = blockIdx.x == 0 && tid == 0 && g_attn_trace != nullptr;
-  unsigned long long* tr_lds = reinterpret_cast<unsigned long long*>(smem + lds_fused96());
-  if (tid < 16) tr_lds[tid] = 0;
-  __syncthreads();
-  unsigned long long tr_t = __builtin_amdgcn_s_memtime();
-  const unsigned long long tr_r0 = __builtin_amdgcn_s_memrealtime(), tr_c0 = tr_t;
-#endif
   for (; w < nheads; w += gridDim.x) {
     int L, b, h;
     long row0;
     point_at(w, L, row0, b, h);
-    ATTN_STAMP(7);                                         // (loop bookkeeping)
     const int wnext = w + (int)gridDim.x < nheads ? w + (int)gridDim.x : w;   // last head: re-request its own rows
     if (L <= 0) {                                          // (workgroup-uniform) empty sequence of a packed batch
       issue_head(wnext);
@@ -1878,7 +1792,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused96w8_kernel(const AP p) 
     __syncthreads();
     finish_delta(0);
     __syncthreads();
-    ATTN_STAMP(0);                                         // wait for the head's rows, K rows -> LDS, block 0, delta (2 barriers)
 
     f32x4 dk[DT][KTW], dv[DT][KTW];
 #pragma unroll
@@ -1963,9 +1876,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused96w8_kernel(const AP p) 
       dvdk();
       __builtin_amdgcn_sched_barrier(0);
       store_block(j + 1);                                  // the other buffer
-      ATTN_STAMP(1);                                       // step: S / dP, softmax, dS^T, dV / dK, staging of the next block
       __syncthreads();                                     // every wave's dS^T tile is written
-      ATTN_STAMP(4);                                       // step: the barrier after it
       // dQ^T = K^T dS^T as COMPLETE (d tile, 16-query tile) outputs over all keys: waves 0-3 take d tiles 0-3 (both query
       // tiles), waves 4-7 d tiles 4 / 5 (one query tile each) - three tiles per SIMD - reading the K^T fragments of the
       // staged K rows and the dS^T tile of the wave that owns each 32-key chunk.  No shares, no sums over waves: the
@@ -2008,12 +1919,10 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused96w8_kernel(const AP p) 
       }
       if (j + 1 < nblk) finish_delta(j + 1);
       __syncthreads();
-      ATTN_STAMP(2);                                       // step: dQ tiles, barrier, dQ rows, delta, barrier
     }
 
     // ---- the next head's rows: K / V fragment registers are free now; they land under the write-out below
     issue_head(wnext);
-    ATTN_STAMP(3);                                         // issuing the next head's loads
 
     // ---- dK^T (x scale) and dV^T accumulators -> bf16 [key][d] images (one after the other, over the K rows) -> rows
 #pragma unroll 1
@@ -2042,18 +1951,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused96w8_kernel(const AP p) 
       }
       __syncthreads();
     }
-    ATTN_STAMP(5);                                         // dK / dV images, barriers, row stores
-#ifdef CLIPK_ATTN_TRACE
-    if (tr_on) atomicAdd(&tr_lds[8], 1ull);
-#endif
   }
-#ifdef CLIPK_ATTN_TRACE
-  if (tr_on) {
-    for (int i = 0; i < 9; ++i) g_attn_trace[i] = tr_lds[i];
-    g_attn_trace[9] = __builtin_amdgcn_s_memtime() - tr_c0;
-    g_attn_trace[10] = __builtin_amdgcn_s_memrealtime() - tr_r0;
-  }
-#endif
 }
 
 // =================================================================================================
@@ -2090,17 +1988,6 @@ __global__ __launch_bounds__(256, ROT ? 3 : 4) void attn_fwd_whole32_kernel(cons
     const unsigned int HD = (unsigned int)(H * D), cc = 8u * (ci < cpr ? ci : cpr - 1);
     const unsigned short* qb = p.qkv + row0 * 3 * (long)HD + (long)h * D;
     u32x4 ck[4], cv[4];
-#ifdef CLIPK_ATTN_HM_PROBE
-    const unsigned short* qhm = p.qkv + (long)(b * H + h) * 3 * p.L * D;      // timing only, see attn_bwd_fused32_kernel
-    const unsigned int LDm = (unsigned int)(p.L * D);
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      int row = ps * 64 + r0; row = row < L ? row : L - 1;
-      const unsigned int ho = (unsigned int)row * D + cc;
-      if (!ROT) ck[ps] = *reinterpret_cast<const u32x4*>(qhm + (ho + LDm));
-      cv[ps] = *reinterpret_cast<const u32x4*>(qhm + (ho + 2u * LDm));
-    }
-#else
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
       int row = ps * 64 + r0; row = row < L ? row : L - 1;
@@ -2108,7 +1995,6 @@ __global__ __launch_bounds__(256, ROT ? 3 : 4) void attn_fwd_whole32_kernel(cons
       if (!ROT) ck[ps] = *reinterpret_cast<const u32x4*>(qb + (qo + HD));
       cv[ps] = *reinterpret_cast<const u32x4*>(qb + (qo + 2u * HD));
     }
-#endif
     RowRegs<4> rk, rq;                                     // ROT: thread t owns row t of K and of Q
     const int pc = tid < L ? tid : L - 1;
     if (ROT) {
@@ -2121,10 +2007,6 @@ __global__ __launch_bounds__(256, ROT ? 3 : 4) void attn_fwd_whole32_kernel(cons
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
           int row = qh * 128 + wid * 32 + qt * 16 + li; row = row < L ? row : L - 1;
-#ifdef CLIPK_ATTN_HM_PROBE
-          if (!ROT) qfr[qh][qt] = *reinterpret_cast<const u32x4*>(qhm + ((unsigned int)row * D + 8u * (g < cpr ? g : cpr - 1)));
-          else
-#endif
           qfr[qh][qt] = *reinterpret_cast<const u32x4*>(qb + ((unsigned int)row * 3u * HD + 8u * (g < cpr ? g : cpr - 1)));
         }
     }
@@ -2353,7 +2235,7 @@ int launch_fwd(const AP& p, hipStream_t st) {
 
 template <bool ROPE, int D, int NW>
 void launch_fused_nw(const AP& p, hipStream_t st) {
-  constexpr size_t lds = lds_fused(D) + FUSED_TRACE_LDS;
+  constexpr size_t lds = lds_fused(D);
   static std::atomic<uint64_t> attr_set{0};
   clipk_once_per_device(attr_set, [&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused32_kernel<ROPE, D, NW>),
@@ -2380,8 +2262,8 @@ inline void launch_fused96(const AP& p, hipStream_t st) {
   const int nheads = p.B * p.H, cus = attn_cu_count();
   if (clipk_opt_get(OPT_ATTN_FUSED_WAVES) != 4) {             // default: eight waves of 32 keys (948 vs 1132 us per layer at B = 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused96w8_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + FUSED_TRACE_LDS));
-    hipLaunchKernelGGL(attn_bwd_fused96w8_kernel, dim3(nheads < cus ? nheads : cus), dim3(512), lds + FUSED_TRACE_LDS, st, p);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(attn_bwd_fused96w8_kernel, dim3(nheads < cus ? nheads : cus), dim3(512), lds, st, p);
     return;
   }
   hipLaunchKernelGGL(attn_bwd_fused96_kernel, dim3(nheads < cus ? nheads : cus), dim3(256), lds, st, p);

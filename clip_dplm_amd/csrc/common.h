@@ -10,7 +10,7 @@
 
 // Kernel-selection options (core.hip): set explicitly through clipk_set_option(), never read from the environment.
 // Every value of every option computes the same results; they choose between kernels / schedules that tests and
-// tools/ want to compare.  Result-changing ablation switches exist only in builds with -DCLIPK_EXPERIMENTS.
+// tools/ want to compare.
 enum clipk_opt {
   OPT_GEMM_KERNEL = 0,     // -1 auto, 1 generic kernel (gemm_nt.hip), 2 128x128 (v2), 3 persistent 256x256 (v3)
   OPT_GEMM_EPI_GENERIC,    // 1: run-time epilogue instead of the specialised modes
@@ -25,7 +25,6 @@ enum clipk_opt {
   OPT_ATTN_FUSED_WAVES,    // waves per workgroup in the whole-head backward: 0 auto (hd <= 32: 4, hd 96: 8), 4, 8
   OPT_WGRAD_SPLITS,        // v3 weight-gradient kernel: M splits (0 = about one workgroup per CU)
   OPT_SIMCE_KERNEL,        // -1 auto (tiled LSE pass for >= 64 queries), 1 first-generation kernel, 2 tiled
-  OPT_GEMM_ABL,            // CLIPK_EXPERIMENTS builds only: timing ablations that change results
   OPT_ATTN_ROW_STORES,     // whole-head forward: 2 = rotated q / k rows written back four lanes to a row from LDS (measured slower; default off)
   OPT_GEMM_F32_SPLITS,     // skinny exact-f32 Linear: cross-workgroup splits of the contraction (0 = auto, 1 .. 8)
   OPT_RETRIEVAL_SPLITS,    // clipk_sim_topk / clipk_sim_rank: key-range splits (0 = auto, n > 0: n, capped by the tile count)

@@ -22,7 +22,7 @@ struct OptDef { const char* name; int dflt; };
 const OptDef kOpts[OPT_COUNT] = {
     {"gemm_kernel", -1}, {"gemm_epi_generic", 0}, {"gemm_bm", 0}, {"gemm_stages", 1}, {"gemm_nwg", 0},
     {"gemm_stagger", 0}, {"epi_nt", 0}, {"wgrad_kernel", -1}, {"attn_whole_fwd", -1}, {"attn_fused_bwd", -1},
-    {"attn_fused_waves", 0}, {"wgrad_splits", 0}, {"simce_kernel", -1}, {"gemm_abl", 0},
+    {"attn_fused_waves", 0}, {"wgrad_splits", 0}, {"simce_kernel", -1},
     {"attn_row_stores", 0}, {"gemm_f32_splits", 0}, {"retrieval_splits", 0},
 };
 std::atomic<int> g_opts[OPT_COUNT];
@@ -56,9 +56,6 @@ extern "C" int clipk_set_option(const char* name, int value) {
   opts_init();
   const int i = opt_index(name);
   if (i < 0) return CLIPK_ERR_BAD_ARG;
-#ifndef CLIPK_EXPERIMENTS
-  if (i == OPT_GEMM_ABL && value != 0) return CLIPK_ERR_UNSUPPORTED;   // result-changing: not in product builds
-#endif
   g_opts[i].store(value, std::memory_order_relaxed);
   return CLIPK_OK;
 }

@@ -1,4 +1,4 @@
-// gemm_epilogue.h — epilogue shared by the clipk_gemm_nt kernels (gemm_nt_v2.hip, gemm_nt_v3.hip).
+// gemm_epilogue.h — epilogue shared by the clipk_gemm_nt kernels (gemm_nt_v2.hip, gemm_nt_v3.hip, gemm_nt_v4.hip).
 //
 // Each wave owns a [16*NJ m][64 n] block of the output as accumulators acc[n-tile i][m-tile j] (swapped operand
 // roles: lane holds rows n = 16i + 4g + r of column m = 16j + (lane & 15)).  One 16-row m-tile at a time goes through a
@@ -14,6 +14,7 @@
 #pragma once
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 struct EpiArgs {
   void* C; long ldc; int c_f32;
@@ -105,6 +106,31 @@ static inline int epi_mode_for(const clipk_gemm_args* a) {
   if (a->act == CLIPK_ACT_NONE && has_aux && a->dact == CLIPK_ACT_GELU && !has_res && !has_pre && !c_f32 && !has_bias)
     return aux8 ? EPI_DGELU8 : EPI_DGELU;
   return EPI_GENERIC;
+}
+
+// the mode a launch runs: epi_mode_for, or the run-time epilogue when option gemm_epi_generic = 1
+static inline int select_epi_mode(const clipk_gemm_args* a) {
+  return clipk_opt_get(OPT_GEMM_EPI_GENERIC) == 1 ? EPI_GENERIC : epi_mode_for(a);
+}
+
+// f(std::integral_constant<int, MODE>{}) for a specialised mode, EPI_GENERIC for any other value (callers refuse
+// EPI_UNSUPPORTED first): one kernel instantiation per specialised mode plus the generic one
+template <class F>
+void with_epi_mode(int mode, F&& f) {
+  switch (mode) {
+    case EPI_PLAIN: f(std::integral_constant<int, EPI_PLAIN>{}); break;
+    case EPI_RES32: f(std::integral_constant<int, EPI_RES32>{}); break;
+    case EPI_GELU_PRE: f(std::integral_constant<int, EPI_GELU_PRE>{}); break;
+    case EPI_DGELU: f(std::integral_constant<int, EPI_DGELU>{}); break;
+    case EPI_RES16: f(std::integral_constant<int, EPI_RES16>{}); break;
+    case EPI_PRES16: f(std::integral_constant<int, EPI_PRES16>{}); break;
+    case EPI_ROPE: f(std::integral_constant<int, EPI_ROPE>{}); break;
+    case EPI_GELU_D8: f(std::integral_constant<int, EPI_GELU_D8>{}); break;
+    case EPI_DGELU8: f(std::integral_constant<int, EPI_DGELU8>{}); break;
+    case EPI_PLAIN_NB: f(std::integral_constant<int, EPI_PLAIN_NB>{}); break;
+    case EPI_ROPE_IL: f(std::integral_constant<int, EPI_ROPE_IL>{}); break;
+    default: f(std::integral_constant<int, EPI_GENERIC>{}); break;
+  }
 }
 
 constexpr int EPI_LD = 68;                              // f32 per staged row (16 rows x 64 cols per wave + pad)

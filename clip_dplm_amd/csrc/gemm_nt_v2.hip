@@ -173,7 +173,7 @@ extern "C" int clipk_gemm_nt_v2_launch(const clipk_gemm_args* a, void* stream) {
   p.stagger = clipk_opt_get(OPT_GEMM_STAGGER);
   const bool big = clipk_opt_get(OPT_GEMM_BM) == 256;      // A/B switches for tools/bench_kernels.py
   const int stages = clipk_opt_get(OPT_GEMM_STAGES);
-  const int mode = clipk_opt_get(OPT_GEMM_EPI_GENERIC) == 1 ? EPI_GENERIC : epi_mode_for(a);
+  const int mode = select_epi_mode(a);
   if (mode == EPI_UNSUPPORTED) return CLIPK_ERR_UNSUPPORTED;
   if (a->rope_cos && ((mode != EPI_ROPE && mode != EPI_ROPE_IL) || big || stages == 2)) return CLIPK_ERR_UNSUPPORTED;   // never unrotated
   static std::atomic<uint64_t> attr_set{0};
@@ -192,18 +192,9 @@ extern "C" int clipk_gemm_nt_v2_launch(const clipk_gemm_args* a, void* stream) {
     const int lds = 128 * BK * 2 + B_TILE_BYTES;
     const dim3 grid(ntm * ntn), blk(256);
     if (stages == 2) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 2>), grid, blk, 2 * lds, st, p);
-    else if (mode == EPI_PLAIN) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_PLAIN>), grid, blk, lds, st, p);
-    else if (mode == EPI_RES32) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_RES32>), grid, blk, lds, st, p);
-    else if (mode == EPI_GELU_PRE) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_GELU_PRE>), grid, blk, lds, st, p);
-    else if (mode == EPI_DGELU) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_DGELU>), grid, blk, lds, st, p);
-    else if (mode == EPI_RES16) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_RES16>), grid, blk, lds, st, p);
-    else if (mode == EPI_PRES16) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_PRES16>), grid, blk, lds, st, p);
-    else if (mode == EPI_ROPE) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_ROPE>), grid, blk, lds, st, p);
-    else if (mode == EPI_GELU_D8) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_GELU_D8>), grid, blk, lds, st, p);
-    else if (mode == EPI_DGELU8) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_DGELU8>), grid, blk, lds, st, p);
-    else if (mode == EPI_PLAIN_NB) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_PLAIN_NB>), grid, blk, lds, st, p);
-    else if (mode == EPI_ROPE_IL) hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, EPI_ROPE_IL>), grid, blk, lds, st, p);
-    else hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1>), grid, blk, lds, st, p);
+    else with_epi_mode(mode, [&](auto m) {
+      hipLaunchKernelGGL((gemm_nt_v2_kernel<128, 1, decltype(m)::value>), grid, blk, lds, st, p);
+    });
   }
   return clipk_check_launch();
 }

@@ -49,7 +49,6 @@ struct Params {
   int M, N, K;
   EpiArgs e;
   int ntn, ntiles;
-  int abl;          // timing-only ablation (tools/bench_kernels.py): 1 = no epilogue
   int stagger;      // workgroup b starts ((b >> 3) & 3) * stagger * ~3.4 us late, 0 = off
 };
 
@@ -58,26 +57,6 @@ struct Params {
 // half was already accumulated by the K-tile before)
 template <int NH, int MH, int KLO = 0>
 __device__ __forceinline__ void quad(f32x4 (&acc)[4][8], const bf16x8 (&wf)[2][2][2], const bf16x8 (&xf)[4][2]) {
-#ifdef CLIPK_GEMM_MFMA32
-  // TIMING-ONLY experiment (tools/exp_gemm_mfma_shape.py): the same quadrant as 8 x
-  // v_mfma_f32_32x32x16_bf16 (2 m-tiles of 32 x 1 n-tile of 32 x 4 k-steps of 16; 8 x 32 = 256 pipe cycles, as 16 x
-  // 16) on the SAME 12 fragment registers and the same 32 accumulator registers.  The fragments were fetched in the
-  // 16x16x32 lane layout, so the products are garbage (random bf16 data all the same: realistic operand toggling);
-  // instruction mix, LDS traffic, register footprint and MFMA pipe cycles are those of a real 32x32x16 loop.
-  typedef __attribute__((ext_vector_type(16))) float f32x16;
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
-    f32x16 c;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) c[e] = acc[NH * 2 + (e >> 3)][MH * 4 + mt * 2 + ((e >> 2) & 1)][e & 3];
-#pragma unroll
-    for (int ks = 2 * KLO; ks < 4; ++ks)
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[NH][ks & 1][ks >> 1], xf[mt * 2 + (ks & 1)][ks >> 1], c, 0, 0, 0);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[NH * 2 + (e >> 3)][MH * 4 + mt * 2 + ((e >> 2) & 1)][e & 3] = c[e];
-  }
-  return;
-#endif
 #pragma unroll
   for (int kk = KLO; kk < 2; ++kk)
 #pragma unroll
@@ -90,12 +69,6 @@ __device__ __forceinline__ void quad(f32x4 (&acc)[4][8], const bf16x8 (&wf)[2][2
 
 #define CLIPK_BAR() __builtin_amdgcn_s_barrier()
 #define CLIPK_SB() __builtin_amdgcn_sched_barrier(0)
-#ifdef CLIPK_GEMM_TRACE
-// experiment builds (tools/exp_gemm_mfma_shape.py): shader cycles (s_memtime) and 100 MHz ticks (s_memrealtime) summed
-// over the main loops of workgroup 0, and its K-tile count -> cycles per K-tile and the in-kernel clock
-// (MI355X_MICROARCH.md, DVFS item 6).  The stamps go to a buffer of their own; no output depends on them.
-__device__ unsigned long long* g_gemm_trace = nullptr;
-#endif
 #define CLIPK_STR2(x) #x
 #define CLIPK_STR(x) CLIPK_STR2(x)
 // counted wait that tolerates NS younger-than-the-loads store instructions (NS is a template constant 0..32)
@@ -267,11 +240,6 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_v3_kernel(const Params p) {
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef CLIPK_GEMM_TRACE
-    const bool tr_on = blockIdx.x == 0 && tid == 0 && g_gemm_trace != nullptr;
-    unsigned long long tc0 = 0, tr0 = 0;
-    if (tr_on) { tc0 = __builtin_amdgcn_s_memtime(); tr0 = __builtin_amdgcn_s_memrealtime(); }
-#endif
     tile_body(std::integral_constant<int, 3>{}, 0);
     for (int T = 1; T < nk - 2; ++T) tile_body(std::integral_constant<int, 0>{}, T);
     tile_body(std::integral_constant<int, 1>{}, nk - 2);
@@ -280,13 +248,6 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_v3_kernel(const Params p) {
     const int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const int gn_e = cn0 + wn * 64 + (lane_e & 7) * 8;
     tile_body(std::integral_constant<int, 2>{}, nk - 1);
-#ifdef CLIPK_GEMM_TRACE
-    if (tr_on) {
-      g_gemm_trace[0] += __builtin_amdgcn_s_memtime() - tc0;
-      g_gemm_trace[1] += __builtin_amdgcn_s_memrealtime() - tr0;
-      g_gemm_trace[2] += (unsigned long long)nk;
-    }
-#endif
     if (wm == 0) CLIPK_BAR();                                   // re-align: every fragment read of this tile retired
     CLIPK_SB();
     // bias before the prefetch: vmcnt is in-order, a load issued after the prefetch could not be waited for
@@ -302,23 +263,9 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_v3_kernel(const Params p) {
     }
     // ---- epilogue (gemm_epilogue.h): issues its stores and moves on; they drain under the next main loop
     float* eb = reinterpret_cast<float*>(smem + 2 * BUF_BYTES) + wid * (SLAB_BYTES / 4);
-#ifdef CLIPK_EXPERIMENTS
-    if (p.abl & 1) {
-      float sacc = bv[0];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sacc += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-      if (sacc == 1.2345e-30f) reinterpret_cast<float*>(p.e.C)[0] = sacc;
-    } else
-#endif
     gemm_epilogue<MODE, 8, true>(p.e, acc, eb, lane_e, cm0 + wm * 128, gn_e, bv);
     if (!more) break;
-#ifdef CLIPK_EXPERIMENTS
-    const bool drain = MODE == EPI_GENERIC || (p.abl & 1);
-#else
     constexpr bool drain = MODE == EPI_GENERIC;
-#endif
     if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // store count unknown: drain
     first = drain;
   }
@@ -347,12 +294,6 @@ int cu_count() {
 
 }  // namespace
 
-#ifdef CLIPK_GEMM_TRACE
-extern "C" int clipk_gemm_v3_set_trace(void* buf) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_trace), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 // called by clipk_gemm_nt (gemm_nt.hip) after it validated the arguments (K % 32 == 0, K >= 192)
 extern "C" int clipk_gemm_nt_v3_launch(const clipk_gemm_args* a, void* stream) {
   Params p;
@@ -369,27 +310,11 @@ extern "C" int clipk_gemm_nt_v3_launch(const clipk_gemm_args* a, void* stream) {
   { const int e = clipk_opt_get(OPT_GEMM_NWG); if (e >= 8) nwg = e & ~7; }                   // experiments only
   if (nwg > p.ntiles) nwg = p.ntiles;
   const dim3 grid(nwg);
-#ifdef CLIPK_EXPERIMENTS
-  p.abl = clipk_opt_get(OPT_GEMM_ABL);                      // timing-only ablations: experiment builds only
-  if (p.abl & 4) p.e.N = 0;                                 // every store out of range: same instructions, no traffic
-#else
-  p.abl = 0;
-#endif
   p.stagger = clipk_opt_get(OPT_GEMM_STAGGER);
   hipStream_t st = (hipStream_t)stream;
-  const int mode = clipk_opt_get(OPT_GEMM_EPI_GENERIC) == 1 ? EPI_GENERIC : epi_mode_for(a);
-  if (mode == EPI_PLAIN) launch_v3<EPI_PLAIN>(p, grid, st);
-  else if (mode == EPI_RES32) launch_v3<EPI_RES32>(p, grid, st);
-  else if (mode == EPI_GELU_PRE) launch_v3<EPI_GELU_PRE>(p, grid, st);
-  else if (mode == EPI_DGELU) launch_v3<EPI_DGELU>(p, grid, st);
-  else if (mode == EPI_RES16) launch_v3<EPI_RES16>(p, grid, st);
-  else if (mode == EPI_PRES16) launch_v3<EPI_PRES16>(p, grid, st);
-  else if (mode == EPI_ROPE) launch_v3<EPI_ROPE>(p, grid, st);
-  else if (mode == EPI_GELU_D8) launch_v3<EPI_GELU_D8>(p, grid, st);
-  else if (mode == EPI_DGELU8) launch_v3<EPI_DGELU8>(p, grid, st);
-  else if (mode == EPI_PLAIN_NB) launch_v3<EPI_PLAIN_NB>(p, grid, st);
-  else if (mode == EPI_ROPE_IL) launch_v3<EPI_ROPE_IL>(p, grid, st);
-  else if (mode == EPI_UNSUPPORTED || a->rope_cos) return CLIPK_ERR_UNSUPPORTED;   // rotation: its own mode only
-  else launch_v3<EPI_GENERIC>(p, grid, st);
+  const int mode = select_epi_mode(a);
+  if (mode == EPI_UNSUPPORTED || (a->rope_cos && mode != EPI_ROPE && mode != EPI_ROPE_IL))
+    return CLIPK_ERR_UNSUPPORTED;                            // rotation: its own mode only
+  with_epi_mode(mode, [&](auto m) { launch_v3<decltype(m)::value>(p, grid, st); });
   return clipk_check_launch();
 }

@@ -48,7 +48,6 @@ struct Params {
   int M, N, K;
   EpiArgs e;
   int ntn, ntiles;
-  int abl;          // timing-only ablation (CLIPK_EXPERIMENTS builds): 1 = no epilogue
   int stagger;      // the second workgroup of every CU (blockIdx >= gridDim / 2) starts stagger x ~3.9 us late
 };
 
@@ -151,11 +150,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v4_kernel(const Params p) {
 
   f32x4 acc[4][8];          // [n-tile i][m-tile j]: rows n = 4g+r, col m = lane&15
   bf16x8 xf[4][2], wf[2][2][2];
-#ifdef CLIPK_EXPERIMENTS
-  const bool prio = !(p.abl & 8);                               // ablation 8: MFMA blocks without s_setprio 1
-#else
-  constexpr bool prio = true;
-#endif
   bool first = true;                                            // no epilogue stores of a previous tile in flight
   bool more = true;                                             // set per tile before its last K-tile
 
@@ -181,10 +175,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v4_kernel(const Params p) {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) xf[j][kk] = *reinterpret_cast<const bf16x8*>(smem + xo[kk] + XH0 + j * 2048);
     CLIPK_SB();
-    if (prio) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
     if (KT == 2 && tail) quad<0, 0, 1>(acc, wf, xf);
     else quad<0, 0>(acc, wf, xf);
-    if (prio) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     CLIPK_SB();
     // ---- phase 1: W nh1 landed (younger: X mh1 2 [, stores]); W nh0 / X mh0 are dead -> refill
     if (KT == 0 && !first) CLIPK_VMCNT_PLUS(2, NS);
@@ -196,10 +190,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v4_kernel(const Params p) {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) wf[1][t][kk] = *reinterpret_cast<const bf16x8*>(smem + wo[kk] + WH_BYTES + t * 2048);
     CLIPK_SB();
-    if (prio) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
     if (KT == 2 && tail) quad<1, 0, 1>(acc, wf, xf);
     else quad<1, 0>(acc, wf, xf);
-    if (prio) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     CLIPK_SB();
     // ---- phase 2: X mh1 landed (younger: [stores,] the 6 pieces just requested - or nothing); W nh1 is dead -> refill
     if (!refill) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -212,18 +206,18 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v4_kernel(const Params p) {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) xf[j][kk] = *reinterpret_cast<const bf16x8*>(smem + xo[kk] + XH1 + j * 2048);
     CLIPK_SB();
-    if (prio) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
     if (KT == 2 && tail) quad<1, 1, 1>(acc, wf, xf);
     else quad<1, 1>(acc, wf, xf);
-    if (prio) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     CLIPK_SB();
     // ---- phase 3: nothing to fetch; X mh1 is dead -> refill
     CLIPK_BAR(); CLIPK_SB();
     if (refill) stage_x(dx1, Tn, XH1);
-    if (prio) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
     if (KT == 2 && tail) quad<0, 1, 1>(acc, wf, xf);
     else quad<0, 1>(acc, wf, xf);
-    if (prio) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     CLIPK_SB();
   };
 
@@ -255,23 +249,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v4_kernel(const Params p) {
     float bv[8];
     epi_load_bias(p.e, gn_e, bv);
     float* eb = reinterpret_cast<float*>(smem + BUF_BYTES) + wn * (SLAB_BYTES / 4);
-#ifdef CLIPK_EXPERIMENTS
-    if (p.abl & 1) {
-      float sacc = bv[0];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sacc += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-      if (sacc == 1.2345e-30f) reinterpret_cast<float*>(p.e.C)[0] = sacc;
-    } else
-#endif
     gemm_epilogue<MODE, 8, true>(p.e, acc, eb, lane_e, cm0, gn_e, bv);
     if (!more) break;
-#ifdef CLIPK_EXPERIMENTS
-    const bool drain = MODE == EPI_GENERIC || (p.abl & 1);
-#else
     constexpr bool drain = MODE == EPI_GENERIC;
-#endif
     if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // store count unknown: drain
     first = drain;
   }
@@ -315,27 +295,11 @@ extern "C" int clipk_gemm_nt_v4_launch(const clipk_gemm_args* a, void* stream) {
   { const int e = clipk_opt_get(OPT_GEMM_NWG); if (e >= 8) nwg = e & ~7; }                   // experiments only
   if (nwg > p.ntiles) nwg = p.ntiles;
   const dim3 grid(nwg);
-#ifdef CLIPK_EXPERIMENTS
-  p.abl = clipk_opt_get(OPT_GEMM_ABL);                      // timing-only ablations: experiment builds only
-  if (p.abl & 4) p.e.N = 0;                                 // every store out of range: same instructions, no traffic
-#else
-  p.abl = 0;
-#endif
   p.stagger = clipk_opt_get(OPT_GEMM_STAGGER);
   hipStream_t st = (hipStream_t)stream;
-  const int mode = clipk_opt_get(OPT_GEMM_EPI_GENERIC) == 1 ? EPI_GENERIC : epi_mode_for(a);
-  if (mode == EPI_PLAIN) launch_v4<EPI_PLAIN>(p, grid, st);
-  else if (mode == EPI_RES32) launch_v4<EPI_RES32>(p, grid, st);
-  else if (mode == EPI_GELU_PRE) launch_v4<EPI_GELU_PRE>(p, grid, st);
-  else if (mode == EPI_DGELU) launch_v4<EPI_DGELU>(p, grid, st);
-  else if (mode == EPI_RES16) launch_v4<EPI_RES16>(p, grid, st);
-  else if (mode == EPI_PRES16) launch_v4<EPI_PRES16>(p, grid, st);
-  else if (mode == EPI_ROPE) launch_v4<EPI_ROPE>(p, grid, st);
-  else if (mode == EPI_GELU_D8) launch_v4<EPI_GELU_D8>(p, grid, st);
-  else if (mode == EPI_DGELU8) launch_v4<EPI_DGELU8>(p, grid, st);
-  else if (mode == EPI_PLAIN_NB) launch_v4<EPI_PLAIN_NB>(p, grid, st);
-  else if (mode == EPI_ROPE_IL) launch_v4<EPI_ROPE_IL>(p, grid, st);
-  else if (mode == EPI_UNSUPPORTED || a->rope_cos) return CLIPK_ERR_UNSUPPORTED;   // rotation: its own mode only
-  else launch_v4<EPI_GENERIC>(p, grid, st);
+  const int mode = select_epi_mode(a);
+  if (mode == EPI_UNSUPPORTED || (a->rope_cos && mode != EPI_ROPE && mode != EPI_ROPE_IL))
+    return CLIPK_ERR_UNSUPPORTED;                            // rotation: its own mode only
+  with_epi_mode(mode, [&](auto m) { launch_v4<decltype(m)::value>(p, grid, st); });
   return clipk_check_launch();
 }

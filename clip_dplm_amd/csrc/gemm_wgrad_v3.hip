@@ -77,27 +77,7 @@ __device__ __forceinline__ void quad(f32x4 (&acc)[8][4], const bf16x8 (&yf)[4][2
 }
 
 #define CLIPK_SB() __builtin_amdgcn_sched_barrier(0)
-#ifdef CLIPK_WGRAD_TRACE
-// experiment builds (tools/exp_wgrad_trace.py): cycle stamps after every barrier of steps 8..11, workgroup 0,
-// waves 0 (n-wave group 0) and 4 (group 1) -> where a K-step's time goes
-__device__ unsigned long long* g_wgrad_trace = nullptr;
-#define CLIPK_BAR()                                                                                       \
-  do {                                                                                                    \
-    __builtin_amdgcn_s_barrier();                                                                         \
-    if (tr_on && tr_T >= 8 && tr_T < 12 && tr_i < 16) tr[(tr_T - 8) * 16 + tr_i] = __builtin_readcyclecounter(); \
-    ++tr_i;                                                                                               \
-  } while (0)
-#define CLIPK_BAR2() __builtin_amdgcn_s_barrier()
-#define CLIPK_STAMP()                                                                                     \
-  do {                                                                                                    \
-    if (tr_on && tr_T >= 8 && tr_T < 12 && tr_i < 16) tr[(tr_T - 8) * 16 + tr_i] = __builtin_readcyclecounter(); \
-    ++tr_i;                                                                                               \
-  } while (0)
-#else
 #define CLIPK_BAR() __builtin_amdgcn_s_barrier()
-#define CLIPK_BAR2() __builtin_amdgcn_s_barrier()
-#define CLIPK_STAMP() do { } while (0)
-#endif
 
 // SCHED 1: the 8-phase schedule (two wave groups one barrier apart, reads issued right before the barrier of the
 // phase that consumes them).  SCHED 2: software-pipelined schedule, see the main loop below.
@@ -117,11 +97,6 @@ __global__ __launch_bounds__(512, 1) void wgrad_v3_kernel(const clipk_wgrad_v3_a
   const int m_beg = split * p.m_per_split;
   int m_end = m_beg + p.m_per_split; m_end = m_end < M ? m_end : M;
   const int nkt = (m_end - m_beg + BMS - 1) / BMS;             // >= 1
-#ifdef CLIPK_WGRAD_TRACE
-  const bool tr_on = bid == 0 && (wid == 0 || wid == 4) && lane == 0 && g_wgrad_trace != nullptr;
-  unsigned long long* tr = g_wgrad_trace + (wid == 4 ? 64 : 0);
-  int tr_T = -1, tr_i = 0;
-#endif
   const bool has_bias = p.bslab != nullptr;
   int bias_T = tk;                                             // next step whose dY rows this workgroup sums
 
@@ -233,9 +208,6 @@ __global__ __launch_bounds__(512, 1) void wgrad_v3_kernel(const clipk_wgrad_v3_a
     auto step_body = [&](auto mode_c, int T) {
       constexpr int TM = decltype(mode_c)::value;
       const unsigned bo = (T & 1) * BUF_BYTES;
-  #ifdef CLIPK_WGRAD_TRACE
-      tr_T = T; tr_i = 0;
-  #endif
       // ---- phase 0: quadrant (k0, n0); fetch X kh0 (8 reads, first) + dY nh0 (16 reads); refill dY nh1 of step T+1
   #pragma unroll
       for (int u = 0; u < 2; ++u)
@@ -312,26 +284,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_v3_kernel(const clipk_wgrad_v3_a
     }
     CLIPK_SB(); CLIPK_BAR(); CLIPK_SB();
     if (wn == 1) CLIPK_BAR();                                     // n = 1 waves run one barrier behind
-  #ifdef CLIPK_WGRAD_TRACE
-    // in-kernel clock (MI355X_MICROARCH.md, DVFS item 6): shader cycles and 100 MHz ticks around the main loop
-    unsigned long long tc0 = 0, tr0 = 0;
-    if (tr_on && wid == 0) { tc0 = __builtin_amdgcn_s_memtime(); tr0 = __builtin_amdgcn_s_memrealtime(); }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-  #endif
     for (int T = 0; T < nkt - 2; ++T) step_body(std::integral_constant<int, 0>{}, T);
     if (nkt > 1) step_body(std::integral_constant<int, 1>{}, nkt - 2);
     step_body(std::integral_constant<int, 2>{}, nkt - 1);
     if (wn == 0) CLIPK_BAR();                                     // re-align
-  #ifdef CLIPK_WGRAD_TRACE
-    if (tr_on && wid == 0) {
-      g_wgrad_trace[128] = __builtin_amdgcn_s_memtime() - tc0;
-      g_wgrad_trace[129] = __builtin_amdgcn_s_memrealtime() - tr0;
-      g_wgrad_trace[130] = (unsigned long long)nkt;
-    }
-  #endif
   } else {
     // ================================================================================================
-    // SCHED 2.  Stamps of the 8-phase loop (tools/exp_wgrad_trace.py) show every MFMA block preceded by the full
+    // SCHED 2.  Stamps of the 8-phase loop show every MFMA block preceded by the full
     // latency of the LDS reads issued just before its barrier: 256 cycles of MFMAs per ~450-cycle window, the matrix
     // pipe 57 % busy - the second wave group only issues DMA in that window, it does not compute.  Here every wave
     // issues the reads of a LATER block before the MFMAs of the current one, without more registers: a K-step is 8
@@ -404,17 +363,6 @@ __global__ __launch_bounds__(512, 1) void wgrad_v3_kernel(const clipk_wgrad_v3_a
     };
 #define CLIPK_BIAS_Q(q, a0, a1) \
   bias_mfma(b_odd, b_sel, (q) & 1, a0, a1, ones, yq[(q) & 1][0][0], yq[(q) & 1][0][1], yq[(q) & 1][1][0], yq[(q) & 1][1][1])
-#if defined(CLIPK_WGRAD_TRACE) && defined(CLIPK_WGRAD_ABL)
-    // timing ablations of the experiment build (results are garbage): 1 no LDS-DMA in the loop, 2 no LDS reads in the
-    // loop, 4 no barriers in the loop
-#define CLIPK_ABL_DMA(x) do { if (!(CLIPK_WGRAD_ABL & 1)) { x; } } while (0)
-#define CLIPK_ABL_RD(x) do { if (!(CLIPK_WGRAD_ABL & 2)) { x; } } while (0)
-#define CLIPK_ABL_BAR(x) do { if (!(CLIPK_WGRAD_ABL & 4)) { x; } } while (0)
-#else
-#define CLIPK_ABL_DMA(x) do { x; } while (0)
-#define CLIPK_ABL_RD(x) do { x; } while (0)
-#define CLIPK_ABL_BAR(x) do { x; } while (0)
-#endif
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
 #define CLIPK_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
@@ -431,59 +379,53 @@ __global__ __launch_bounds__(512, 1) void wgrad_v3_kernel(const clipk_wgrad_v3_a
       const bool bias_now = has_bias && T == bias_T;              // (workgroup-uniform)
       const bool y1_next = TM != 2 && T >= 1;                     // (step 1's dY nh1 comes with the prologue)
       auto none = [] {};
-#ifdef CLIPK_WGRAD_TRACE
-      tr_T = T; tr_i = 0;
-#endif
       // ---- block 0 (k0, q0): needs dY q0 + X k0 (read during blocks 6 / 7 of the previous step)
-      CLIPK_LGKM0(); CLIPK_SB(); CLIPK_STAMP();
-      CLIPK_ABL_RD(read_yq(I1{}, bo); read_x(I1{}, bo));
+      CLIPK_LGKM0(); CLIPK_SB();
+      read_yq(I1{}, bo); read_x(I1{}, bo);
       CLIPK_SB();
-      blk(I0{}, I0{}, [&] { if (y1_next) CLIPK_ABL_DMA(stage1(true, 1, T + 1, YH1, 0)); });
+      blk(I0{}, I0{}, [&] { if (y1_next) stage1(true, 1, T + 1, YH1, 0); });
       if (bias_now) CLIPK_BIAS_Q(0, accb[0][0], accb[0][1]);
       CLIPK_SB();
       // ---- block 1 (k1, q0)
-      CLIPK_LGKM0(); CLIPK_SB(); CLIPK_STAMP();
-      blk(I1{}, I0{}, [&] { if (y1_next) CLIPK_ABL_DMA(stage1(true, 1, T + 1, YH1, 1)); });
+      CLIPK_LGKM0(); CLIPK_SB();
+      blk(I1{}, I0{}, [&] { if (y1_next) stage1(true, 1, T + 1, YH1, 1); });
       CLIPK_SB();
       // ---- block 2 (k1, q1): barrier alpha
       if (TM == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      CLIPK_SB(); CLIPK_ABL_BAR(CLIPK_BAR2()); CLIPK_SB(); CLIPK_STAMP();
-      CLIPK_ABL_RD(read_yq(I2{}, bo));
+      CLIPK_SB(); CLIPK_BAR(); CLIPK_SB();
+      read_yq(I2{}, bo);
       CLIPK_SB();
-      blk(I1{}, I1{}, [&] { if (TM == 0) CLIPK_ABL_DMA(stage1(true, 0, T + 2, YH0, 0)); });
+      blk(I1{}, I1{}, [&] { if (TM == 0) stage1(true, 0, T + 2, YH0, 0); });
       if (bias_now) CLIPK_BIAS_Q(1, accb[0][0], accb[0][1]);
       CLIPK_SB();
       // ---- block 3 (k0, q1)
-      CLIPK_STAMP();
-      blk(I0{}, I1{}, [&] { if (TM == 0) CLIPK_ABL_DMA(stage1(true, 0, T + 2, YH0, 1)); });
+      blk(I0{}, I1{}, [&] { if (TM == 0) stage1(true, 0, T + 2, YH0, 1); });
       CLIPK_SB();
       // ---- block 4 (k0, q2)
-      CLIPK_LGKM0(); CLIPK_SB(); CLIPK_STAMP();
-      CLIPK_ABL_RD(read_yq(I3{}, bo));
+      CLIPK_LGKM0(); CLIPK_SB();
+      read_yq(I3{}, bo);
       CLIPK_SB();
-      blk(I0{}, I2{}, [&] { if (TM == 0) CLIPK_ABL_DMA(stage1(false, 0, T + 2, XH0, 0)); });
+      blk(I0{}, I2{}, [&] { if (TM == 0) stage1(false, 0, T + 2, XH0, 0); });
       if (bias_now) CLIPK_BIAS_Q(2, accb[1][0], accb[1][1]);
       CLIPK_SB();
       // ---- block 5 (k1, q2)
-      CLIPK_STAMP();
-      blk(I1{}, I2{}, [&] { if (TM == 0) CLIPK_ABL_DMA(stage1(false, 0, T + 2, XH0, 1)); });
+      blk(I1{}, I2{}, [&] { if (TM == 0) stage1(false, 0, T + 2, XH0, 1); });
       CLIPK_SB();
       // ---- block 6 (k0, q3): barrier beta
       CLIPK_LGKM0();
       if (TM == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
       else if (TM == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      CLIPK_SB(); CLIPK_ABL_BAR(CLIPK_BAR2()); CLIPK_SB(); CLIPK_STAMP();
-      if (TM != 2) CLIPK_ABL_RD(read_yq(I0{}, bn));
+      CLIPK_SB(); CLIPK_BAR(); CLIPK_SB();
+      if (TM != 2) read_yq(I0{}, bn);
       CLIPK_SB();
-      blk(I0{}, I3{}, [&] { if (TM == 0) CLIPK_ABL_DMA(stage1(false, 1, T + 2, XH1, 0)); });
+      blk(I0{}, I3{}, [&] { if (TM == 0) stage1(false, 1, T + 2, XH1, 0); });
       if (bias_now) CLIPK_BIAS_Q(3, accb[1][0], accb[1][1]);
       CLIPK_SB();
       // ---- block 7 (k1, q3)
-      CLIPK_STAMP();
-      if (TM != 2) CLIPK_ABL_RD(read_x(I0{}, bn));
+      if (TM != 2) read_x(I0{}, bn);
       CLIPK_SB();
-      blk(I1{}, I3{}, [&] { if (TM == 0) CLIPK_ABL_DMA(stage1(false, 1, T + 2, XH1, 1)); });
+      blk(I1{}, I3{}, [&] { if (TM == 0) stage1(false, 1, T + 2, XH1, 1); });
       if (bias_now) bias_T += p.ntk;
       CLIPK_SB();
       (void)none;
@@ -497,23 +439,11 @@ __global__ __launch_bounds__(512, 1) void wgrad_v3_kernel(const clipk_wgrad_v3_a
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    CLIPK_SB(); CLIPK_BAR2(); CLIPK_SB();
+    CLIPK_SB(); CLIPK_BAR(); CLIPK_SB();
     read_yq(I0{}, 0u); read_x(I0{}, 0u);
-#ifdef CLIPK_WGRAD_TRACE
-    unsigned long long tc0 = 0, tr0 = 0;
-    if (tr_on && wid == 0) { tc0 = __builtin_amdgcn_s_memtime(); tr0 = __builtin_amdgcn_s_memrealtime(); }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-#endif
     for (int T = 0; T < nkt - 2; ++T) step2(std::integral_constant<int, 0>{}, T);
     if (nkt > 1) step2(std::integral_constant<int, 1>{}, nkt - 2);
     step2(std::integral_constant<int, 2>{}, nkt - 1);
-#ifdef CLIPK_WGRAD_TRACE
-    if (tr_on && wid == 0) {
-      g_wgrad_trace[128] = __builtin_amdgcn_s_memtime() - tc0;
-      g_wgrad_trace[129] = __builtin_amdgcn_s_memrealtime() - tr0;
-      g_wgrad_trace[130] = (unsigned long long)nkt;
-    }
-#endif
   }
 
   // ---- store the f32 partial tile: rows n (4 per lane), cols k (lane&15)
@@ -558,12 +488,6 @@ extern "C" void clipk_wgrad_v3_plan(int M, int N, int K, int* ntn, int* ntk, int
   *mps = m;
   *splits = (M + m - 1) / m;
 }
-
-#ifdef CLIPK_WGRAD_TRACE
-extern "C" int clipk_wgrad_v3_set_trace(void* buf) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad_trace), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 extern "C" int clipk_wgrad_v3_launch(const clipk_wgrad_v3_args* a, void* stream) {
   static std::atomic<uint64_t> attr_set{0};

@@ -16,9 +16,6 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-if os.environ.get("BENCH_LIB"):          # an experiment build of the library (make tools/probes/libclipk_exp.so)
-    from clip_dplm_amd import _ffi  # noqa: E402
-    _ffi.LIB_PATH = os.path.join(ROOT, os.environ["BENCH_LIB"])
 from clip_dplm_amd import ops  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -58,28 +55,23 @@ GEMM_SHAPES = [  # (name, M, N, K, epilogue)
 def bench_gemm():
     """arms interleaved in one process: 128^2 kernel with the run-time epilogue (round-1 baseline), 128^2 with the
     specialised straight-line epilogue, 256^2 phase-interleaved kernel (option gemm_kernel = 3).  Arms are dicts of
-    libclipk options (ops.set_option); BENCH_NT / BENCH_NWG / BENCH_STAGGER / BENCH_ABL (the last needs a
-    -DCLIPK_EXPERIMENTS build) add arms."""
+    libclipk options (ops.set_option); BENCH_NT / BENCH_NWG / BENCH_STAGGER (and BENCH_NWG4 / BENCH_STAGGER4 for
+    gemm_kernel = 4) add arms."""
     arms = [("v2gen", {"gemm_epi_generic": 1, "gemm_kernel": 2}), ("v2", {"gemm_kernel": 2}), ("v3", {"gemm_kernel": 3}),
             ("v4", {"gemm_kernel": 4})]
     if os.environ.get("BENCH_NT"):
         arms.append(("v3nt1", {"gemm_kernel": 3, "epi_nt": 1}))
-    for ab in os.environ.get("BENCH_ABL", "").split():
-        arms.append(("v3a" + ab, {"gemm_kernel": 3, "gemm_abl": int(ab)}))
     for nw in os.environ.get("BENCH_NWG", "").split():
         arms.append(("v3w" + nw, {"gemm_kernel": 3, "gemm_nwg": int(nw)}))
     for st in os.environ.get("BENCH_STAGGER", "").split():
         arms.append(("v3s" + st, {"gemm_kernel": 3, "gemm_stagger": int(st)}))
-    for ab in os.environ.get("BENCH_ABL4", "").split():
-        arms.append(("v4a" + ab, {"gemm_kernel": 4, "gemm_abl": int(ab)}))
-    for nw in os.environ.get("BENCH_NWG4", "").split():          # "256:1" = grid 256 (one workgroup per CU), ablation 1
-        g, _, ab = nw.partition(":")
-        arms.append(("v4w" + nw, {"gemm_kernel": 4, "gemm_nwg": int(g), "gemm_abl": int(ab or 0)}))
+    for nw in os.environ.get("BENCH_NWG4", "").split():          # "256" = grid 256 (one workgroup per CU)
+        arms.append(("v4w" + nw, {"gemm_kernel": 4, "gemm_nwg": int(nw)}))
     for st in os.environ.get("BENCH_STAGGER4", "").split():
         arms.append(("v4s" + st, {"gemm_kernel": 4, "gemm_stagger": int(st)}))
     if os.environ.get("BENCH_ARMS"):
         keep = os.environ["BENCH_ARMS"].split()
-        arms = [a for a in arms if a[0] in keep or a[0].startswith(("v4s", "v4a", "v3a", "v4w"))]
+        arms = [a for a in arms if a[0] in keep or a[0].startswith(("v4s", "v4w"))]
     print(f"{'shape':12s} {'M':>7s} {'N':>5s} {'K':>5s} {'epi':9s} | " + " | ".join(f"{n:>5s} us  TF/s" for n, _ in arms)
           + " | v2/v2gen v3/v2 v3/v4")
     tot = {n: 0.0 for n, _ in arms}
