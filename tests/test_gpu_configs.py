@@ -359,3 +359,36 @@ def test_notebook_model_at_its_own_dims_vs_oracle(dev):
         e = (got[n].grad.cpu() - r).abs().max().item() / max(r.abs().max().item(), 1e-12)
         assert e < 1e-3, (n, e)
     assert abs(lb.item() - ref.item()) < 2e-2
+
+
+# ----------------------------------------------------------------------------------------------------- bench.py
+def _bench_line(args, tmp_path, tag):
+    import json
+    import subprocess
+    import sys
+    out = tmp_path / tag
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                      "bench.py"), "--batch", "32", "--seq-len", "64", "--steps", "2",
+                        "--warmup", "1", "--dump-outputs", str(out)] + args,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads(r.stdout.strip()), out
+
+
+def test_bench_plain_run_and_full_extras(tmp_path):
+    """bench.py at a small config-2 size: a plain run prints the headline fields and nothing that needs work of its own
+    (no parity, no cpu_baseline, `kernels` only from the timed region); --full adds parity (within its bar),
+    cpu_baseline and the breakdown steps, and leaves what the timed steps compute bit for bit as the plain run's."""
+    import numpy as np
+    plain, d_plain = _bench_line([], tmp_path, "plain")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in plain, k
+    assert "parity" not in plain and "cpu_baseline" not in plain
+    assert plain["kernels"]["_source"] == "timed region"
+    full, d_full = _bench_line(["--full"], tmp_path, "full")
+    assert full["parity"]["loss_abs_err"] <= full["parity"]["bar"], full["parity"]
+    assert len(full["parity"]["trajectory"]) == 4
+    assert full["cpu_baseline"]["value"] > 0
+    assert full["kernels"]["_source"] != "timed region"
+    for name in ("loss", "params_sample", "grads_sample"):
+        assert np.array_equal(np.load(d_plain / f"{name}.npy"), np.load(d_full / f"{name}.npy")), name

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $ROOT
-ARGS="--steps 6 --warmup 2 --no-cpu-baseline --no-parity"
+ARGS="--steps 6 --warmup 2 --full --no-cpu-baseline --no-parity"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o c2 -- python3 bench.py $ARGS > $OUT/bench_stats.json 2> $OUT/bench_stats.err || exit 1
 echo "stats pass done" 
 PARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-kernel-timers"
