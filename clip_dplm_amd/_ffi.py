@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libclipk.so")
 
 BF16, F32, U8 = 0, 1, 2
+SAME_CLASS = {"mask": 0, "positive": 1}       # CLIPK_SAME_CLASS_MASK / CLIPK_SAME_CLASS_POSITIVE
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_CELU, ACT_SOFTPLUS = 0, 1, 2, 3, 4
 ACT = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "gelu": ACT_GELU, "celu": ACT_CELU, "softplus": ACT_SOFTPLUS}
 
@@ -60,6 +61,10 @@ SIGNATURES = {
     "clipk_simce_grad": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "clipk_simce_grad_scaled": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_ce_combine": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
+    "clipk_simce_cls_workspace": (_sz, [_i, _i, _i]),
+    "clipk_simce_lse_cls": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_simce_grad_cls": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _f, _f,
+                                  _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_simce_pairs_workspace": (_sz, [_i, _i, _i]),
     "clipk_simce_lse_pairs": (_i, [_vp, _i, _i, _i, C.POINTER(_i), _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_simce_grad_pairs": (_i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _vp, _f, _f, _f, _vp, _vp,
@@ -69,6 +74,7 @@ SIGNATURES = {
     "clipk_sim_topk": (_i, [_vp, _i, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipk_sim_rank_workspace": (_sz, [_i, _i, _i]),
     "clipk_sim_rank": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_sim_rank_cls": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_ce_logits_lse": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "clipk_ce_logits_bwd": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp]),
     "clipk_transpose_scale_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp]),

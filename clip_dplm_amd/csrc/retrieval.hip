@@ -16,7 +16,9 @@
 //
 // Rank: one extra tile per workgroup computes S[i, l_i] from a gathered tile whose key rows are the labels' rows, with
 // the same K-loop and the same query rows, so it has the bits the counting loop sees at that key; every score then costs
-// one compare pair against it.  Per-split counts are summed by sim_rank_finalize.
+// one compare pair against it.  Per-split counts are summed by sim_rank_finalize.  The class-filtered rank (CLS = true)
+// loads the gallery ids of a lane's 16 key rows once per tile, before its K-loop, and counts only keys of other classes;
+// CLS = false is the plain kernel (the filter sits under `if constexpr`).
 #include "common.h"
 #include "sim_tile.h"
 #include <limits.h>
@@ -183,6 +185,7 @@ struct RKP {
   int* part_cnt;                         // [ksplit][Mx]
   float* pos;                            // [Mx]
   int tiles_per_split, ntiles;
+  const int64_t* cls;                    // [Ny] gallery class ids (CLS instantiation only)
 };
 
 __device__ __forceinline__ int label_of(const int64_t* labels, int64_t label_offset, int q, int Ny) {
@@ -190,6 +193,7 @@ __device__ __forceinline__ int label_of(const int64_t* labels, int64_t label_off
   return (l >= 0 && l < Ny) ? (int)l : -1;                                // -1: out of range, reported as rank -1
 }
 
+template <bool CLS>
 __global__ __launch_bounds__(256, 2) void sim_rank_kernel(const RKP p) {
   __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (RBK + 4)];
   __shared__ int labl[RQ];
@@ -231,6 +235,8 @@ __global__ __launch_bounds__(256, 2) void sim_rank_kernel(const RKP p) {
   }
   const float pv = posl[wn * 32 + li];
   const int lab = labl[wn * 32 + li];
+  int64_t lcl = 0;                                                        // CLS: the positive's class
+  if constexpr (CLS) lcl = p.cls[lab < 0 ? 0 : lab];
   int cnt = 0;
   const int t_beg = ks * p.tiles_per_split;
   int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
@@ -239,12 +245,26 @@ __global__ __launch_bounds__(256, 2) void sim_rank_kernel(const RKP p) {
     const int j0 = kt * RK;
     const float* yrows[RBK / 16];
     key_rows(yrows, p.Y, Ny, P, j0, tid);
+    const int kb = j0 + wm * 32 + 4 * h;
+    bool other[16];                                                       // CLS: key of another class than the positive
+    if constexpr (CLS) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = kb + key_off(r);
+        other[r] = key < Ny && p.cls[key] != lcl;
+      }
+    }
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     s_tile<RBK>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
-    const int kb = j0 + wm * 32 + 4 * h;
-    if (j0 + RK <= Ny) {
+    if constexpr (CLS) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float sv = scale * acc[r];
+        cnt += other[r] & ((sv > pv) | ((sv == pv) & (kb + key_off(r) < lab)));
+      }
+    } else if (j0 + RK <= Ny) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float sv = scale * acc[r];
@@ -377,13 +397,36 @@ extern "C" int clipk_sim_rank(const float* X, int Mx, const float* Y, int Ny, in
   if (!labels && (label_offset < 0 || label_offset + Mx > Ny)) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y)) return CLIPK_ERR_BAD_ARG;
   if (workspace_bytes < clipk_sim_rank_workspace(Mx, Ny, P)) return CLIPK_ERR_BAD_ARG;
-  RKP p;
+  RKP p{};
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale; p.labels = labels; p.label_offset = label_offset;
   p.part_cnt = static_cast<int*>(workspace); p.pos = pos;
   int nqb, ksplit;
   plan(Mx, Ny, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(sim_rank_kernel, dim3(nqb, ksplit), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(sim_rank_kernel<false>, dim3(nqb, ksplit), dim3(256), 0, st, p);
+  int rc = clipk_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(sim_rank_finalize, dim3((Mx + 255) / 256), dim3(256), 0, st, (const int*)p.part_cnt, ksplit, Mx,
+                     labels, label_offset, Ny, rank);
+  return clipk_check_launch();
+}
+
+extern "C" int clipk_sim_rank_cls(const float* X, int Mx, const float* Y, int Ny, int P, float scale,
+                                  const int64_t* labels, int64_t label_offset, const int64_t* cls, int64_t* rank,
+                                  float* pos, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!X || !Y || !cls || !rank || !pos || !workspace) return CLIPK_ERR_BAD_ARG;
+  if (Mx <= 0 || Ny <= 0 || P <= 0) return CLIPK_ERR_BAD_ARG;
+  if (P % 4 || !shape_ok(Mx, Ny, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (!labels && (label_offset < 0 || label_offset + Mx > Ny)) return CLIPK_ERR_BAD_ARG;
+  if (!aligned16(X) || !aligned16(Y)) return CLIPK_ERR_BAD_ARG;
+  if (workspace_bytes < clipk_sim_rank_workspace(Mx, Ny, P)) return CLIPK_ERR_BAD_ARG;
+  RKP p;
+  p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale; p.labels = labels; p.label_offset = label_offset;
+  p.part_cnt = static_cast<int*>(workspace); p.pos = pos; p.cls = cls;
+  int nqb, ksplit;
+  plan(Mx, Ny, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(sim_rank_kernel<true>, dim3(nqb, ksplit), dim3(256), 0, st, p);
   int rc = clipk_check_launch();
   if (rc) return rc;
   hipLaunchKernelGGL(sim_rank_finalize, dim3((Mx + 255) / 256), dim3(256), 0, st, (const int*)p.part_cnt, ksplit, Mx,

@@ -282,6 +282,39 @@ __global__ __launch_bounds__(256) void simce_lse_finalize(const float* part_ml, 
   if (lane == 0) lse[i] = m + logf(l);
 }
 
+// class-aware finalize: the (m, l) merge of simce_lse_finalize (the same arithmetic, so the same bits), the three
+// target sums of the splits in the same fixed order, then tgt = (1 - eps) q + eps / N sum_{D} S with q = S[i, label]
+// ("mask": the tiled pass left it in tgt) or the same-class mean ("positive")
+__global__ __launch_bounds__(256) void simce_lse_finalize_cls(const float* part_ml, const float* part_t, int ksplit, int Mx,
+                                                              int nkeys, int same_positive, float eps, float* lse,
+                                                              float* tgt, float* cnt) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= Mx) return;
+  float m = -INFINITY;
+  for (int s = lane; s < ksplit; s += 64) m = fmaxf(m, part_ml[((long)s * Mx + i) * 2]);
+  m = wave_max(m);
+  float l = 0.f;
+  for (int s = lane; s < ksplit; s += 64) {
+    const float ms = part_ml[((long)s * Mx + i) * 2], ls = part_ml[((long)s * Mx + i) * 2 + 1];
+    if (ms > -INFINITY) l += ls * expf(ms - m);
+  }
+  l = wave_sum(l);
+  float sd = 0.f, ss = 0.f, c = 0.f;
+  for (int s = lane; s < ksplit; s += 64) {
+    const float* t = part_t + ((long)s * Mx + i) * 3;
+    sd += t[0]; ss += t[1]; c += t[2];
+  }
+  sd = wave_sum(sd); ss = wave_sum(ss); c = wave_sum(c);
+  if (lane == 0) {
+    const float n = same_positive ? (float)nkeys : (float)nkeys - (c - 1.f);
+    const float q = same_positive ? ss / c : tgt[i];
+    lse[i] = m + logf(l);
+    tgt[i] = (1.f - eps) * q + eps * (sd / n);
+    cnt[i] = c;
+  }
+}
+
 __global__ void simce_grad_finalize(const float* slab, const float* dsc_part, int ksplit, int Mx, int P,
                                     const float* scale, float* dX, float* dscale_partial, long z_slab,
                                     long z_dsc) {
@@ -423,6 +456,89 @@ extern "C" int clipk_simce_lse(const float* X, int Mx, const float* Y, int Ny, c
   if (rc) return rc;
   hipLaunchKernelGGL(simce_lse_finalize, dim3((Mx + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                      (const float*)workspace, pl.ksplit, Mx, lse, 0L);
+  return clipk_check_launch();
+}
+
+// ---- class-aware pair: the tiled kernels' CLS instantiations (simce_tiled.hip), any Mx / Nkeys, P % 4 == 0, P <= 512
+extern "C" int clipk_simce_lse_tiled_cls_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc,
+                                                int P, const float* scale, int label_offset, const int64_t* cls_x,
+                                                const int64_t* cls_y, int same_positive, float* part_ml, float* part_t,
+                                                float* pos, void* stream);
+extern "C" int clipk_simce_grad_tiled_cls_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc,
+                                                 int P, const float* scale, int label_offset, const float* lse_x,
+                                                 const float* lse_y, const float* cnt_x, const float* cnt_y,
+                                                 const int64_t* cls_x, const int64_t* cls_y, int same_positive,
+                                                 float eps, int nkeys_y, float w_row, float w_col, float inv_bg,
+                                                 const float* upstream, float* slab, float* dsc_part, void* stream);
+
+static bool cls_shape_ok(int Mx, int Nkeys, int P) { return Mx > 0 && Nkeys > 0 && P > 0 && P % 4 == 0 && P <= 512; }
+
+extern "C" size_t clipk_simce_cls_workspace(int Mx, int Nkeys, int P) {
+  if (!cls_shape_ok(Mx, Nkeys, P)) return 0;
+  int nqb, ks2, ks3, tps, nt;
+  clipk_simce_tiled_plan(Mx, Nkeys, &nqb, &ks2, &tps, &nt);
+  clipk_simce_grad_tiled_plan(Mx, Nkeys, &nqb, &ks3, &tps, &nt);
+  const size_t a = (size_t)ks2 * Mx * 5 * sizeof(float);                   // (m, l) + target-sum partials
+  const size_t c = (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float);    // dX slabs + dscale partials
+  return a > c ? a : c;
+}
+
+static int cls_args_ok(const int64_t* cls_x, const int64_t* cls_y, int same_class, float eps) {
+  if ((cls_x == nullptr) != (cls_y == nullptr)) return 0;
+  if (same_class != CLIPK_SAME_CLASS_MASK && same_class != CLIPK_SAME_CLASS_POSITIVE) return 0;
+  return eps >= 0.f && eps < 1.f;
+}
+
+extern "C" int clipk_simce_lse_cls(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                                   const float* scale, int label_offset, const int64_t* cls_x, const int64_t* cls_y,
+                                   int same_class, float eps, float* lse, float* tgt, float* cnt, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  if (!X || !Y || !scale || !lse || !tgt || !cnt || !workspace || Nc < 0 || (Nc > 0 && !Yc)) return CLIPK_ERR_BAD_ARG;
+  if (!cls_args_ok(cls_x, cls_y, same_class, eps)) return CLIPK_ERR_BAD_ARG;
+  if (!cls_shape_ok(Mx, Ny + Nc, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (label_offset < 0 || (long)label_offset + Mx > Ny) return CLIPK_ERR_BAD_ARG;   // every row has its diagonal key
+  if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc))) return CLIPK_ERR_BAD_ARG;
+  int nqb, ks2, tps, nt;
+  clipk_simce_tiled_plan(Mx, Ny + Nc, &nqb, &ks2, &tps, &nt);
+  if (workspace_bytes < (size_t)ks2 * Mx * 5 * sizeof(float)) return CLIPK_ERR_BAD_ARG;
+  float* part_ml = (float*)workspace;
+  float* part_t = part_ml + (size_t)ks2 * Mx * 2;
+  const int positive = same_class == CLIPK_SAME_CLASS_POSITIVE;
+  int rc = clipk_simce_lse_tiled_cls_launch(X, Mx, Y, Ny, Yc, Nc, P, scale, label_offset, cls_x, cls_y, positive, part_ml,
+                                            part_t, tgt, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(simce_lse_finalize_cls, dim3((Mx + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)part_ml, (const float*)part_t, ks2, Mx, Ny + Nc, positive, eps, lse, tgt, cnt);
+  return clipk_check_launch();
+}
+
+extern "C" int clipk_simce_grad_cls(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                                    const float* scale, int label_offset, const float* lse_x, const float* lse_y,
+                                    const float* cnt_x, const float* cnt_y, const int64_t* cls_x, const int64_t* cls_y,
+                                    int same_class, float eps, int nkeys_y, float w_row, float w_col, float inv_bg,
+                                    const float* upstream, float* dX, float* dscale_partial, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  if (!X || !Y || !scale || !lse_x || !lse_y || !dX || !workspace || Nc < 0 || (Nc > 0 && !Yc)) return CLIPK_ERR_BAD_ARG;
+  if (!cls_args_ok(cls_x, cls_y, same_class, eps)) return CLIPK_ERR_BAD_ARG;
+  if ((w_row != 0.f && !cnt_x) || (w_col != 0.f && !cnt_y) || nkeys_y < Ny) return CLIPK_ERR_BAD_ARG;
+  if (!cls_shape_ok(Mx, Ny + Nc, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (label_offset < 0 || (long)label_offset + Mx > Ny) return CLIPK_ERR_BAD_ARG;
+  if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc)) || !aligned16(dX) || !aligned16(workspace))
+    return CLIPK_ERR_BAD_ARG;
+  int nqb, ks3, tps, nt;
+  clipk_simce_grad_tiled_plan(Mx, Ny + Nc, &nqb, &ks3, &tps, &nt);
+  if (workspace_bytes < (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float)) return CLIPK_ERR_BAD_ARG;
+  float* slab = (float*)workspace;
+  float* dscp = slab + (size_t)ks3 * Mx * P;
+  int rc = clipk_simce_grad_tiled_cls_launch(X, Mx, Y, Ny, Yc, Nc, P, scale, label_offset, lse_x, lse_y,
+                                             w_row != 0.f ? cnt_x : nullptr, w_col != 0.f ? cnt_y : nullptr, cls_x,
+                                             cls_y, same_class == CLIPK_SAME_CLASS_POSITIVE, eps, nkeys_y, w_row,
+                                             w_col, inv_bg, upstream, slab, dscp, stream);
+  if (rc) return rc;
+  long n4 = (long)Mx * P / 4;
+  int blocks = (int)((n4 + 63) / 64); if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(simce_grad_finalize, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)slab,
+                     (const float*)dscp, ks3, Mx, P, scale, dX, dscale_partial, 0L, 0L);
   return clipk_check_launch();
 }
 

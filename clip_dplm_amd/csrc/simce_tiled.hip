@@ -12,6 +12,12 @@
 //   * key-range splits write (m, l) partials that simce_lse_finalize merges in a fixed order, as before.
 // Numerics: the same k-ordered f32 fmaf chains per logit (the MFMA's arithmetic), a different but fixed summation order
 // of the exponentials; deterministic.
+//
+// Class-aware instantiation (CLS = true, include/clipk.h: clipk_simce_lse_cls / clipk_simce_grad_cls): the same tiles
+// with class ids on the pairs.  A lane loads the ids of its 16 key rows once per tile, before the tile's K-loop; keys of
+// the query's class other than its diagonal enter the running (max, sum) as -inf ("mask"), and the sums the target needs
+// (S over the denominator set, S over the same-class keys, their count) are kept next to (m, l) and merged in the same
+// fixed order.  CLS = false is the plain kernel: every class-aware line sits under `if constexpr`.
 #include "common.h"
 #include "sim_tile.h"
 #include <math.h>
@@ -29,12 +35,17 @@ struct LP {
   float* part_ml;      // [ksplit][Mx][2]
   float* pos;          // [Mx]
   int tiles_per_split, ntiles;
+  // class-aware instantiation only
+  const int64_t* cls_x; const int64_t* cls_y;   // [Mx] / [Ny] class ids, or both null (all distinct)
+  int same_positive;                            // 0: same-class keys leave the denominator ("mask"), 1: they stay
+  float* part_t;                                // [ksplit][Mx][3]: sum_{D_i} S, sum_{same} S, #same
 };
 
+template <bool CLS>
 __global__ __launch_bounds__(256, 2) void simce_lse_tiled_kernel(const LP p) {
   constexpr int BKL = 32;                                                 // 16 MFMAs per wave between barriers
   __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (BKL + 4)];   // 2 buffers x (keys | queries)
-  __shared__ float mrg[2][2][TQ];                                         // [key-wave][m | l][query]
+  __shared__ float mrg[2][CLS ? 5 : 2][TQ];                               // [key-wave][m | l (| sd | ss | c)][query]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;                                  // key half, query half
   const int li = lane & 31, h = lane >> 5;
@@ -45,6 +56,11 @@ __global__ __launch_bounds__(256, 2) void simce_lse_tiled_kernel(const LP p) {
   const int label = p.label_offset + qg;
   float m_run = -INFINITY, l_run = 0.f, pos_v = 0.f;
   bool pos_hit = false;
+  float sd = 0.f, ss = 0.f, cnt = 0.f;                                    // CLS: sum_{D} S, sum_{same} S, #same
+  int64_t cq = 0;
+  if constexpr (CLS) {
+    if (p.cls_x) cq = p.cls_x[qg < p.Mx ? qg : p.Mx - 1];
+  }
   const float* xrows[BKL / 16];
 #pragma unroll
   for (int i = 0; i < BKL / 16; ++i) {
@@ -62,18 +78,43 @@ __global__ __launch_bounds__(256, 2) void simce_lse_tiled_kernel(const LP p) {
       int j = j0 + (tid + i * 256) / (BKL / 4); j = j < Nkeys ? j : Nkeys - 1;      // clamped: masked in the epilogue
       yrows[i] = (j < p.Ny) ? p.Y + (long)j * P : p.Yc + (long)(j - p.Ny) * P;
     }
+    int64_t ck[16];                                                       // CLS: ids of this lane's 16 key rows
+    if constexpr (CLS) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = j0 + wm * 32 + keyrow32(r, h);
+        ck[r] = (p.cls_y && key < p.Ny) ? p.cls_y[key] : ~cq;             // cache keys / no ids: never same-class
+      }
+    }
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     s_tile<BKL>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
     // ---- softmax statistics of this lane's query over its 16 key rows of the tile
     float sv[16], tmax = -INFINITY;
+    if constexpr (CLS) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = j0 + wm * 32 + keyrow32(r, h);
-      sv[r] = key < Nkeys ? scale * acc[r] : -INFINITY;
-      tmax = fmaxf(tmax, sv[r]);
-      if (key == label && key < p.Ny) { pos_v = sv[r]; pos_hit = true; }
+      for (int r = 0; r < 16; ++r) {
+        const int key = j0 + wm * 32 + keyrow32(r, h);
+        const float s = scale * acc[r];
+        const bool diag = key == label && key < p.Ny;
+        const bool same = diag || ck[r] == cq;
+        const bool in_d = key < Nkeys && (p.same_positive || !same || diag);
+        sv[r] = in_d ? s : -INFINITY;
+        tmax = fmaxf(tmax, sv[r]);
+        if (diag) { pos_v = s; pos_hit = true; }
+        sd += in_d ? s : 0.f;
+        ss += same ? s : 0.f;
+        cnt += same ? 1.f : 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = j0 + wm * 32 + keyrow32(r, h);
+        sv[r] = key < Nkeys ? scale * acc[r] : -INFINITY;
+        tmax = fmaxf(tmax, sv[r]);
+        if (key == label && key < p.Ny) { pos_v = sv[r]; pos_hit = true; }
+      }
     }
     if (tmax > -INFINITY) {
       const float m_new = fmaxf(m_run, tmax);
@@ -93,8 +134,14 @@ __global__ __launch_bounds__(256, 2) void simce_lse_tiled_kernel(const LP p) {
     if (m_n > -INFINITY) l_n = l_run * expf(m_run - m_n) + l_o * expf(m_o - m_n);
     m_run = m_n; l_run = l_n;
   }
+  if constexpr (CLS) {
+    sd += __shfl_xor(sd, 32, 64); ss += __shfl_xor(ss, 32, 64); cnt += __shfl_xor(cnt, 32, 64);
+  }
   if (pos_hit && qg < p.Mx) p.pos[qg] = pos_v;                            // exactly one lane of the grid holds it
   if (h == 0) { mrg[wm][0][wn * 32 + li] = m_run; mrg[wm][1][wn * 32 + li] = l_run; }
+  if constexpr (CLS) {
+    if (h == 0) { mrg[wm][2][wn * 32 + li] = sd; mrg[wm][3][wn * 32 + li] = ss; mrg[wm][4][wn * 32 + li] = cnt; }
+  }
   __syncthreads();
   if (wm == 0 && h == 0 && qg < p.Mx) {
     const float m1 = mrg[1][0][wn * 32 + li], l1 = mrg[1][1][wn * 32 + li];
@@ -103,6 +150,10 @@ __global__ __launch_bounds__(256, 2) void simce_lse_tiled_kernel(const LP p) {
     if (m_n > -INFINITY) l_n = l_run * expf(m_run - m_n) + l1 * expf(m1 - m_n);
     float* o = p.part_ml + ((long)ks * p.Mx + qg) * 2;
     o[0] = m_n; o[1] = l_n;
+    if constexpr (CLS) {
+      float* t = p.part_t + ((long)ks * p.Mx + qg) * 3;
+      t[0] = sd + mrg[1][2][wn * 32 + li]; t[1] = ss + mrg[1][3][wn * 32 + li]; t[2] = cnt + mrg[1][4][wn * 32 + li];
+    }
   }
 }
 
@@ -128,6 +179,12 @@ struct GP2 {
   float* slab;         // [ksplit][Mx][P]
   float* dsc_part;     // [ksplit][Mx]
   int tiles_per_split, ntiles;
+  // class-aware instantiation only
+  const int64_t* cls_x; const int64_t* cls_y;   // [Mx] / [Ny] class ids, or both null (all distinct)
+  const float* cnt_x; const float* cnt_y;       // same-class counts c of the queries / of the keys (null: w = 0 side)
+  int same_positive;
+  float eps;
+  float nkeys_y;                                // key count of the column direction (its denominator before masking)
 };
 
 constexpr int GPMAX = 512;                         // contraction / output width limit of the tiled gradient pass
@@ -136,6 +193,7 @@ constexpr int KSB = 16;                            // keys per staged block of t
 constexpr int BKG = 16;                            // K-step of the gradient pass's S tile (LDS budget: 2 workgroups per CU)
 constexpr int GRAD_LDS_FLOATS = 2 * 2 * 64 * (BKG + 4) + TK * TQ + KSB * YH_LD + 2 * TQ;
 
+template <bool CLS>
 __global__ __launch_bounds__(256, 2) void simce_grad_tiled_kernel(const GP2 p) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* smem = reinterpret_cast<float*>(smem_raw);                      // K-loop buffers
@@ -162,6 +220,15 @@ __global__ __launch_bounds__(256, 2) void simce_grad_tiled_kernel(const GP2 p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) dx[a][b][r] = 0.f;
   float dsc = 0.f;
+  int64_t cq = 0;                                 // CLS: the query's id, 1 / c_i, eps / N_i
+  float inv_cx = 1.f, eps_nx = 0.f;
+  if constexpr (CLS) {
+    const int qc = qg < p.Mx ? qg : p.Mx - 1;
+    if (p.cls_x) cq = p.cls_x[qc];
+    const float cx = p.cnt_x ? p.cnt_x[qc] : 1.f;
+    inv_cx = 1.f / cx;
+    eps_nx = p.eps / (p.same_positive ? (float)Nkeys : (float)Nkeys - (cx - 1.f));
+  }
 
   const float* xrows[1];
   { int q = q0 + (tid >> 2); q = q < p.Mx ? q : p.Mx - 1; xrows[0] = p.X + (long)q * P; }
@@ -186,13 +253,32 @@ __global__ __launch_bounds__(256, 2) void simce_grad_tiled_kernel(const GP2 p) {
       const int key = j0 + kl;
       const float sv = scale * acc[r];
       float gv = 0.f;
-      if (key < Nkeys && qg < p.Mx) {
-        gv = p.w_row * expf(sv - lse_xi);
-        if (key < p.Ny) {
-          gv += p.w_col * expf(sv - p.lse_y[key]);
-          if (key == label) gv -= (p.w_row + p.w_col);
+      if constexpr (CLS) {
+        // w_row ([j in D_i] P_row - T[i,j]) + w_col ([i in D'_j] P_col - T'[j,i]); `same` is symmetric, so is D
+        if (key < Nkeys && qg < p.Mx) {
+          const bool kin = key < p.Ny;
+          const bool diag = kin && key == label;
+          const bool same = diag || (kin && p.cls_y && p.cls_y[key] == cq);
+          const bool in_d = p.same_positive || !same || diag;
+          const float hard = p.same_positive ? (same ? inv_cx : 0.f) : (diag ? 1.f : 0.f);
+          gv = p.w_row * ((in_d ? expf(sv - lse_xi) : 0.f) - ((1.f - p.eps) * hard + (in_d ? eps_nx : 0.f)));
+          if (kin) {
+            const float cy = p.cnt_y ? p.cnt_y[key] : 1.f;
+            const float hy = p.same_positive ? (same ? 1.f / cy : 0.f) : (diag ? 1.f : 0.f);
+            const float ny = p.same_positive ? p.nkeys_y : p.nkeys_y - (cy - 1.f);
+            gv += p.w_col * ((in_d ? expf(sv - p.lse_y[key]) : 0.f) - ((1.f - p.eps) * hy + (in_d ? p.eps / ny : 0.f)));
+          }
+          gv *= ibg;
         }
-        gv *= ibg;
+      } else {
+        if (key < Nkeys && qg < p.Mx) {
+          gv = p.w_row * expf(sv - lse_xi);
+          if (key < p.Ny) {
+            gv += p.w_col * expf(sv - p.lse_y[key]);
+            if (key == label) gv -= (p.w_row + p.w_col);
+          }
+          gv *= ibg;
+        }
       }
       dsc += gv * acc[r];
       gl[kl * TQ + wn * 32 + li] = gv;
@@ -286,35 +372,73 @@ extern "C" void clipk_simce_grad_tiled_plan(int Mx, int Nkeys, int* nqb, int* ks
   *ksplit = (*ntiles + *tps - 1) / *tps;
 }
 
+namespace {
+template <bool CLS>
+int grad_tiled_launch(GP2& p, int Mx, int Nkeys, void* stream) {
+  int nqb, ksplit;
+  clipk_simce_grad_tiled_plan(Mx, Nkeys, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  const size_t lds = (size_t)GRAD_LDS_FLOATS * sizeof(float);
+  static std::atomic<uint64_t> attr_set{0};
+  clipk_once_per_device(attr_set, [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(simce_grad_tiled_kernel<CLS>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  });
+  hipLaunchKernelGGL(simce_grad_tiled_kernel<CLS>, dim3(nqb, ksplit), dim3(256), lds, (hipStream_t)stream, p);
+  return clipk_check_launch();
+}
+}  // namespace
+
 extern "C" int clipk_simce_grad_tiled_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc,
                                              int P, const float* scale, int label_offset, const float* lse_x,
                                              const float* lse_y, float w_row, float w_col, float inv_bg,
                                              const float* upstream, float* slab, float* dsc_part, void* stream) {
   if (P > GPMAX) return CLIPK_ERR_UNSUPPORTED;
-  GP2 p;
+  GP2 p{};
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.Yc = Yc ? Yc : Y; p.Nc = Nc; p.P = P;
   p.scale = scale; p.label_offset = label_offset; p.lse_x = lse_x; p.lse_y = lse_y;
   p.w_row = w_row; p.w_col = w_col; p.inv_bg = inv_bg; p.upstream = upstream; p.slab = slab; p.dsc_part = dsc_part;
-  int nqb, ksplit;
-  clipk_simce_grad_tiled_plan(Mx, Ny + Nc, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
-  const size_t lds = (size_t)GRAD_LDS_FLOATS * sizeof(float);
-  static std::atomic<uint64_t> attr_set{0};
-  clipk_once_per_device(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(simce_grad_tiled_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
-  hipLaunchKernelGGL(simce_grad_tiled_kernel, dim3(nqb, ksplit), dim3(256), lds, (hipStream_t)stream, p);
-  return clipk_check_launch();
+  return grad_tiled_launch<false>(p, Mx, Ny + Nc, stream);
+}
+
+extern "C" int clipk_simce_grad_tiled_cls_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc,
+                                                 int P, const float* scale, int label_offset, const float* lse_x,
+                                                 const float* lse_y, const float* cnt_x, const float* cnt_y,
+                                                 const int64_t* cls_x, const int64_t* cls_y, int same_positive,
+                                                 float eps, int nkeys_y, float w_row, float w_col, float inv_bg,
+                                                 const float* upstream, float* slab, float* dsc_part, void* stream) {
+  if (P > GPMAX) return CLIPK_ERR_UNSUPPORTED;
+  GP2 p{};
+  p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.Yc = Yc ? Yc : Y; p.Nc = Nc; p.P = P;
+  p.scale = scale; p.label_offset = label_offset; p.lse_x = lse_x; p.lse_y = lse_y;
+  p.w_row = w_row; p.w_col = w_col; p.inv_bg = inv_bg; p.upstream = upstream; p.slab = slab; p.dsc_part = dsc_part;
+  p.cls_x = cls_x; p.cls_y = cls_y; p.cnt_x = cnt_x; p.cnt_y = cnt_y; p.same_positive = same_positive; p.eps = eps;
+  p.nkeys_y = (float)nkeys_y;
+  return grad_tiled_launch<true>(p, Mx, Ny + Nc, stream);
 }
 
 extern "C" int clipk_simce_lse_tiled_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
                                             const float* scale, int label_offset, float* part_ml, float* pos,
                                             void* stream) {
-  LP p;
+  LP p{};
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.Yc = Yc ? Yc : Y; p.Nc = Nc; p.P = P;
   p.scale = scale; p.label_offset = label_offset; p.part_ml = part_ml; p.pos = pos;
   int nqb, ksplit;
   clipk_simce_tiled_plan(Mx, Ny + Nc, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
-  hipLaunchKernelGGL(simce_lse_tiled_kernel, dim3(nqb, ksplit), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(simce_lse_tiled_kernel<false>, dim3(nqb, ksplit), dim3(256), 0, (hipStream_t)stream, p);
+  return clipk_check_launch();
+}
+
+// pos: S[i, label(i)] lands here (the class-aware finalize turns it into the target); part_t: [ksplit][Mx][3]
+extern "C" int clipk_simce_lse_tiled_cls_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc,
+                                                int P, const float* scale, int label_offset, const int64_t* cls_x,
+                                                const int64_t* cls_y, int same_positive, float* part_ml, float* part_t,
+                                                float* pos, void* stream) {
+  LP p{};
+  p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.Yc = Yc ? Yc : Y; p.Nc = Nc; p.P = P;
+  p.scale = scale; p.label_offset = label_offset; p.part_ml = part_ml; p.pos = pos;
+  p.cls_x = cls_x; p.cls_y = cls_y; p.same_positive = same_positive; p.part_t = part_t;
+  int nqb, ksplit;
+  clipk_simce_tiled_plan(Mx, Ny + Nc, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  hipLaunchKernelGGL(simce_lse_tiled_kernel<true>, dim3(nqb, ksplit), dim3(256), 0, (hipStream_t)stream, p);
   return clipk_check_launch();
 }

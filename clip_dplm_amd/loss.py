@@ -5,6 +5,9 @@ Reference losses covered (weights select the variant):
   * symmetric  (CE(S) + CE(S^T)) / 2              current/rna_clip_codes.ipynb:1952-1953    (0.5, 0.5)
   * cache-negative variant                        old/clip_opt.py:130-151                   (0.5, 0.5, cache=...)
   * global batch over ranks                       old/clip_opt.py:102-112 — but differentiable
+  * class-aware / label-smoothed InfoNCE          class_ids=, same_class=, label_smoothing= (include/clipk.h:
+                                                  clipk_simce_lse_cls): pairs that share a partner stop being each
+                                                  other's negatives ("mask") or become positives ("positive")
 
 Multi-GPU scheme: one all-gather of the stacked embeddings [2, B_l, P], one
 all-gather of the two LSE vectors [2, B_l]; every rank then computes the COMPLETE gradient of the global
@@ -101,19 +104,126 @@ class ClipLossFn(torch.autograd.Function):
         return da, db, dscale, None, None, None, None
 
 
+class ClassAwareClipLossFn(torch.autograd.Function):
+    """ClipLossFn with class ids on the pairs and / or label smoothing (clipk_simce_lse_cls / clipk_simce_grad_cls).
+    Multi-GPU: the ids take one more all-gather, the same-class counts travel with the LSE gather ([W, 4, Bl])."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, ids, same_class, eps, w_row, w_col, cache, group):
+        a, b = a.contiguous(), b.contiguous()
+        cache = None if cache is None else cache.contiguous()
+        scale = scale.reshape(1).contiguous()
+        bl = a.shape[0]
+        if group is not None:
+            world, rank = dist.get_world_size(group), dist.get_rank(group)
+            both = _gather_cat(torch.stack([a, b]), group)                 # [W, 2, Bl, P]
+            a_g = both[:, 0].reshape(world * bl, -1)
+            b_g = both[:, 1].reshape(world * bl, -1)
+            ids_g = None if ids is None else _gather_cat(ids, group).reshape(-1)
+        else:
+            world, rank, a_g, b_g, ids_g = 1, 0, a, b, ids
+        off = rank * bl
+        bg = world * bl
+        nc = 0 if cache is None else cache.shape[0]
+        kw = dict(cls_x=ids, cls_y=ids_g, same_class=same_class, eps=eps, label_offset=off)
+        lse_r, tgt_r, cnt_r = _kernels.simce_lse_cls(a, b_g, scale, cache=cache, **kw)
+        if w_col != 0.0:
+            lse_c, tgt_c, cnt_c = _kernels.simce_lse_cls(b, a_g, scale, **kw)
+        else:
+            lse_c, tgt_c, cnt_c = _inf_like(lse_r), None, cnt_r       # the unused direction contributes nothing
+        if group is None:
+            out = _kernels.ce_combine(lse_r, tgt_r, lse_c if tgt_c is not None else None, tgt_c, w_row, w_col, bg)
+            lse_r_g, lse_c_g, cnt_r_g, cnt_c_g = lse_r, lse_c, cnt_r, cnt_c
+        else:
+            local = w_row * (lse_r - tgt_r).sum()
+            if tgt_c is not None:
+                local = local + w_col * (lse_c - tgt_c).sum()
+            stats = _gather_cat(torch.stack([lse_r, lse_c, cnt_r, cnt_c]), group)    # [W, 4, Bl]
+            lse_r_g, lse_c_g, cnt_r_g, cnt_c_g = (stats[:, k].reshape(-1).contiguous() for k in range(4))
+            dist.all_reduce(local, group=group)
+            out = local / bg
+        ctx.meta = (same_class, eps, w_row, w_col, off, bg, nc, cache)
+        ctx.save_for_backward(a, b, a_g, b_g, scale, ids, ids_g, lse_r, lse_c, cnt_r, cnt_c, lse_r_g, lse_c_g, cnt_r_g,
+                              cnt_c_g)
+        return out
+
+    @staticmethod
+    def backward(ctx, dloss):
+        a, b, a_g, b_g, scale, ids, ids_g, lse_r, lse_c, cnt_r, cnt_c, lse_r_g, lse_c_g, cnt_r_g, cnt_c_g = ctx.saved_tensors
+        same_class, eps, w_row, w_col, off, bg, nc, cache = ctx.meta
+        g = dloss.reshape(1).contiguous() if dloss.numel() == 1 else None
+        kw = dict(cls_x=ids, cls_y=ids_g, same_class=same_class, eps=eps, label_offset=off, upstream=g)
+        # rows of a: their own direction has the cache keys, the column direction (rows of b) has the Bg rows of a
+        da, dsa = _kernels.simce_grad_cls(a, b_g, scale, lse_r, lse_c_g, cnt_r, cnt_c_g, w_row, w_col, 1.0 / bg, bg,
+                                          cache=cache, **kw)
+        # rows of b are the queries of the column direction; the keys' (a's) own direction has Bg + Nc keys
+        db, _ = _kernels.simce_grad_cls(b, a_g, scale, lse_c, lse_r_g, cnt_c, cnt_r_g, w_col, w_row, 1.0 / bg, bg + nc,
+                                        **kw)
+        dscale = dsa.sum().reshape(1)
+        return da, db, dscale, None, None, None, None, None, None, None
+
+
+SAME_CLASS_MODES = ("mask", "positive")
+
+
+def _check_class_args(a, b, cache, class_ids, same_class, label_smoothing):
+    """Validate the class-aware arguments (ValueError); returns (ids as contiguous int64 or None, eps)."""
+    if same_class not in SAME_CLASS_MODES:
+        raise ValueError(f"same_class must be one of {SAME_CLASS_MODES}, got {same_class!r}")
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)):
+        raise ValueError(f"label_smoothing must be a number in [0, 1), got {label_smoothing!r}")
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {eps}")
+    if class_ids is None and eps == 0.0:
+        return None, eps
+    if a.dim() != 2 or a.shape != b.shape:
+        raise ValueError(f"embeddings must be two [B, P] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    for name, t in (("a_embeds", a), ("b_embeds", b), ("cache", cache)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"class-aware / label-smoothed InfoNCE takes float32 embeddings, {name} is {t.dtype}")
+    P = a.shape[1]
+    if cache is not None and (cache.dim() != 2 or cache.shape[1] != P):
+        raise ValueError(f"cache must be [Nc, {P}], got {tuple(cache.shape)}")
+    if P % 4 or P > 512:
+        raise ValueError(f"class-aware / label-smoothed InfoNCE supports P % 4 == 0 and P <= 512, got P = {P}")
+    if class_ids is None:
+        return None, eps
+    if not torch.is_tensor(class_ids):
+        raise ValueError(f"class_ids must be a tensor, got {type(class_ids).__name__}")
+    if class_ids.dtype.is_floating_point or class_ids.dtype.is_complex or class_ids.dtype == torch.bool:
+        raise ValueError(f"class_ids must be an integer tensor, got {class_ids.dtype}")
+    if tuple(class_ids.shape) != (a.shape[0],):
+        raise ValueError(f"class_ids must have shape ({a.shape[0]},), got {tuple(class_ids.shape)}")
+    if class_ids.device != a.device:
+        raise ValueError(f"class_ids are on {class_ids.device}, the embeddings on {a.device}")
+    return class_ids.to(torch.int64).contiguous(), eps
+
+
 def clip_loss(a_embeds: torch.Tensor, b_embeds: torch.Tensor, logit_scale_exp: torch.Tensor, *,
               symmetric: bool = True, cache: Optional[torch.Tensor] = None, group=None,
-              w_row: Optional[float] = None, w_col: Optional[float] = None) -> torch.Tensor:
+              w_row: Optional[float] = None, w_col: Optional[float] = None,
+              class_ids: Optional[torch.Tensor] = None, same_class: str = "mask",
+              label_smoothing: float = 0.0) -> torch.Tensor:
     """InfoNCE over L2-normalised embeddings [B_local, P] (f32).  `logit_scale_exp` = exp(logit_scale)
     (already clamped if the model clamps, old/clip_opt.py:100).  With `group`, the batch is the concatenation
-    over ranks in rank order and the returned value is the global-batch loss on every rank."""
+    over ranks in rank order and the returned value is the global-batch loss on every rank.
+
+    class_ids: integer [B_local] on the embeddings' device, one id per pair (pairs that share a partner share an id).
+    same_class="mask" drops the other same-class keys from each row's softmax; "positive" keeps them and spreads the
+    target over them (supervised contrastive).  label_smoothing: eps in [0, 1), torch's convention (eps / N on every
+    key of the row's softmax).  Cache rows carry no class.  Defaults: exactly the plain loss and its kernels."""
+    ids, eps = _check_class_args(a_embeds, b_embeds, cache, class_ids, same_class, label_smoothing)
     if w_row is None:
         w_row, w_col = (0.5, 0.5) if symmetric else (1.0, 0.0)
     if group is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         group = dist.group.WORLD
     if group is not None and dist.get_world_size(group) == 1 and not os.environ.get("CLIPK_FORCE_DIST"):
         group = None                         # (CLIPK_FORCE_DIST keeps the collective path for 1-rank RCCL rehearsals)
-    return ClipLossFn.apply(a_embeds, b_embeds, logit_scale_exp, float(w_row), float(w_col), cache, group)
+    if ids is None and eps == 0.0:
+        return ClipLossFn.apply(a_embeds, b_embeds, logit_scale_exp, float(w_row), float(w_col), cache, group)
+    return ClassAwareClipLossFn.apply(a_embeds, b_embeds, logit_scale_exp, ids, same_class, eps, float(w_row),
+                                      float(w_col), cache, group)
 
 
 def contrastive_loss(x: torch.Tensor, y: torch.Tensor, temperature: float = 0.1, queue: Optional[torch.Tensor] = None,

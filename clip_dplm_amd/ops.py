@@ -312,6 +312,81 @@ def simce_grad(x, y, scale, lse_x, lse_y, w_row, w_col, inv_bg, label_offset=0, 
     return dx, dsc
 
 
+def _cls_args(x, y, scale, cache, cls_x, cls_y, same_class, eps, vectors=()):
+    """Shapes and dtypes of the class-aware passes' operands (the kernels read them as raw f32 / int64 arrays of these
+    lengths): ValueError on anything else.  vectors: (name, tensor or None, length) of further f32 [length] inputs."""
+    def f32(name, t, shape):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape}, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    if x.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"x and y must be 2-D, got {tuple(x.shape)} and {tuple(y.shape)}")
+    Mx, P = x.shape
+    Ny = y.shape[0]
+    f32("x", x, (Mx, P))
+    f32("y", y, (Ny, P))
+    if cache is not None:
+        f32("cache", cache, (cache.shape[0], P))
+    if scale.dtype != torch.float32 or scale.numel() != 1:
+        raise ValueError(f"scale must be a 1-element float32 tensor, got {scale.dtype} {tuple(scale.shape)}")
+    if (cls_x is None) != (cls_y is None):
+        raise ValueError("cls_x and cls_y: both or neither")
+    for name, t, n in (("cls_x", cls_x, Mx), ("cls_y", cls_y, Ny)):
+        if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != (n,) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int64 tensor of shape ({n},), got {t.dtype} {tuple(t.shape)}")
+    for name, t, n in vectors:
+        if t is not None:
+            f32(name, t, (n,))
+    if same_class not in _ffi.SAME_CLASS:
+        raise ValueError(f"same_class must be one of {tuple(_ffi.SAME_CLASS)}, got {same_class!r}")
+    if not 0.0 <= float(eps) < 1.0:
+        raise ValueError(f"eps must be in [0, 1), got {eps}")
+    return Mx, Ny, P, 0 if cache is None else cache.shape[0]
+
+
+def simce_lse_cls(x, y, scale, cls_x=None, cls_y=None, same_class="mask", eps=0.0, label_offset=0, cache=None):
+    """Class-aware LSE pass (include/clipk.h: clipk_simce_lse_cls): (lse, tgt, cnt), each f32 [Mx].  cls_x [Mx] /
+    cls_y [Ny]: device int64 class ids, both or neither (None: all distinct); the cache rows carry no class."""
+    Mx, Ny, P, Nc = _cls_args(x, y, scale, cache, cls_x, cls_y, same_class, eps)
+    _need_cuda(x, y, scale, cache, cls_x, cls_y)
+    lse = torch.empty(Mx, dtype=torch.float32, device=x.device)
+    tgt = torch.empty(Mx, dtype=torch.float32, device=x.device)
+    cnt = torch.empty(Mx, dtype=torch.float32, device=x.device)
+    lib = _lib()
+    nbytes = lib.clipk_simce_cls_workspace(Mx, Ny + Nc, P)
+    if nbytes == 0:
+        raise _ffi.ClipkError(f"simce (class-aware): unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
+    ws = workspace(nbytes, x.device, "simce")
+    check(lib.clipk_simce_lse_cls(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), label_offset,
+                                  ptr(cls_x), ptr(cls_y), _ffi.SAME_CLASS[same_class], float(eps), lse.data_ptr(),
+                                  tgt.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "clipk_simce_lse_cls")
+    return lse, tgt, cnt
+
+
+def simce_grad_cls(x, y, scale, lse_x, lse_y, cnt_x, cnt_y, w_row, w_col, inv_bg, nkeys_y, cls_x=None, cls_y=None,
+                   same_class="mask", eps=0.0, label_offset=0, cache=None, upstream=None):
+    """Class-aware gradient pass (include/clipk.h: clipk_simce_grad_cls): (dx, dscale partials).  nkeys_y: the key
+    count of the column direction (its rows' denominator before masking)."""
+    Mx, Ny, P, Nc = _cls_args(x, y, scale, cache, cls_x, cls_y, same_class, eps,
+                              (("lse_x", lse_x, x.shape[0]), ("lse_y", lse_y, y.shape[0]), ("cnt_x", cnt_x, x.shape[0]),
+                               ("cnt_y", cnt_y, y.shape[0]), ("upstream", upstream, 1)))
+    _need_cuda(x, y, scale, lse_x, lse_y, cnt_x, cnt_y, cls_x, cls_y, cache, upstream)
+    dx = torch.empty_like(x)
+    dsc = torch.empty(Mx, dtype=torch.float32, device=x.device)
+    lib = _lib()
+    nbytes = lib.clipk_simce_cls_workspace(Mx, Ny + Nc, P)
+    if nbytes == 0:
+        raise _ffi.ClipkError(f"simce (class-aware): unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
+    ws = workspace(nbytes, x.device, "simce")
+    check(lib.clipk_simce_grad_cls(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), label_offset,
+                                   lse_x.data_ptr(), lse_y.data_ptr(), ptr(cnt_x), ptr(cnt_y), ptr(cls_x), ptr(cls_y),
+                                   _ffi.SAME_CLASS[same_class], float(eps), int(nkeys_y), float(w_row), float(w_col),
+                                   float(inv_bg), ptr(upstream), dx.data_ptr(), dsc.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   _stream()), "clipk_simce_grad_cls")
+    return dx, dsc
+
+
 def _pairs_arrays(pairs):
     flat = [int(v) for pr in pairs for v in pr]
     rev = [pairs.index((b, a)) if (b, a) in pairs else i for i, (a, b) in enumerate(pairs)]
@@ -397,24 +472,33 @@ def sim_topk(x, y, k: int, scale: Optional[float] = None):
     return scores, idx
 
 
-def sim_rank(x, y, labels=None, label_offset: int = 0, scale: Optional[float] = None):
+def sim_rank(x, y, labels=None, label_offset: int = 0, scale: Optional[float] = None, class_ids=None):
     """(rank int64 [Mx], pos f32 [Mx]): 0-based rank of key l_i in row i of S = scale * x y^T under the same order as
     sim_topk, and S[i, l_i] (include/clipk.h: clipk_sim_rank).  l_i = labels[i] (device int64 [Mx]) or label_offset + i.
-    A label outside [0, Ny) gives rank -1 and pos NaN."""
+    A label outside [0, Ny) gives rank -1 and pos NaN.  class_ids (device int64 [Ny], gallery class ids): count only
+    gallery rows of another class than l_i's (clipk_sim_rank_cls)."""
     Mx, Ny, P = _retrieval_args(x, y)
     if labels is not None:
         if labels.dtype != torch.int64 or labels.shape != (Mx,) or not labels.is_contiguous():
             raise ValueError(f"labels must be a contiguous int64 tensor of shape ({Mx},)")
     elif not (0 <= int(label_offset) and int(label_offset) + Mx <= Ny):
         raise ValueError(f"labels label_offset + i = {label_offset} .. {int(label_offset) + Mx - 1} outside [0, {Ny})")
-    _need_cuda(x, y, labels)
+    if class_ids is not None:
+        if class_ids.dtype != torch.int64 or class_ids.shape != (Ny,) or not class_ids.is_contiguous():
+            raise ValueError(f"class_ids must be a contiguous int64 tensor of shape ({Ny},)")
+    _need_cuda(x, y, labels, class_ids)
     rank = torch.empty(Mx, dtype=torch.int64, device=x.device)
     pos = torch.empty(Mx, dtype=torch.float32, device=x.device)
     lib = _lib()
     ws = workspace(lib.clipk_sim_rank_workspace(Mx, Ny, P), x.device, "retrieval")
-    check(lib.clipk_sim_rank(x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale),
-                             ptr(labels), int(label_offset), rank.data_ptr(), pos.data_ptr(), ws.data_ptr(), ws.numel(),
-                             _stream()), "clipk_sim_rank")
+    sc = 1.0 if scale is None else float(scale)
+    if class_ids is None:
+        check(lib.clipk_sim_rank(x.data_ptr(), Mx, y.data_ptr(), Ny, P, sc, ptr(labels), int(label_offset),
+                                 rank.data_ptr(), pos.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipk_sim_rank")
+    else:
+        check(lib.clipk_sim_rank_cls(x.data_ptr(), Mx, y.data_ptr(), Ny, P, sc, ptr(labels), int(label_offset),
+                                     class_ids.data_ptr(), rank.data_ptr(), pos.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     _stream()), "clipk_sim_rank_cls")
     return rank, pos
 
 

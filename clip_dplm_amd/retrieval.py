@@ -7,6 +7,10 @@ confusion matrix and failure analysis from that argmax (:265, :423) and material
 
 Order everywhere: score descending, equal scores by the lower gallery index (torch.argmax's first-occurrence rule), so
 rank 0 is exactly the reference's "correct" and results do not depend on how the gallery is split or chunked.
+
+Class ids (`class_ids=`): where several pairs share a partner (one RBP bound by many RNAs), their gallery rows are
+identical and tie-breaking by index caps recall@1 below 1 even for a perfect model.  With ids the rank counts only gallery
+rows of another class than the positive (include/clipk.h: clipk_sim_rank_cls); with all ids distinct it is the plain rank.
 """
 from __future__ import annotations
 
@@ -34,13 +38,25 @@ def topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, scale: Optional[f
     return ops.sim_topk(_as_f32(queries, "queries"), _as_f32(gallery, "gallery"), k, scale)
 
 
+def _as_ids(t: torch.Tensor, n: int, device, name: str) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"{name} must be an integer tensor")
+    t = t.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+    if t.numel() != n:
+        raise ValueError(f"{name} must hold {n} ids, got {t.numel()}")
+    return t
+
+
 def ranks(queries: torch.Tensor, gallery: torch.Tensor, labels: Optional[torch.Tensor] = None,
-          scale: Optional[float] = None) -> torch.Tensor:
-    """0-based rank (int64 [Mq]) of each query's positive gallery row: labels[i], or i when labels is None."""
+          scale: Optional[float] = None, class_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """0-based rank (int64 [Mq]) of each query's positive gallery row: labels[i], or i when labels is None.
+    class_ids [Ng]: gallery class ids; only rows of another class than the positive's count."""
     q, g = _as_f32(queries, "queries"), _as_f32(gallery, "gallery")
     if labels is not None:
         labels = labels.to(device=q.device, dtype=torch.int64).contiguous()
-    return ops.sim_rank(q, g, labels=labels, scale=scale)[0]
+    if class_ids is not None:
+        class_ids = _as_ids(class_ids, g.shape[0], q.device, "class_ids")
+    return ops.sim_rank(q, g, labels=labels, scale=scale, class_ids=class_ids)[0]
 
 
 def metrics_from_ranks(ranks, ks: Sequence[int] = (1, 5, 10)) -> Dict[str, float]:
@@ -61,21 +77,26 @@ def metrics_from_ranks(ranks, ks: Sequence[int] = (1, 5, 10)) -> Dict[str, float
 
 
 def retrieval_metrics(a_embeds: torch.Tensor, b_embeds: torch.Tensor, ks: Sequence[int] = (1, 5, 10),
-                      labels: Optional[torch.Tensor] = None) -> Dict[str, Optional[Dict[str, float]]]:
+                      labels: Optional[torch.Tensor] = None,
+                      class_ids: Optional[torch.Tensor] = None) -> Dict[str, Optional[Dict[str, float]]]:
     """{"a_to_b": ..., "b_to_a": ...}: a_i's positive is b[labels[i]] (b_i when labels is None).  b_to_a needs the
-    inverse pairing: it is None when labels is not a permutation of range(len(b))."""
+    inverse pairing: it is None when labels is not a permutation of range(len(b)).
+    class_ids: the pairs' class ids, one per row of b (pairs that share a partner share an id); a row of a has its
+    positive's id.  Both directions then rank among the rows of other classes only."""
     na, nb = a_embeds.shape[0], b_embeds.shape[0]
+    ids_b = None if class_ids is None else _as_ids(class_ids, nb, a_embeds.device, "class_ids")
     if labels is None:
         if na != nb:
             raise ValueError(f"paired embeddings need equal counts, got {na} and {nb}")
-        return {"a_to_b": metrics_from_ranks(ranks(a_embeds, b_embeds), ks),
-                "b_to_a": metrics_from_ranks(ranks(b_embeds, a_embeds), ks)}
+        return {"a_to_b": metrics_from_ranks(ranks(a_embeds, b_embeds, class_ids=ids_b), ks),
+                "b_to_a": metrics_from_ranks(ranks(b_embeds, a_embeds, class_ids=ids_b), ks)}
     labels = labels.to(device=a_embeds.device, dtype=torch.int64).reshape(-1)
-    out = {"a_to_b": metrics_from_ranks(ranks(a_embeds, b_embeds, labels), ks), "b_to_a": None}
+    out = {"a_to_b": metrics_from_ranks(ranks(a_embeds, b_embeds, labels, class_ids=ids_b), ks), "b_to_a": None}
     if na == nb and torch.equal(torch.sort(labels).values, torch.arange(nb, device=labels.device)):
         inv = torch.empty_like(labels)
         inv[labels] = torch.arange(na, device=labels.device)
-        out["b_to_a"] = metrics_from_ranks(ranks(b_embeds, a_embeds, inv), ks)
+        ids_a = None if ids_b is None else ids_b[labels]
+        out["b_to_a"] = metrics_from_ranks(ranks(b_embeds, a_embeds, inv, class_ids=ids_a), ks)
     return out
 
 

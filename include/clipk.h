@@ -166,6 +166,45 @@ int clipk_simce_grad_scaled(const float* X, int Mx, const float* Y, int Ny, cons
 int clipk_ce_combine(const float* lse_r, const float* pos_r, const float* lse_c, const float* pos_c, int n,
                      float w_row, float w_col, float bg, float* loss, void* stream);
 
+/* Class-aware InfoNCE: pairs carry class ids, so pairs that share a partner (one RBP bound by many RNAs, one
+ * perturbation over many cells) are no longer each other's negatives.  For query row i with diagonal key
+ * l = label_offset + i, keys j over the Ny batch keys and then the Nc cache keys, S[i,j] = scale * <X_i, Y_j>:
+ *   same[i,j] = (j < Ny) and (j == l or cls_y[j] == cls_x[i])       the diagonal always; cache keys never
+ *   D_i       = all keys except {j != l : same[i,j]}   (same_class = CLIPK_SAME_CLASS_MASK)
+ *             = all keys                               (same_class = CLIPK_SAME_CLASS_POSITIVE, supervised contrastive)
+ *   N_i = |D_i|,  c_i = #{j : same[i,j]}
+ *   q[i,j]    = [j == l] (mask)  or  same[i,j] / c_i (positive)
+ *   T[i,j]    = (1 - eps) q[i,j] + eps / N_i [j in D_i]        eps = label smoothing in [0, 1)
+ *   lse[i] = log sum_{j in D_i} exp S[i,j],   tgt[i] = sum_j T[i,j] S[i,j],   cnt[i] = c_i
+ * The loss is clipk_ce_combine with tgt in place of pos.  With no ids (cls_x = cls_y = NULL: all distinct) and eps > 0
+ * this is F.cross_entropy(S, arange, label_smoothing=eps) over [S | S_cache] (torch's convention: eps / N on every key,
+ * the diagonal's included); with distinct ids and eps = 0 it is the plain loss.  Its lse then has the bits of
+ * clipk_simce_lse's tiled LSE pass, which clipk_simce_lse runs for Mx >= 64 and Ny + Nc >= 64 (or with option
+ * simce_kernel = 2); for smaller shapes clipk_simce_lse defaults to the first-generation kernel, whose summation order
+ * differs, and the two agree to rounding only.
+ * cls_x [Mx], cls_y [Ny]: device int64, both or neither.  label_offset + Mx <= Ny.  All work stays on the device.
+ * Requirements: P % 4 == 0, P <= 512 (else CLIPK_ERR_UNSUPPORTED).  workspace: clipk_simce_cls_workspace(Mx, Ny + Nc, P)
+ * bytes (covers both passes).  Key-split partials merge in a fixed order: deterministic. */
+enum { CLIPK_SAME_CLASS_MASK = 0, CLIPK_SAME_CLASS_POSITIVE = 1 };
+size_t clipk_simce_cls_workspace(int Mx, int Nkeys, int P);
+int clipk_simce_lse_cls(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                        const float* scale, int label_offset, const int64_t* cls_x, const int64_t* cls_y,
+                        int same_class, float eps, float* lse /*[Mx]*/, float* tgt /*[Mx]*/, float* cnt /*[Mx]*/,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* Gradient of (w_row * sum_i (lse_x[i] - tgt_x[i]) + w_col * sum_j (lse_y[j] - tgt_y[j])) * inv_bg (* upstream) w.r.t.
+ * the rows of X, the column direction being the keys' own CE over the pair rows (its sets, counts and targets primed):
+ *   G[i,j] = w_row ([j in D_i] exp(S[i,j] - lse_x[i]) - T[i,j]) + w_col ([i in D'_j] exp(S[i,j] - lse_y[j]) - T'[j,i])
+ * same is symmetric, so i in D'_j iff j in D_i;  T'[j,i] uses c'_j = cnt_y[j] and N'_j from nkeys_y, the column
+ * direction's key count (Ny, plus the cache rows when the direction that owns them is the column one).  dX and
+ * dscale_partial follow from G as in clipk_simce_grad.  cnt_x / cnt_y: the cnt outputs of clipk_simce_lse_cls for
+ * each direction (cnt_x may be NULL when w_row == 0, cnt_y when w_col == 0). */
+int clipk_simce_grad_cls(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                         const float* scale, int label_offset, const float* lse_x, const float* lse_y,
+                         const float* cnt_x, const float* cnt_y, const int64_t* cls_x, const int64_t* cls_y,
+                         int same_class, float eps, int nkeys_y, float w_row, float w_col, float inv_bg,
+                         const float* upstream, float* dX /*[Mx,P]*/, float* dscale_partial /*[Mx]*/,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Batched form for several same-shape contrastive problems on one logit scale — the tri-modal ContrastiveModel of
  * current/tf_clip_codes (1).ipynb:13150-13163 (cell x pert, cell x protein, pert x protein, each symmetric) is six
  * directed problems (X = E[pairs[2i]], Y = E[pairs[2i+1]]), computed by ONE launch per pass (grid z = problem):
@@ -213,6 +252,13 @@ size_t clipk_sim_rank_workspace(int Mx, int Ny, int P);
 int clipk_sim_rank(const float* X, int Mx, const float* Y, int Ny, int P, float scale, const int64_t* labels,
                    int64_t label_offset, int64_t* rank /*[Mx]*/, float* pos /*[Mx]*/, void* workspace,
                    size_t workspace_bytes, void* stream);
+/* clipk_sim_rank_cls: the rank among the gallery rows of other classes, cls = device int64 [Ny] gallery class ids:
+ *   rank[i] = #{j : cls[j] != cls[l_i] and (S[i,j] > S[i,l_i] or (S[i,j] == S[i,l_i] and j < l_i))}
+ * so a duplicate partner of the positive is not a miss.  With all ids distinct it is clipk_sim_rank exactly.
+ * workspace: clipk_sim_rank_workspace(Mx, Ny, P) bytes. */
+int clipk_sim_rank_cls(const float* X, int Mx, const float* Y, int Ny, int P, float scale, const int64_t* labels,
+                       int64_t label_offset, const int64_t* cls, int64_t* rank /*[Mx]*/, float* pos /*[Mx]*/,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* Cross-entropy on MATERIALISED logits — the reference's loss call sites take the logits tensor its modules return:
  * F.cross_entropy(logits, arange(B)) at old/ablation.py:16 / run1/full.py:133, the symmetric pair at
