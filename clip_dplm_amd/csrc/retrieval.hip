@@ -433,3 +433,386 @@ extern "C" int clipk_sim_rank_cls(const float* X, int Mx, const float* Y, int Ny
                      labels, label_offset, Ny, rank);
   return clipk_check_launch();
 }
+
+// ================================================================================================================
+// Prefiltered exact top-k: a bf16 candidate pass, an exact re-rank of the candidates and a per-query certificate
+// (include/clipk.h: clipk_split_bf16, clipk_sim_topk_cand, clipk_sim_rerank; the bound is derived there).
+//
+// Candidate pass tile (sim_cand_kernel): 128 queries x 64 keys per workgroup, 4 waves; wave w owns queries
+// [32 w, +32) against all 64 keys, i.e. two 32x32 accumulators of v_mfma_f32_32x32x16_bf16 sharing one query fragment.
+// 128 queries per workgroup halve the gallery re-reads of the exact kernel's 64 (shape a: 64 instead of 128 passes
+// over the bf16 gallery, most of them L2 / MALL hits because the query blocks of one key split run side by side).
+// A lane keeps ONE list (its query), fed by 32 keys per tile in ascending index order (accumulator 0 then 1, rows
+// ascending), so the sorted-list epilogue and topk_merge_kernel are reused unchanged, with 2 lists per key split.
+// bf16 planes have a row pitch of P rounded up to 32 with zero pads (clipk_split_bf16 writes them): the K loop has no
+// tail and every staging load is 16 bytes.  X3 (bf16x3): three MFMAs per fragment pair into the same accumulator
+// (hi.hi, hi.lo, lo.hi).
+// Re-rank (sim_rerank_kernel): one workgroup per query; s_tile over a gathered tile whose 64 key rows are the query's
+// candidates and whose 64 query columns are all the query itself.  Each MFMA output element depends only on its row
+// and column operands and its accumulator, in the same K order as sim_topk_kernel, so the scores have its bits.
+// ================================================================================================================
+namespace {
+
+constexpr int CQ = 128, CK = 64;          // queries per workgroup, keys per tile of the candidate pass
+constexpr int CBK = 32, CLD = CBK + 8;    // K-step in bf16 elements (two MFMA k-steps), LDS row pitch (80 B)
+constexpr int PF_MAX_P = 65536;           // prefilter entries: the norm and bound arithmetic assumes P <= 2^16
+
+int plane_pitch(int P) { return (P + 31) & ~31; }
+
+// rows of X -> bf16 hi (and lo = bf16(x - hi)) planes with zero pads; the row norm, computed in f64 and rounded up to
+// f32, raises the running maximum *norm_max (non-negative floats order as their bit patterns); NaN / overflow -> +inf
+__global__ __launch_bounds__(256) void split_bf16_kernel(const float* X, int n, int P, int PP, unsigned short* hi,
+                                                         unsigned short* lo, float* norm_max) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + w;
+  if (row >= n) return;                                                   // per wave; no barriers below
+  const float* x = X + (long)row * P;
+  unsigned short* hr = hi + (long)row * PP;
+  unsigned short* lr = lo ? lo + (long)row * PP : nullptr;
+  double ss = 0.0;
+  for (int c = 4 * lane; c < PP; c += 256) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (c < P) v = *reinterpret_cast<const f32x4*>(x + c);
+    u32x2 hv;
+    hv[0] = pack_bf16x2(v[0], v[1]); hv[1] = pack_bf16x2(v[2], v[3]);
+    *reinterpret_cast<u32x2*>(hr + c) = hv;
+    if (lr) {                                                             // x - hi is exact in f32
+      u32x2 lv;
+      lv[0] = pack_bf16x2(v[0] - __uint_as_float(hv[0] << 16), v[1] - __uint_as_float(hv[0] & 0xffff0000u));
+      lv[1] = pack_bf16x2(v[2] - __uint_as_float(hv[1] << 16), v[3] - __uint_as_float(hv[1] & 0xffff0000u));
+      *reinterpret_cast<u32x2*>(lr + c) = lv;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ss += (double)v[e] * (double)v[e];       // exact squares, P <= 2^16 terms
+  }
+  if (!norm_max) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  if (lane == 0) {
+    const double nd = sqrt(ss) * (1.0 + 0x1p-30);                         // covers the f64 sum and sqrt roundings
+    float nf = INFINITY;
+    if (nd <= 3.0e38) {
+      nf = (float)nd;
+      if ((double)nf < nd) nf = __uint_as_float(__float_as_uint(nf) + 1u);   // round up
+    }
+    atomicMax(reinterpret_cast<unsigned int*>(norm_max), __float_as_uint(nf));
+  }
+}
+
+struct CKPm {
+  const unsigned short* xh; const unsigned short* xl; int Mx;
+  const unsigned short* yh; const unsigned short* yl; int Ny;
+  int PP; float scale;
+  float* part_s; int* part_i;            // [2 ksplit][Mx][KP]
+  int tiles_per_split, ntiles;
+};
+
+template <int KP, bool X3>
+__global__ __launch_bounds__(256, 2) void sim_cand_kernel(const CKPm p) {
+  constexpr int NPL = X3 ? 2 : 1, KT = CK * CLD, QT = CQ * CLD, BUF = NPL * (KT + QT);
+  __shared__ __attribute__((aligned(16))) unsigned short sm[2 * BUF];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int li = lane & 31, h = lane >> 5;
+  const int q0 = blockIdx.x * CQ, ks = blockIdx.y;
+  const int PP = p.PP, Ny = p.Ny;
+  const float scale = p.scale;
+  const int sr = tid >> 2, sc = (tid & 3) * 8;                            // staging: row sr (+64), 16-byte chunk sc
+  const unsigned short* xs[2][NPL];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    int q = q0 + sr + 64 * i; q = q < p.Mx ? q : p.Mx - 1;               // clamped: computed and dropped
+    xs[i][0] = p.xh + (long)q * PP + sc;
+    if constexpr (X3) xs[i][1] = p.xl + (long)q * PP + sc;
+  }
+  float s[KP];
+  int ix[KP];
+#pragma unroll
+  for (int t = 0; t < KP; ++t) { s[t] = -INFINITY; ix[t] = EMPTY; }
+  const int t_beg = ks * p.tiles_per_split;
+  int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
+  const int ns = PP / CBK;
+
+  for (int kt = t_beg; kt < t_end; ++kt) {
+    const int j0 = kt * CK;
+    int j = j0 + sr; j = j < Ny ? j : Ny - 1;
+    const unsigned short* ys[NPL];
+    ys[0] = p.yh + (long)j * PP + sc;
+    if constexpr (X3) ys[1] = p.yl + (long)j * PP + sc;
+    u32x4 ky[NPL], kq[2][NPL];
+    auto load = [&](int k0) {
+#pragma unroll
+      for (int pl = 0; pl < NPL; ++pl) {
+        ky[pl] = *reinterpret_cast<const u32x4*>(ys[pl] + k0);
+        kq[0][pl] = *reinterpret_cast<const u32x4*>(xs[0][pl] + k0);
+        kq[1][pl] = *reinterpret_cast<const u32x4*>(xs[1][pl] + k0);
+      }
+    };
+    auto store = [&](unsigned short* b) {
+#pragma unroll
+      for (int pl = 0; pl < NPL; ++pl) {
+        *reinterpret_cast<u32x4*>(b + pl * KT + sr * CLD + sc) = ky[pl];
+        *reinterpret_cast<u32x4*>(b + NPL * KT + pl * QT + sr * CLD + sc) = kq[0][pl];
+        *reinterpret_cast<u32x4*>(b + NPL * KT + pl * QT + (sr + 64) * CLD + sc) = kq[1][pl];
+      }
+    };
+    f32x16 acc[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
+    load(0);
+    __syncthreads();                                                      // whoever read these buffers last is done
+    store(sm);
+    __syncthreads();
+    for (int st = 0; st < ns; ++st) {
+      const unsigned short* b = sm + (st & 1) * BUF;
+      if (st + 1 < ns) load((st + 1) * CBK);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        bf16x8 a[2][NPL], bq[NPL];
+#pragma unroll
+        for (int pl = 0; pl < NPL; ++pl) {
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb)
+            a[kb][pl] = *reinterpret_cast<const bf16x8*>(b + pl * KT + (kb * 32 + li) * CLD + kk * 16 + 8 * h);
+          bq[pl] = *reinterpret_cast<const bf16x8*>(b + NPL * KT + pl * QT + (w * 32 + li) * CLD + kk * 16 + 8 * h);
+        }
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+          acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kb][0], bq[0], acc[kb], 0, 0, 0);
+          if constexpr (X3) {
+            acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kb][0], bq[1], acc[kb], 0, 0, 0);
+            acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kb][1], bq[0], acc[kb], 0, 0, 0);
+          }
+        }
+      }
+      if (st + 1 < ns) store(sm + ((st + 1) & 1) * BUF);
+      __syncthreads();
+    }
+    const int kb0 = j0 + 4 * h;                                           // key of acc[kb][r]: kb0 + 32 kb + key_off(r)
+    float tmax = -INFINITY;
+    if (j0 + CK <= Ny) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, fmaxf(scale * acc[0][r], scale * acc[1][r]));
+    } else {
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) if (kb0 + 32 * kb + key_off(r) < Ny) tmax = fmaxf(tmax, scale * acc[kb][r]);
+    }
+    if (tmax > s[KP - 1]) {                                               // rare once the list is full
+      unsigned m = 0;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (kb0 + 32 * kb + key_off(r) < Ny && scale * acc[kb][r] > s[KP - 1]) m |= 1u << (kb * 16 + r);
+      while (m) {                                                         // ascending bit = ascending key
+        const int bi = __builtin_ctz(m);
+        m &= m - 1;
+        float a = acc[0][0];
+#pragma unroll
+        for (int bb = 1; bb < 32; ++bb) a = (bi == bb) ? acc[bb >> 4][bb & 15] : a;
+        const float v = scale * a;
+        if (v > s[KP - 1]) list_insert<KP>(s, ix, v, kb0 + 32 * (bi >> 4) + key_off(bi & 15));
+      }
+    }
+  }
+
+  const int qg = q0 + w * 32 + li;
+  if (qg < p.Mx) {
+    const long o = ((long)(ks * 2 + h) * p.Mx + qg) * KP;
+#pragma unroll
+    for (int t = 0; t < KP; ++t) { p.part_s[o + t] = s[t]; p.part_i[o + t] = ix[t]; }
+  }
+}
+
+// the plan of plan(), for 128-query blocks
+void cplan(int Mx, int Ny, int* nqb, int* ksplit, int* tps, int* ntiles) {
+  *nqb = (Mx + CQ - 1) / CQ;
+  *ntiles = (Ny + CK - 1) / CK;
+  const int opt = clipk_opt_get(OPT_RETRIEVAL_SPLITS);
+  int ks = opt > 0 ? opt : (512 + *nqb - 1) / *nqb;
+  if (ks > 65535) ks = 65535;
+  if (ks > *ntiles) ks = *ntiles;
+  if (ks < 1) ks = 1;
+  *tps = (*ntiles + ks - 1) / ks;
+  *ksplit = (*ntiles + *tps - 1) / *tps;
+}
+
+int kcpad(int kc) { return kc <= 16 ? 16 : kc <= 32 ? 32 : 64; }
+
+size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+template <int KP>
+int cand_launch(CKPm p, int Mx, int Ny, int kc, bool x3, float* cs, int64_t* ci, char* lists, hipStream_t st) {
+  int nqb, ksplit;
+  cplan(Mx, Ny, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  const int la = 2 * ksplit, lb = (la + MG - 1) / MG;
+  const size_t per_list = (size_t)Mx * KP;
+  float* a_s = reinterpret_cast<float*>(lists);
+  int* a_i = reinterpret_cast<int*>(a_s + la * per_list);
+  float* b_s = reinterpret_cast<float*>(a_i + la * per_list);
+  int* b_i = reinterpret_cast<int*>(b_s + lb * per_list);
+  p.part_s = a_s; p.part_i = a_i;
+  if (x3) hipLaunchKernelGGL((sim_cand_kernel<KP, true>), dim3(nqb, ksplit), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((sim_cand_kernel<KP, false>), dim3(nqb, ksplit), dim3(256), 0, st, p);
+  int rc = clipk_check_launch();
+  if (rc) return rc;
+  const float* src_s = a_s; const int* src_i = a_i;
+  float* dst_s = b_s; int* dst_i = b_i;
+  for (int L = la;;) {
+    const int groups = (L + MG - 1) / MG;
+    if (groups == 1) {
+      hipLaunchKernelGGL(topk_merge_kernel<KP>, dim3(Mx, 1), dim3(256), 0, st, src_s, src_i, L, Mx,
+                         (float*)nullptr, (int*)nullptr, cs, ci, kc, Ny);
+      return clipk_check_launch();
+    }
+    hipLaunchKernelGGL(topk_merge_kernel<KP>, dim3(Mx, groups), dim3(256), 0, st, src_s, src_i, L, Mx, dst_s, dst_i,
+                       (float*)nullptr, (int64_t*)nullptr, kc, Ny);
+    if ((rc = clipk_check_launch())) return rc;
+    L = groups;
+    float* ts = const_cast<float*>(src_s); int* ti = const_cast<int*>(src_i);
+    src_s = dst_s; src_i = dst_i; dst_s = ts; dst_i = ti;
+  }
+}
+
+struct RRP {
+  const float* X; int Mx;
+  const float* Y; int Ny;
+  int P; float scale;
+  const int64_t* cidx; const float* cs; int kc, k;
+  double eps_rel; const float* ynorm;
+  float* scores; int64_t* idx; int* cert;
+};
+
+__global__ __launch_bounds__(256) void sim_rerank_kernel(const RRP p) {
+  __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (RBK + 4)];
+  __shared__ float ex[64];
+  __shared__ int ej[64], er[64];
+  __shared__ double red[4];
+  __shared__ float tks;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid >> 1, wn = wid & 1;
+  const int li = lane & 31, h = lane >> 5;
+  const int q = blockIdx.x, P = p.P, Ny = p.Ny, kc = p.kc, k = p.k;
+  const float* xq = p.X + (long)q * P;
+  const float* xrows[RBK / 16];
+  const float* yrows[RBK / 16];
+#pragma unroll
+  for (int i = 0; i < RBK / 16; ++i) {
+    const int c = (tid + i * 256) / (RBK / 4);                            // key row c of the tile: candidate c
+    int64_t j = c < kc ? p.cidx[(long)q * kc + c] : 0;
+    j = (j >= 0 && j < Ny) ? j : 0;
+    yrows[i] = p.Y + j * P;
+    xrows[i] = xq;
+  }
+  if (tid < 64) {
+    const int64_t j = tid < kc ? p.cidx[(long)q * kc + tid] : -1;
+    const float a = tid < kc ? p.cs[(long)q * kc + tid] : -INFINITY;
+    er[tid] = (a > -INFINITY && j >= 0 && j < Ny);                        // the fillers of a short list carry -inf
+    ej[tid] = er[tid] ? (int)j : INT_MAX;
+  }
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  s_tile<RBK>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
+  if (wn == 0 && li == 0) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ex[wm * 32 + keyrow32(r, h)] = p.scale * acc[r];
+  }
+  double ss = 0.0;
+  for (int c = tid; c < P; c += 256) ss += (double)xq[c] * (double)xq[c];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  if (lane == 0) red[wid] = ss;
+  if (tid == 0) tks = -INFINITY;
+  __syncthreads();
+  if (tid < kc && er[tid]) {
+    const float v = ex[tid];
+    const int j = ej[tid];
+    int rank = 0;
+    for (int u = 0; u < kc; ++u) rank += er[u] && (ex[u] > v || (ex[u] == v && ej[u] < j));
+    if (rank < k) { p.scores[(long)q * k + rank] = v; p.idx[(long)q * k + rank] = j; }
+    if (rank == k - 1) tks = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int nreal = 0;
+    bool nan = false;
+    for (int u = 0; u < kc; ++u) { nreal += er[u]; nan |= er[u] && ex[u] != ex[u]; }
+    for (int t = nreal; t < k; ++t) { p.scores[(long)q * k + t] = -INFINITY; p.idx[(long)q * k + t] = 0; }
+    const double tk = (double)tks;
+    bool ok = !nan && nreal >= k && tk > -INFINITY;
+    if (ok && nreal < Ny) {                                               // nreal == Ny: every key is a candidate
+      const double xn = sqrt(red[0] + red[1] + red[2] + red[3]) * (1.0 + 0x1p-30);
+      const double yn = (double)p.ynorm[0], sc = fabs((double)p.scale), mag = xn * yn;
+      const double c = (double)p.cs[(long)q * kc + kc - 1];              // the weakest approximate candidate
+      const double eps = (sc * mag * p.eps_rel + (sc * P * (xn + yn + 1.0) + 1.0) * 0x1p-120) * (1.0 + 0x1p-30);
+      ok = nreal == kc && mag * (sc > 1.0 ? sc : 1.0) < 0x1p126 && tk > c + eps;
+    }
+    p.cert[q] = ok ? 1 : 0;
+  }
+}
+
+}  // namespace
+
+extern "C" int clipk_split_bf16(const float* X, int n_rows, int P, void* hi, void* lo, float* norm_max, void* stream) {
+  if (!X || !hi || n_rows <= 0 || P <= 0) return CLIPK_ERR_BAD_ARG;
+  if (P % 4 || P > PF_MAX_P) return CLIPK_ERR_UNSUPPORTED;
+  if (!aligned16(X) || !aligned16(hi) || (lo && !aligned16(lo))) return CLIPK_ERR_BAD_ARG;
+  hipLaunchKernelGGL(split_bf16_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, X, n_rows, P,
+                     plane_pitch(P), static_cast<unsigned short*>(hi), static_cast<unsigned short*>(lo), norm_max);
+  return clipk_check_launch();
+}
+
+extern "C" size_t clipk_sim_topk_cand_workspace(int Mx, int Ny, int P, int kc, int planes) {
+  if (!shape_ok(Mx, Ny, P) || P % 4 || P > PF_MAX_P || kc < 1 || kc > 64 || (planes != 1 && planes != 2)) return 0;
+  int nqb, ksplit, tps, nt;
+  cplan(Mx, Ny, &nqb, &ksplit, &tps, &nt);
+  const size_t la = 2 * (size_t)ksplit, lb = (la + MG - 1) / MG;
+  return round256((size_t)planes * Mx * plane_pitch(P) * 2) +
+         (la + lb) * (size_t)Mx * kcpad(kc) * (sizeof(float) + sizeof(int));
+}
+
+extern "C" int clipk_sim_topk_cand(const float* X, int Mx, const void* Yhi, const void* Ylo, int Ny, int P, float scale,
+                                   int kc, float* cand_scores, int64_t* cand_idx, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  if (!X || !Yhi || !cand_scores || !cand_idx || !workspace) return CLIPK_ERR_BAD_ARG;
+  if (Mx <= 0 || Ny <= 0 || P <= 0 || kc < 1 || kc > 64) return CLIPK_ERR_BAD_ARG;
+  if (P % 4 || P > PF_MAX_P || !shape_ok(Mx, Ny, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (!aligned16(X) || !aligned16(Yhi) || (Ylo && !aligned16(Ylo)) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
+  const int planes = Ylo ? 2 : 1;
+  if (workspace_bytes < clipk_sim_topk_cand_workspace(Mx, Ny, P, kc, planes)) return CLIPK_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int PP = plane_pitch(P);
+  unsigned short* xh = static_cast<unsigned short*>(workspace);          // the queries' planes, split once per call
+  unsigned short* xl = Ylo ? xh + (size_t)Mx * PP : nullptr;
+  char* lists = static_cast<char*>(workspace) + round256((size_t)planes * Mx * PP * 2);
+  hipLaunchKernelGGL(split_bf16_kernel, dim3((Mx + 3) / 4), dim3(256), 0, st, X, Mx, P, PP, xh, xl, (float*)nullptr);
+  int rc = clipk_check_launch();
+  if (rc) return rc;
+  CKPm p{};
+  p.xh = xh; p.xl = xl; p.Mx = Mx;
+  p.yh = static_cast<const unsigned short*>(Yhi); p.yl = static_cast<const unsigned short*>(Ylo); p.Ny = Ny;
+  p.PP = PP; p.scale = scale;
+  switch (kcpad(kc)) {
+    case 16: return cand_launch<16>(p, Mx, Ny, kc, Ylo != nullptr, cand_scores, cand_idx, lists, st);
+    case 32: return cand_launch<32>(p, Mx, Ny, kc, Ylo != nullptr, cand_scores, cand_idx, lists, st);
+    default: return cand_launch<64>(p, Mx, Ny, kc, Ylo != nullptr, cand_scores, cand_idx, lists, st);
+  }
+}
+
+extern "C" int clipk_sim_rerank(const float* X, int Mx, const float* Y, int Ny, int P, float scale,
+                                const int64_t* cand_idx, const float* cand_scores, int kc, int k, double eps_rel,
+                                const float* y_norm_max, float* scores, int64_t* idx, int* certified, void* stream) {
+  if (!X || !Y || !cand_idx || !cand_scores || !y_norm_max || !scores || !idx || !certified) return CLIPK_ERR_BAD_ARG;
+  if (Mx <= 0 || Ny <= 0 || P <= 0 || k < 1 || k > kc || kc > 64 || k > Ny) return CLIPK_ERR_BAD_ARG;
+  if (!(eps_rel >= 0.0 && eps_rel < 1.0)) return CLIPK_ERR_BAD_ARG;
+  if (P % 4 || P > PF_MAX_P || !shape_ok(Mx, Ny, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (!aligned16(X) || !aligned16(Y)) return CLIPK_ERR_BAD_ARG;
+  RRP p;
+  p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale;
+  p.cidx = cand_idx; p.cs = cand_scores; p.kc = kc; p.k = k; p.eps_rel = eps_rel; p.ynorm = y_norm_max;
+  p.scores = scores; p.idx = idx; p.cert = certified;
+  hipLaunchKernelGGL(sim_rerank_kernel, dim3(Mx), dim3(256), 0, (hipStream_t)stream, p);
+  return clipk_check_launch();
+}

@@ -472,6 +472,81 @@ def sim_topk(x, y, k: int, scale: Optional[float] = None):
     return scores, idx
 
 
+def plane_pitch(P: int) -> int:
+    """Row pitch (bf16 elements) of the planes clipk_split_bf16 writes: P rounded up to 32, pads zero."""
+    return (int(P) + 31) // 32 * 32
+
+
+def split_bf16(x, hi, lo=None, norm_max=None):
+    """Rows of f32 x [n, P] -> bf16 plane hi (and lo = bf16(x - hi)), both [n, plane_pitch(P)] (any 2-byte dtype);
+    norm_max (device f32 [1]) is raised to the largest row norm, rounded upward (include/clipk.h: clipk_split_bf16)."""
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
+        raise TypeError("split_bf16 needs a contiguous 2-D float32 tensor")
+    n, P = x.shape
+    for t in (hi, lo):
+        if t is not None and (t.element_size() != 2 or tuple(t.shape) != (n, plane_pitch(P)) or not t.is_contiguous()):
+            raise ValueError(f"planes must be contiguous 2-byte tensors of shape ({n}, {plane_pitch(P)})")
+    if norm_max is not None and (norm_max.dtype != torch.float32 or norm_max.numel() != 1):
+        raise ValueError("norm_max must be a float32 tensor of one element")
+    _need_cuda(x, hi, lo, norm_max)
+    if n == 0:
+        return
+    check(_lib().clipk_split_bf16(x.data_ptr(), n, P, hi.data_ptr(), ptr(lo), ptr(norm_max), _stream()),
+          "clipk_split_bf16")
+
+
+def sim_topk_cand(x, yhi, ylo, Ny: int, P: int, kc: int, scale: Optional[float] = None):
+    """(scores f32 [Mx, kc], idx int64 [Mx, kc]): the kc best keys of the bf16 (ylo None) or bf16x3 similarity
+    scale * x y^T from the gallery's planes, in the order of sim_topk (include/clipk.h: clipk_sim_topk_cand)."""
+    if x.dtype != torch.float32:
+        raise TypeError(f"queries must be float32, got {x.dtype}")
+    if x.dim() != 2 or not x.is_contiguous() or x.shape[1] != P or x.data_ptr() % 16:
+        raise ValueError("queries must be a contiguous, 16-byte aligned [Mx, P] tensor")
+    for t in (yhi, ylo):
+        if t is not None and (t.element_size() != 2 or t.dim() != 2 or t.shape[0] < Ny or t.shape[1] != plane_pitch(P)
+                              or not t.is_contiguous() or t.data_ptr() % 16):
+            raise ValueError(f"gallery planes must be contiguous, aligned [>= {Ny}, {plane_pitch(P)}] 2-byte tensors")
+    kc = int(kc)
+    if not 1 <= kc <= 64:
+        raise ValueError(f"candidates must be in [1, 64], got {kc}")
+    Mx = x.shape[0]
+    if Mx == 0 or Ny <= 0 or P <= 0 or P % 4:
+        raise ValueError(f"need non-empty inputs and P % 4 == 0 (Mx={Mx}, Ny={Ny}, P={P})")
+    _need_cuda(x, yhi, ylo)
+    scores = torch.empty((Mx, kc), dtype=torch.float32, device=x.device)
+    idx = torch.empty((Mx, kc), dtype=torch.int64, device=x.device)
+    lib = _lib()
+    ws = workspace(lib.clipk_sim_topk_cand_workspace(Mx, Ny, P, kc, 1 if ylo is None else 2), x.device, "retrieval")
+    check(lib.clipk_sim_topk_cand(x.data_ptr(), Mx, yhi.data_ptr(), ptr(ylo), Ny, P, 1.0 if scale is None else float(scale),
+                                  kc, scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "clipk_sim_topk_cand")
+    return scores, idx
+
+
+def sim_rerank(x, y, cand_scores, cand_idx, k: int, eps_rel: float, y_norm_max, scale: Optional[float] = None):
+    """(scores f32 [Mx, k], idx int64 [Mx, k], certified int32 [Mx]): the exact top k among each row's candidates, with the
+    bits of sim_topk, and whether the bound proves them the top k of the whole gallery (include/clipk.h:
+    clipk_sim_rerank).  Rows with certified == 0 hold unspecified results."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    kc, k = cand_idx.shape[1], int(k)
+    if cand_idx.dtype != torch.int64 or cand_scores.dtype != torch.float32 or cand_idx.shape != (Mx, kc) \
+            or cand_scores.shape != (Mx, kc) or not cand_idx.is_contiguous() or not cand_scores.is_contiguous():
+        raise ValueError("candidates must be contiguous [Mx, kc] float32 scores and int64 indices")
+    if not 1 <= k <= kc <= 64 or k > Ny:
+        raise ValueError(f"need 1 <= k <= candidates <= 64 and k <= Ny (k={k}, candidates={kc}, Ny={Ny})")
+    if y_norm_max.dtype != torch.float32 or y_norm_max.numel() != 1:
+        raise ValueError("y_norm_max must be a float32 tensor of one element")
+    _need_cuda(x, y, cand_scores, cand_idx, y_norm_max)
+    scores = torch.empty((Mx, k), dtype=torch.float32, device=x.device)
+    idx = torch.empty((Mx, k), dtype=torch.int64, device=x.device)
+    cert = torch.empty(Mx, dtype=torch.int32, device=x.device)
+    check(_lib().clipk_sim_rerank(x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale),
+                                  cand_idx.data_ptr(), cand_scores.data_ptr(), kc, k, float(eps_rel),
+                                  y_norm_max.data_ptr(), scores.data_ptr(), idx.data_ptr(), cert.data_ptr(), _stream()),
+          "clipk_sim_rerank")
+    return scores, idx, cert
+
+
 def sim_rank(x, y, labels=None, label_offset: int = 0, scale: Optional[float] = None, class_ids=None):
     """(rank int64 [Mx], pos f32 [Mx]): 0-based rank of key l_i in row i of S = scale * x y^T under the same order as
     sim_topk, and S[i, l_i] (include/clipk.h: clipk_sim_rank).  l_i = labels[i] (device int64 [Mx]) or label_offset + i.

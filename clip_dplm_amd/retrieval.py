@@ -11,6 +11,10 @@ rank 0 is exactly the reference's "correct" and results do not depend on how the
 Class ids (`class_ids=`): where several pairs share a partner (one RBP bound by many RNAs), their gallery rows are
 identical and tie-breaking by index caps recall@1 below 1 even for a perfect model.  With ids the rank counts only gallery
 rows of another class than the positive (include/clipk.h: clipk_sim_rank_cls); with all ids distinct it is the plain rank.
+
+Prefilter (`prefilter="bf16"` / `"bf16x3"` in `topk` and `EmbeddingIndex`): the same results, bit for bit, from a bf16
+matrix-core candidate pass, an exact re-rank of `candidates` keys per query and a per-query certificate; queries the bound
+cannot certify run the exact kernel (include/clipk.h: clipk_sim_topk_cand, clipk_sim_rerank).
 """
 from __future__ import annotations
 
@@ -33,9 +37,91 @@ def _as_f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
-def topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, scale: Optional[float] = None):
-    """(scores f32 [Mq, k], idx int64 [Mq, k]): the k gallery rows most similar to each query (1 <= k <= 64)."""
-    return ops.sim_topk(_as_f32(queries, "queries"), _as_f32(gallery, "gallery"), k, scale)
+PREFILTERS = (None, "bf16", "bf16x3")
+
+
+def prefilter_eps_rel(P: int, mode: str) -> float:
+    """eps_rel of the certificate (include/clipk.h, "Certificate"): a bound of |approximate - exact score| relative to
+    |scale| |x| max|y|, for rows of P columns.  Operand rounding + bf16 MFMA accumulation (gamma = n 2^-22 over n
+    products) + the exact f32 kernel's own error (P 2^-23) + the two multiplications by scale (2^-22)."""
+    v = 2.0 ** -8                                    # bf16 keeps 8 significant bits: unit roundoff 2^-8
+    if mode == "bf16":
+        operands, acc = 2 * v + v * v, P * 2.0 ** -22 * (1 + v) ** 2
+    elif mode == "bf16x3":
+        operands, acc = 3 * v * v + 7 * v ** 3, 3 * P * 2.0 ** -22 * (1 + v) ** 2 * (1 + 2 * v)
+    else:
+        raise ValueError(f"prefilter must be one of {PREFILTERS}, got {mode!r}")
+    return operands + acc + P * 2.0 ** -23 + 2.0 ** -22
+
+
+def _prefilter_args(k, prefilter, candidates):
+    """(k, kc): validated before any device work."""
+    if prefilter not in PREFILTERS:
+        raise ValueError(f"prefilter must be one of {PREFILTERS}, got {prefilter!r}")
+    k = int(k)
+    if prefilter is None:
+        if candidates is not None:
+            raise ValueError("candidates= needs a prefilter")
+        return k, None
+    if not 1 <= k <= 63:
+        raise ValueError(f"k must be in [1, 63] with a prefilter, got {k}")
+    if candidates is None:            # bf16's bound (~2^-7 relative) is wider than typical top-k / top-2k score gaps
+        kc = 64 if prefilter == "bf16" else min(64, max(16, 2 * k))
+    else:
+        kc = int(candidates)
+    if not k < kc <= 64:
+        raise ValueError(f"candidates must satisfy k < candidates <= 64, got k = {k}, candidates = {kc}")
+    return k, kc
+
+
+def _new_planes(n: int, dim: int, mode: str, device):
+    pp = ops.plane_pitch(dim)
+    hi = torch.empty((n, pp), dtype=torch.bfloat16, device=device)
+    lo = torch.empty((n, pp), dtype=torch.bfloat16, device=device) if mode == "bf16x3" else None
+    return hi, lo
+
+
+def _prefiltered_topk(q, g, hi, lo, norm_max, k, kc, scale, mode):
+    """The four steps of include/clipk.h "Prefiltered exact top-k" on f32 q, g and g's planes."""
+    Mq, P = q.shape
+    Ny = g.shape[0]
+    cs, ci = ops.sim_topk_cand(q, hi, lo, Ny, P, kc, scale)
+    s, i, cert = ops.sim_rerank(q, g, cs, ci, k, prefilter_eps_rel(P, mode), norm_max, scale)
+    bad = torch.nonzero(cert == 0).flatten()          # the one device -> host read of the call (not capturable)
+    if bad.numel():                                   # the exact kernel on the uncertified rows; per-row results
+        s2, i2 = ops.sim_topk(q.index_select(0, bad), g, k, scale)
+        s.index_copy_(0, bad, s2)
+        i.index_copy_(0, bad, i2)
+    return s, i, {"queries": Mq, "certified": Mq - int(bad.numel()), "candidates": kc, "prefilter": mode}
+
+
+def _exact_stats(Mq):
+    return {"queries": Mq, "certified": None, "candidates": None, "prefilter": None}
+
+
+def topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, scale: Optional[float] = None,
+         prefilter: Optional[str] = None, candidates: Optional[int] = None, return_stats: bool = False):
+    """(scores f32 [Mq, k], idx int64 [Mq, k]): the k gallery rows most similar to each query (1 <= k <= 64).
+
+    prefilter "bf16" / "bf16x3" (k <= 63): the same tensors, bit for bit, with most of the work on the bf16 matrix
+    pipe; `candidates` (k < candidates <= 64; default 64 for bf16, min(64, max(16, 2 k)) for bf16x3) keys per query are
+    re-scored exactly.
+    The gallery's bf16 planes are built on every call (an EmbeddingIndex keeps them); the call reads one count back
+    to the host.  return_stats: a third result {"queries", "certified", "candidates", "prefilter"}."""
+    k, kc = _prefilter_args(k, prefilter, candidates)
+    q, g = _as_f32(queries, "queries"), _as_f32(gallery, "gallery")
+    if prefilter is None:
+        s, i = ops.sim_topk(q, g, k, scale)
+        return (s, i, _exact_stats(q.shape[0])) if return_stats else (s, i)
+    Mq, Ny, P = ops._retrieval_args(q, g)
+    if k > Ny:
+        raise ValueError(f"k = {k} exceeds the gallery size {Ny}")
+    ops._need_cuda(q, g)
+    hi, lo = _new_planes(Ny, P, prefilter, g.device)
+    norm_max = torch.zeros(1, dtype=torch.float32, device=g.device)
+    ops.split_bf16(g, hi, lo, norm_max)
+    s, i, stats = _prefiltered_topk(q, g, hi, lo, norm_max, k, kc, scale, prefilter)
+    return (s, i, stats) if return_stats else (s, i)
 
 
 def _as_ids(t: torch.Tensor, n: int, device, name: str) -> torch.Tensor:
@@ -151,15 +237,29 @@ def evaluate_retrieval(model, loader: Iterable, ks: Sequence[int] = (1, 5, 10),
 
 class EmbeddingIndex:
     """An exact gallery for repeated top-k search: add() appends embeddings to a device buffer the index owns (grown
-    geometrically), search() is one topk over everything added so far."""
+    geometrically), search() is one topk over everything added so far.
 
-    def __init__(self, dim: int, device=None):
+    prefilter "bf16" / "bf16x3": add() also keeps the gallery's bf16 plane(s) and the running maximum row norm, and
+    search() runs the prefiltered top-k on them (same results as without).  Memory: the f32 rows stay (the re-rank and
+    the fallback read them); the planes add half of them (bf16: 1.5x in all) or as much again (bf16x3: 2x), with rows
+    padded to a multiple of 32 columns.  state_dict() holds the f32 rows only; load_state_dict() rebuilds the planes."""
+
+    def __init__(self, dim: int, device=None, prefilter: Optional[str] = None):
         if dim <= 0 or dim % 4:
             raise ValueError(f"dim must be a positive multiple of 4, got {dim}")
+        if prefilter not in PREFILTERS:
+            raise ValueError(f"prefilter must be one of {PREFILTERS}, got {prefilter!r}")
         self.dim = int(dim)
+        self.prefilter = prefilter
         self.device = torch.device(device if device is not None else "cuda")
+        self._reset()
+
+    def _reset(self) -> None:
         self._buf = torch.empty((0, self.dim), dtype=torch.float32, device=self.device)
         self._n = 0
+        if self.prefilter is not None:
+            self._hi, self._lo = _new_planes(0, self.dim, self.prefilter, self.device)
+            self._norm = torch.zeros(1, dtype=torch.float32, device=self.device)
 
     def __len__(self) -> int:
         return self._n
@@ -174,17 +274,38 @@ class EmbeddingIndex:
             buf = torch.empty((cap, self.dim), dtype=torch.float32, device=self.device)
             buf[:self._n].copy_(self._buf[:self._n])
             self._buf = buf
+            if self.prefilter is not None:
+                hi, lo = _new_planes(cap, self.dim, self.prefilter, self.device)
+                hi[:self._n].copy_(self._hi[:self._n])
+                if lo is not None:
+                    lo[:self._n].copy_(self._lo[:self._n])
+                self._hi, self._lo = hi, lo
         self._buf[self._n:self._n + n].copy_(e)
+        if self.prefilter is not None and n:
+            rows = slice(self._n, self._n + n)
+            ops.split_bf16(self._buf[rows], self._hi[rows], None if self._lo is None else self._lo[rows], self._norm)
         self._n += n
 
     def embeddings(self) -> torch.Tensor:
         return self._buf[:self._n]
 
-    def search(self, queries: torch.Tensor, k: int, scale: Optional[float] = None):
-        """(scores, idx) of the k best gallery rows per query, as topk(queries, all added rows, k)."""
+    def search(self, queries: torch.Tensor, k: int, scale: Optional[float] = None, candidates: Optional[int] = None,
+               return_stats: bool = False):
+        """(scores, idx) of the k best gallery rows per query, as topk(queries, all added rows, k); with the index's
+        prefilter, from its planes (candidates / return_stats as in topk)."""
+        k, kc = _prefilter_args(k, self.prefilter, candidates)
         if self._n == 0:
             raise _ffi.ClipkError("search on an empty EmbeddingIndex")
-        return topk(queries.to(self.device), self.embeddings(), k, scale)
+        if self.prefilter is None:
+            s, i = topk(queries.to(self.device), self.embeddings(), k, scale)
+            return (s, i, _exact_stats(s.shape[0])) if return_stats else (s, i)
+        q, g = _as_f32(queries.to(self.device), "queries"), self.embeddings()
+        _, Ny, _ = ops._retrieval_args(q, g)
+        if k > Ny:
+            raise ValueError(f"k = {k} exceeds the gallery size {Ny}")
+        lo = None if self._lo is None else self._lo[:self._n]
+        s, i, stats = _prefiltered_topk(q, g, self._hi[:self._n], lo, self._norm, k, kc, scale, self.prefilter)
+        return (s, i, stats) if return_stats else (s, i)
 
     def state_dict(self) -> dict:
         return {"dim": self.dim, "embeds": self.embeddings().clone()}
@@ -193,7 +314,6 @@ class EmbeddingIndex:
         e = state["embeds"]
         if int(state["dim"]) != self.dim or e.dim() != 2 or e.shape[1] != self.dim:
             raise ValueError(f"state of a {state['dim']}-wide index loaded into a {self.dim}-wide one")
-        self._buf = torch.empty((0, self.dim), dtype=torch.float32, device=self.device)
-        self._n = 0
+        self._reset()
         if e.shape[0]:
             self.add(e)

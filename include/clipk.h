@@ -260,6 +260,60 @@ int clipk_sim_rank_cls(const float* X, int Mx, const float* Y, int Ny, int P, fl
                        int64_t label_offset, const int64_t* cls, int64_t* rank /*[Mx]*/, float* pos /*[Mx]*/,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Prefiltered exact top-k: the results of clipk_sim_topk, bit for bit, with the bulk of the similarity work on the bf16
+ * matrix pipe (v_mfma_f32_32x32x16_bf16) instead of the exact-f32 one.  Replaces the same reference sites as
+ * clipk_sim_topk (the similarity matrix of run1/full.py:157 and the argmax of run1/full.py:138,152).
+ *   1. clipk_split_bf16 once per gallery (incrementally as rows are added): bf16 plane(s) and max_j |Y_j|.
+ *   2. clipk_sim_topk_cand: the approximate top-kc of every query, A[i,j] = scale * <X_i, Y_j>_bf16.
+ *   3. clipk_sim_rerank: the exact scores of those kc keys (the bits clipk_sim_topk computes), their top k, and a
+ *      certificate per query; 4. the caller runs clipk_sim_topk on the uncertified rows and scatters them back.
+ * Modes: one plane (bf16: A = sum hi(x) hi(y)) or two (bf16x3: x = hi + lo + r, lo = bf16(x - hi),
+ * A = sum hi.hi + hi.lo + lo.hi).  Planes: row pitch PP = P rounded up to a multiple of 32 bf16 elements, pads zero.
+ * Requirements (all three): P % 4 == 0, P <= 65536 (else CLIPK_ERR_UNSUPPORTED), 16-byte aligned pointers.
+ *
+ * Certificate.  With c the kc-th (weakest) approximate candidate score and t_k the k-th exact score among the
+ * candidates, query i is certified when t_k > c + eps_i, where eps_i bounds |A[i,j] - S[i,j]| for every key j:
+ *   eps_i = |scale| |X_i| max_j|Y_j| eps_rel + eps_abs.
+ * Every non-candidate j has A[i,j] <= c, so S[i,j] <= c + eps_i < t_k: it is below k candidates and cannot enter the
+ * top k; the order among candidates is the exact one.  A query whose list holds every key (Ny <= kc) is certified
+ * trivially.  The comparison is made in f64 with eps_i enlarged by (1 + 2^-30), which covers the roundings of its own
+ * evaluation; |X_i| is summed in f64 and |Y|max is rounded upward to f32.  Non-finite results, NaN scores, norms with
+ * |scale| |X_i| |Y|max >= 2^126 (where f32 partial sums could overflow) and short lists are never certified.
+ * eps_rel (u = 2^-24, v = 2^-8 the unit roundoffs of f32 and bf16 - bf16 keeps 8 significant bits, so a single rounding
+ * moves a value by up to 2^-8 of it, not 2^-9; every term bounds an error relative to sum_p |x_p y_p| <= |x| |y|):
+ *   operands, bf16:   |hi(x) hi(y) - x y| <= (2v + v^2) |x y|
+ *   operands, bf16x3: |hi lo| <= v(1 + v)|x|, |r| <= v^2 |x|; the dropped lo.lo + hi.r + r.hi + lo.r + r.lo + r.r
+ *                     sum to <= (3 v^2 + 6 v^3 + 4 v^4) |x y| <= (3 v^2 + 7 v^3) |x y|
+ *   bf16 MFMA accumulation: its order and rounding are not documented.  The products of bf16 operands are exact in
+ *                     f32; n = P (bf16) or 3P (bf16x3) of them are summed.  Taken as gamma = n 2^-22 (four times the
+ *                     n u of f32 round-to-nearest in any order) times their magnitude, (1 + v)^2 (bf16) or
+ *                     (1 + v)^2 (1 + 2v) (bf16x3) times sum |x y|.  The GPU tests measure |A - S| <= eps_i / 2.
+ *   the exact f32 kernel: a chain of P fused multiply-adds, <= P u / (1 - P u) <= P 2^-23
+ *   the two multiplications by scale: <= 2^-22
+ * eps_abs = (|scale| P (|X_i| + |Y|max + 1) + 1) 2^-120 covers subnormals: the conversion and the MFMA may flush
+ * subnormal operands (the lo plane produces them) and results to zero, each such flush moving a product or a partial sum
+ * by less than 2^-126 (|Y| + 1) per term.  retrieval.prefilter_eps_rel(P, mode) evaluates eps_rel.
+ *
+ * clipk_split_bf16: hi[n_rows, PP] = bf16(X) (round to nearest even), lo (NULL: one plane) = bf16(X - hi), pads zero;
+ * norm_max (device f32 [1], NULL: not tracked) = max(*norm_max, |X_r| rounded upward), +inf for NaN or huge rows. */
+int clipk_split_bf16(const float* X, int n_rows, int P, void* hi, void* lo, float* norm_max, void* stream);
+/* clipk_sim_topk_cand: cand_scores / cand_idx [Mx, kc] = the kc best (A[i,j], j) of row i in the clipk_sim_topk order
+ * applied to A; 1 <= kc <= 64.  Yhi / Ylo: the gallery's planes (Ylo NULL: bf16 mode).  When Ny < kc the list ends in
+ * fillers with score -inf.  The queries are split into the workspace: clipk_sim_topk_cand_workspace(Mx, Ny, P, kc,
+ * planes) bytes, planes = 1 or 2. */
+size_t clipk_sim_topk_cand_workspace(int Mx, int Ny, int P, int kc, int planes);
+int clipk_sim_topk_cand(const float* X, int Mx, const void* Yhi, const void* Ylo, int Ny, int P, float scale, int kc,
+                        float* cand_scores /*[Mx,kc]*/, int64_t* cand_idx /*[Mx,kc]*/, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* clipk_sim_rerank: scores / idx [Mx, k] = the k best candidates of row i by their exact scores S[i,j] (the bits of
+ * clipk_sim_topk), in its order; certified[i] (int32) = 1 when those are the top k of the whole gallery by the bound
+ * above, else 0 (then scores / idx of that row are unspecified).  1 <= k <= kc <= 64, k <= Ny; eps_rel in [0, 1);
+ * y_norm_max: device f32 [1], an upper bound of every |Y_j| (clipk_split_bf16's).  No workspace. */
+int clipk_sim_rerank(const float* X, int Mx, const float* Y, int Ny, int P, float scale, const int64_t* cand_idx,
+                     const float* cand_scores, int kc, int k, double eps_rel, const float* y_norm_max,
+                     float* scores /*[Mx,k]*/, int64_t* idx /*[Mx,k]*/, int* certified /*[Mx]*/, void* stream);
+
 /* Cross-entropy on MATERIALISED logits — the reference's loss call sites take the logits tensor its modules return:
  * F.cross_entropy(logits, arange(B)) at old/ablation.py:16 / run1/full.py:133, the symmetric pair at
  * current/rna_clip_codes.ipynb:1952-1953, and (F.cross_entropy(cat([S, S_cache], 1)) + F.cross_entropy(S^T)) / 2

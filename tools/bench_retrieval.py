@@ -1,6 +1,7 @@
 """Fused retrieval kernels (clipk_sim_topk / clipk_sim_rank) against the materialising baseline, one JSON line per shape.
 
   python3 tools/bench_retrieval.py [--shapes a,b,c,d] [--iters 5] [--warmup 2] [--out profiles/retrieval/bench.jsonl]
+                                   [--prefilter none,bf16,bf16x3] [--candidates KC]
 
 Shapes:  a  Mx = 8192, Ny = 2^20, P = 512, k = 10
          b  Mx = 64,   Ny = 2^22, P = 512, k = 10
@@ -8,7 +9,10 @@ Shapes:  a  Mx = 8192, Ny = 2^20, P = 512, k = 10
          d  a with k = 64 and an ascending gallery: every score beats the current k-th and inserts
 Baseline (same process): ops.sim_logits over gallery chunks, torch.topk per chunk, torch.topk over the chunk winners.
 Time: device events around the call after warm-up, the median of --iters.  FLOPs = 2 Mx Ny P against the 157.3 TFLOP/s
-f32 matrix peak; gallery bytes against 8 TB/s; the larger of the two floors names the bound."""
+f32 matrix peak; gallery bytes against 8 TB/s; the larger of the two floors names the bound.
+--prefilter bf16 / bf16x3 (one line per shape and mode): searches on a prefiltered EmbeddingIndex (its planes built
+before timing) against the exact fused top-k of the same process, the certified fraction, and the functional
+retrieval.topk (which also splits the gallery each call).  Shape d runs at k = 63 there (a prefilter takes k <= 63)."""
 from __future__ import annotations
 
 import argparse
@@ -21,7 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from clip_dplm_amd import ops  # noqa: E402
+from clip_dplm_amd import ops, retrieval  # noqa: E402
 
 F32_PEAK = 157.3e12
 HBM = 8e12
@@ -104,21 +108,50 @@ def run(name, cfg, iters, warmup, dev):
     return out
 
 
+def run_prefilter(name, cfg, mode, candidates, iters, warmup, dev):
+    Mx, Ny, P = cfg["Mx"], cfg["Ny"], cfg["P"]
+    k = min(cfg["k"], 63)
+    x, y = inputs(Mx, Ny, P, cfg["adversarial"], dev)
+    t_exact = timed(lambda: ops.sim_topk(x, y, k), iters, warmup)
+    s0, i0 = ops.sim_topk(x, y, k)
+    idx = retrieval.EmbeddingIndex(P, dev, prefilter=mode)
+    idx.add(y)
+    t_index = timed(lambda: idx.search(x, k, candidates=candidates), iters, warmup)
+    s1, i1, st = idx.search(x, k, candidates=candidates, return_stats=True)
+    t_func = timed(lambda: retrieval.topk(x, y, k, prefilter=mode, candidates=candidates), max(1, iters // 2), 1)
+    out = {
+        "shape": name, "Mx": Mx, "Ny": Ny, "P": P, "k": k, "adversarial": cfg["adversarial"], "prefilter": mode,
+        "candidates": st["candidates"], "index_search_ms": round(t_index, 4), "exact_topk_ms": round(t_exact, 4),
+        "speedup_vs_exact": round(t_exact / t_index, 3), "certified_frac": round(st["certified"] / st["queries"], 5),
+        "functional_topk_ms": round(t_func, 4), "equal_to_exact": bool(torch.equal(s0, s1) and torch.equal(i0, i1)),
+    }
+    del x, y, idx, s0, i0, s1, i1
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="a,b,c,d")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--prefilter", default="none", help="comma list of none, bf16, bf16x3")
+    ap.add_argument("--candidates", type=int, default=None, help="prefilter candidates per query (default: the API's)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     for name in a.shapes.split(","):
-        line = json.dumps(run(name, SHAPES[name], a.iters, a.warmup, dev))
-        print(line, flush=True)
-        if a.out:
-            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
+        for mode in a.prefilter.split(","):
+            if mode == "none":
+                res = run(name, SHAPES[name], a.iters, a.warmup, dev)
+            else:
+                res = run_prefilter(name, SHAPES[name], mode, a.candidates, a.iters, a.warmup, dev)
+            line = json.dumps(res)
+            print(line, flush=True)
+            if a.out:
+                os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
 
 
 if __name__ == "__main__":
