@@ -22,6 +22,8 @@ from .training import (CosineAnnealingLR, EarlyStopping, GraphedTrainStep, evalu
 from . import training
 from .retrieval import EmbeddingIndex, evaluate_retrieval, metrics_from_ranks, retrieval_metrics
 from . import retrieval
+from .diagnostics import SimilarityStats, evaluate_embeddings, similarity_stats
+from . import diagnostics
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -34,4 +36,5 @@ __all__ = [
     "load_checkpoint", "ESMConfig", "ESMIntegration", "ESMOutput", "BiologicalDataType", "ProteinProjection",
     "GeneProjection", "create_esm_integration", "get_embeddings_batch", "MemoryQueue", "contrastive_loss", "set_linear_precision",
     "retrieval", "EmbeddingIndex", "evaluate_retrieval", "retrieval_metrics", "metrics_from_ranks",
+    "diagnostics", "SimilarityStats", "similarity_stats", "evaluate_embeddings",
 ]

@@ -75,6 +75,8 @@ SIGNATURES = {
     "clipk_sim_rank_workspace": (_sz, [_i, _i, _i]),
     "clipk_sim_rank": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "clipk_sim_rank_cls": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_sim_stats_workspace": (_sz, [_i, _i, _i, _i]),
+    "clipk_sim_stats": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _i, _f, _f] + [_vp] * 11 + [_sz, _vp]),
     "clipk_split_bf16": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "clipk_sim_topk_cand_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "clipk_sim_topk_cand": (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -6,7 +6,7 @@ output memory.  Inputs must live on a CUDA(HIP) device; anything else raises.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -575,6 +575,60 @@ def sim_rank(x, y, labels=None, label_offset: int = 0, scale: Optional[float] = 
                                      class_ids.data_ptr(), rank.data_ptr(), pos.data_ptr(), ws.data_ptr(), ws.numel(),
                                      _stream()), "clipk_sim_rank_cls")
     return rank, pos
+
+
+class SimStats(NamedTuple):
+    """The outputs of clipk_sim_stats, in the order of include/clipk.h."""
+    pos: torch.Tensor          # f32 [Mx]
+    best: torch.Tensor         # f32 [Mx]
+    best_idx: torch.Tensor     # int64 [Mx]
+    hard: torch.Tensor         # f32 [Mx]
+    hard_idx: torch.Tensor     # int64 [Mx]
+    lse: torch.Tensor          # f32 [Mx]
+    neg_sum: torch.Tensor      # f64 [Mx]
+    neg_sumsq: torch.Tensor    # f64 [Mx]
+    hist_neg: torch.Tensor     # int64 [nbins + 2]
+    hist_pos: torch.Tensor     # int64 [nbins + 2]
+
+
+def sim_stats(x, y, *, scale: float = 1.0, labels=None, label_offset: int = 0, cls_x=None, cls_y=None, nbins: int = 64,
+              lo: Optional[float] = None, hi: Optional[float] = None) -> SimStats:
+    """Row statistics and histograms of S = scale * x y^T in one fused pass (include/clipk.h: clipk_sim_stats has the
+    definitions and the binning rule).  l_i = labels[i] (device int64 [Mx]) or label_offset + i; cls_x [Mx] / cls_y [Ny]
+    (device int64, both or neither) exclude the keys of the query's class other than its label.  The histograms have
+    nbins in [1, 256] bins over [lo, hi) plus the two outer slots; lo / hi default to -|scale| / |scale|."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    if labels is not None:
+        if labels.dtype != torch.int64 or labels.shape != (Mx,) or not labels.is_contiguous():
+            raise ValueError(f"labels must be a contiguous int64 tensor of shape ({Mx},)")
+    elif not (0 <= int(label_offset) and int(label_offset) + Mx <= Ny):
+        raise ValueError(f"labels label_offset + i = {label_offset} .. {int(label_offset) + Mx - 1} outside [0, {Ny})")
+    if (cls_x is None) != (cls_y is None):
+        raise ValueError("class ids are needed on both sides (cls_x and cls_y) or on neither")
+    for name, t, n in (("cls_x", cls_x, Mx), ("cls_y", cls_y, Ny)):
+        if t is not None and (t.dtype != torch.int64 or t.shape != (n,) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int64 tensor of shape ({n},)")
+    nbins = int(nbins)
+    if not 1 <= nbins <= 256:
+        raise ValueError(f"nbins must be in [1, 256], got {nbins}")
+    sc = float(scale)
+    lo = -abs(sc) if lo is None else float(lo)
+    hi = abs(sc) if hi is None else float(hi)
+    lo32, hi32 = C.c_float(lo).value, C.c_float(hi).value      # what the kernel sees
+    if not (lo32 < hi32) or lo32 in (float("-inf"), float("inf")) or hi32 in (float("-inf"), float("inf")):
+        raise ValueError(f"need finite lo < hi, got lo = {lo}, hi = {hi}")
+    _need_cuda(x, y, labels, cls_x, cls_y)
+    dev = x.device
+    f32 = lambda: torch.empty(Mx, dtype=torch.float32, device=dev)
+    i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)
+    f64 = lambda: torch.empty(Mx, dtype=torch.float64, device=dev)
+    out = SimStats(f32(), f32(), i64(Mx), f32(), i64(Mx), f32(), f64(), f64(), i64(nbins + 2), i64(nbins + 2))
+    lib = _lib()
+    ws = workspace(lib.clipk_sim_stats_workspace(Mx, Ny, P, nbins), dev, "retrieval")
+    check(lib.clipk_sim_stats(x.data_ptr(), Mx, y.data_ptr(), Ny, P, sc, ptr(labels), int(label_offset), ptr(cls_x),
+                              ptr(cls_y), nbins, lo32, hi32, *(t.data_ptr() for t in out), ws.data_ptr(), ws.numel(),
+                              _stream()), "clipk_sim_stats")
+    return out
 
 
 def ce_logits_lse(S, S2=None, columns=False, label_offset=0):

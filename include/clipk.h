@@ -261,6 +261,66 @@ int clipk_sim_rank_cls(const float* X, int Mx, const float* Y, int Ny, int P, fl
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Embedding-space diagnostics: one pass over S (same tiles, order and requirements as the retrieval entries above)
+ * that keeps the distribution of every row's logits instead of one order statistic.  Replaces the reference's
+ * materialise-then-reduce evaluation: the whole cosine_sims matrix of evaluate (run1/full.py:142-160, reduced by
+ * .mean() at :253-254), the per-epoch similarity_stats of track_training_dynamics (:401-414), the prediction and
+ * confidence logits[i].softmax(0)[p] of analyze_failure_cases (:415-430), the negative difficulty of
+ * analyze_hard_negatives_impact (:449-461), and the argmax that feeds the confusion matrix and the per-pair confusion
+ * rates (:257-268, :297-306).  (analyze_embedding_collapse, :307-315, needs no pass: diagnostics.group_similarity.)
+ *
+ * For query i with label l_i (labels[i], device int64 [Mx], or label_offset + i when labels is NULL, as
+ * clipk_sim_rank): E_i = { j != l_i : cls_y[j] == cls_x[i] } (cls_x [Mx] / cls_y [Ny] device int64, both or neither;
+ * empty without ids: the "mask" rule of clipk_simce_lse_cls), N_i = { j : j != l_i, j not in E_i } the negatives.
+ * Per query ([Mx] each):
+ *   pos                S[i, l_i], the bits clipk_sim_rank returns
+ *   best, best_idx     max of S over {l_i} u N_i, equal scores by the lower index (no ids: clipk_sim_topk, k = 1)
+ *   hard, hard_idx     max over N_i alone, same rule; -inf and -1 when N_i is empty
+ *   lse                log sum_{{l_i} u N_i} exp S[i,j]: running max / sum per lane, fixed-order merge of the splits
+ *   neg_sum, neg_sumsq sum over N_i of S and of S^2, f64
+ * Global (int64 [nbins + 2] each, 1 <= nbins <= 256, lo < hi finite, in units of S):
+ *   hist_neg           counts of S[i,j] over all i and j in N_i;  hist_pos: the same binning of pos
+ * Binning rule: with inv_w = nbins / (hi - lo) evaluated in f64 from the two floats and rounded once to f32,
+ *   slot(S) = 0 if S < lo;  nbins + 1 if S >= hi;  else 1 + min(int((S - lo) * inv_w), nbins - 1)
+ * with the subtraction and the product in f32 (two roundings, no fused multiply-add) and int() truncating.  One device
+ * function bins both histograms.
+ * Determinism: pos, best*, hard* and both histograms are bitwise independent of the split plan (option
+ * retrieval_splits) and of the run; lse, neg_sum, neg_sumsq are deterministic for a fixed plan and agree across plans
+ * to rounding.  A device label outside [0, Ny) gives pos NaN, best_idx = hard_idx = -1 (best = hard = lse = -inf,
+ * zero sums) and the row contributes to neither histogram.
+ * Accuracy of the sums (u = 2^-24).  Two bounds are stated; the function itself takes any P, the derivation below
+ * assumes P <= 4096 (P u <= 2^-12) and Ny < 2^31, and for larger P the bounds are simply not claimed.
+ * (1) Guaranteed.  A logit is a k-ordered chain of P fused multiply-adds and one multiplication by scale, so its error
+ * is relative to Sabs[i,j] = |scale| sum_p |X[i,p] Y[j,p]|, not to |S[i,j]|: the terms of a dot product can cancel, and
+ * no bound in terms of |S| alone holds for every input.  This is a deviation from a bound "c(P) u sum_j |S[i,j]|" and
+ * it is meant: Sabs >= |S|, with equality when the products of a row pair share a sign.
+ *   |S~ - S| <= (P + 2) u Sabs  (gamma_P = P u / (1 - P u), the product's u, their cross term).
+ * A lane adds its 16 values of a tile in f32: <= 15 u sum |S~| (15 additions); the tile partial is converted to f64
+ * exactly and everything above it (tiles of a lane, lane halves, key-waves, splits: fewer than Ny / 16 + 2^16 f64
+ * additions) costs <= 2^27 2^-53 sum |S~| = u / 4 sum |S~|.  With |S~| <= (1 + 2^-11) Sabs:
+ *   |neg_sum[i]   - sum_{N_i} S  | <= (P + 18) u sum_{N_i} Sabs[i,j]
+ * The squares are an fma chain (16 roundings per tile) over S~^2, and S~^2 - S^2 = (2 S + e) e with |e| <= (P + 2) u Sabs:
+ *   |neg_sumsq[i] - sum_{N_i} S^2| <= (2 P + 24) u sum_{N_i} Sabs[i,j]^2
+ * (2) Working bounds of the same constants over |S|, for rows without wholesale cancellation (embeddings):
+ *   |neg_sum[i] - sum S| <= (P + 18) u sum_{N_i} |S[i,j]|,   |neg_sumsq[i] - sum S^2| <= (2 P + 24) u sum_{N_i} S[i,j]^2
+ * They hold whenever the error of a logit stays below (P + 2) u |S|, which round-to-nearest does on average: the P
+ * roundings of a chain act like independent zero-mean errors of size u times a partial sum, i.e. about sqrt(P) u |S|
+ * in all.  By the same model the error of a whole row sum is a sum of independent terms bounded by (P + 18) u |S[i,j]|,
+ * so it stays below 6 (P + 18) u sqrt(sum_{N_i} S[i,j]^2) except with probability 2 exp(-18) per row (Hoeffding).  A
+ * running f32 sum above the tile would instead add about u sqrt(Ny / 192) times the sum itself, which for rows with a
+ * non-zero mean is far above that figure; the GPU tests assert (1), (2) and this last one.
+ * None of the bounds has a term that grows with Ny.
+ * Never allocates, never synchronises, capturable.  workspace (16-byte aligned): clipk_sim_stats_workspace(Mx, Ny, P,
+ * nbins) bytes, 0 for refused shapes. */
+size_t clipk_sim_stats_workspace(int Mx, int Ny, int P, int nbins);
+int clipk_sim_stats(const float* X, int Mx, const float* Y, int Ny, int P, float scale, const int64_t* labels,
+                    int64_t label_offset, const int64_t* cls_x, const int64_t* cls_y, int nbins, float lo, float hi,
+                    float* pos /*[Mx]*/, float* best /*[Mx]*/, int64_t* best_idx /*[Mx]*/, float* hard /*[Mx]*/,
+                    int64_t* hard_idx /*[Mx]*/, float* lse /*[Mx]*/, double* neg_sum /*[Mx]*/,
+                    double* neg_sumsq /*[Mx]*/, int64_t* hist_neg /*[nbins+2]*/, int64_t* hist_pos /*[nbins+2]*/,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Prefiltered exact top-k: the results of clipk_sim_topk, bit for bit, with the bulk of the similarity work on the bf16
  * matrix pipe (v_mfma_f32_32x32x16_bf16) instead of the exact-f32 one.  Replaces the same reference sites as
  * clipk_sim_topk (the similarity matrix of run1/full.py:157 and the argmax of run1/full.py:138,152).

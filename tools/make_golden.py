@@ -572,10 +572,88 @@ def gen_esm_integration():
          edge_attention_mask=et["attention_mask"].numpy(), **sd_np(sd))
 
 
+# ------------------------------------------------------------------------------------------------ run1/full.py evaluation
+def gen_embedding_diagnostics():
+    """The reference's own evaluation functions on a 96 x 32 case with 6 groups: `evaluate` (run1/full.py:142-160),
+    `compute_confusion_matrix` (:257-268), `analyze_embedding_collapse` (:307-315) and the prediction / confidence
+    lines of `analyze_failure_cases` (:415-430).  run1/full.py does not import (scanpy at :8, three `__main__` blocks),
+    so the four definitions are taken alone by name, like MemoryQueue above, and run unedited with a stub model that
+    returns seeded unit embeddings and their scaled similarity.  One batch holds all 96 pairs, so the per-batch logits
+    are the whole matrix.  The restatement tests/sim_stats_ref.py is checked against every result."""
+    import ast
+    from collections import defaultdict
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sim_stats_ref as sref
+    names = ("evaluate", "compute_confusion_matrix", "analyze_embedding_collapse", "analyze_failure_cases")
+    tree = ast.parse(open(REF + "/run1/full.py").read())
+    ns = {"torch": torch, "F": F, "defaultdict": defaultdict}
+    for name in names:
+        node = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == name)
+        exec(compile(ast.Module(body=[node], type_ignores=[]), "run1/full.py", "exec"), ns)
+    n, P, G = 96, 32, 6
+    g = torch.Generator().manual_seed(41)
+    unit = lambda v: (v / v.norm(dim=1, keepdim=True)).float()
+    base = torch.randn(n, P, generator=g, dtype=torch.float64)
+    base[:, 0] += 2.0                                           # a common direction: negatives off zero
+    a = unit(base)
+    b = unit(a.double() + 1.6 * torch.randn(n, P, generator=g, dtype=torch.float64) / P ** 0.5)
+    groups = torch.arange(n) % G
+    groups = groups[torch.randperm(n, generator=g)]
+    scale = torch.tensor(1 / 0.07, dtype=torch.float32)
+
+    class Stub:                                                 # model(diffmap_batch, protein_batch) -> the output dict
+        def eval(self):
+            return self
+
+        def __call__(self, x, y):
+            return {"logits_per_diffmap_protein": scale * (x @ y.t()), "diffmap_embeds": x, "protein_embeds": y}
+
+    dev, model = torch.device("cpu"), Stub()
+    acc, cos = ns["evaluate"](model, [(a, b)], dev)
+    confusion = ns["compute_confusion_matrix"](model, [(a, b)], dev, n)
+    cell_types = [f"c{i}" for i in range(n)]
+    cell_groups = {f"g{k}": [cell_types[i] for i in torch.nonzero(groups == k).flatten().tolist()] for k in range(G)}
+    collapse = ns["analyze_embedding_collapse"](a, b, cell_types, cell_groups)
+    fails = ns["analyze_failure_cases"](model, [(a, b, torch.arange(n))], cell_types, dev)
+    rows, pred, conf = [], [], []
+    for key, items in fails.items():
+        t, p = (int(v[1:]) for v in key.split("->"))
+        assert len(items) == 1
+        rows.append(t), pred.append(p), conf.append(items[0]["confidence"])
+    order = np.argsort(rows)
+    rows, pred, conf = np.asarray(rows)[order], np.asarray(pred)[order], np.asarray(conf, dtype=np.float64)[order]
+    assert 10 <= len(rows) <= n - 10, len(rows)                 # failures and successes
+    S = float(scale) * (a.double() @ b.double().t())
+    top2 = S.topk(2, dim=1).values
+    assert float((top2[:, 0] - top2[:, 1]).min()) > 1e-3        # no near tie: the argmax is the same in any precision
+    # the restatement against the reference
+    lab = torch.arange(n)
+    r = sref.sim_stats(S, lab)
+    assert int((r["best_idx"] == lab).sum()) / n == acc
+    assert torch.equal(r["best_idx"], confusion.argmax(1)) and float(confusion.sum()) == n
+    wrong = torch.nonzero(r["best_idx"] != lab).flatten()
+    assert np.array_equal(wrong.numpy(), rows) and np.array_equal(r["best_idx"][wrong].numpy(), pred)
+    check("diagnostics confidence", torch.exp(r["best"] - r["lse"])[wrong], torch.from_numpy(conf), 1e-5)
+    check("diagnostics mean cosine", (r["neg_sum"].sum() + r["pos"].sum()) / n / n / float(scale), cos.double().mean(), 1e-6)
+    off = ~torch.eye(n, dtype=torch.bool)
+    check("diagnostics hardest negative", r["hard"] / float(scale),
+          cos.double().masked_fill(~off, float("-inf")).max(1).values, 1e-6)
+    gs = sref.group_similarity(a, groups, a, groups, G)
+    check("diagnostics group similarity", gs.diag(), torch.tensor([collapse[f"g{k}"] for k in range(G)],
+                                                                    dtype=torch.float64), 1e-6)
+    save("embedding_diagnostics.npz", a=a.numpy(), b=b.numpy(), groups=groups.numpy(), scale=scale.numpy(),
+         accuracy=acc, cosine_sims=cos.numpy(), confusion=confusion.numpy().astype(np.int64),
+         collapse=np.asarray([collapse[f"g{k}"] for k in range(G)], dtype=np.float64),
+         fail_rows=rows.astype(np.int64), fail_pred=pred.astype(np.int64), fail_confidence=conf)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "proj":
         _load("config", REF + "/triple_flow/1_config.py")
         gen_esm_projections()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "diagnostics":
+        gen_embedding_diagnostics()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "icnn":
         gen_icnn()
@@ -603,4 +681,5 @@ if __name__ == "__main__":
     gen_notebook_b32()
     gen_queue_loss()
     gen_esm_integration()
+    gen_embedding_diagnostics()
     print("all golden fixtures written and the oracle agrees with the reference on each")
