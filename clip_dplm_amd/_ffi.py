@@ -65,6 +65,10 @@ SIGNATURES = {
     "clipk_simce_lse_cls": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_simce_grad_cls": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _f, _f,
                                   _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_simce_hard_workspace": (_sz, [_i, _i, _i]),
+    "clipk_simce_lse_hard": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_simce_grad_hard": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp,
+                                   _vp, _vp, _sz, _vp]),
     "clipk_simce_pairs_workspace": (_sz, [_i, _i, _i]),
     "clipk_simce_lse_pairs": (_i, [_vp, _i, _i, _i, C.POINTER(_i), _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_simce_grad_pairs": (_i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _vp, _f, _f, _f, _vp, _vp,

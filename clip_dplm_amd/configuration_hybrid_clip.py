@@ -119,6 +119,12 @@ class HybridCLIPConfig:
         self.training = training if isinstance(training, TrainingConfig) else TrainingConfig(**(training or {}))
         self.extra = kwargs
 
+    @property
+    def hard_negative_beta(self) -> float:
+        """beta of loss.clip_loss(hard_negative_beta=): hard_negative_weight if use_hard_negatives else 0.  No model reads
+        it implicitly (use_hard_negatives defaults to True): pass it to the model's loss to opt in."""
+        return float(self.hard_negative_weight) if self.use_hard_negatives else 0.0
+
     @classmethod
     def from_configs(cls, rna_config, protein_config, diffmap_config, **kwargs):
         return cls(rna_config=_as_sub(rna_config).to_dict(), protein_config=_as_sub(protein_config).to_dict(),

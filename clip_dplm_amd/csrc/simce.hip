@@ -542,6 +542,71 @@ extern "C" int clipk_simce_grad_cls(const float* X, int Mx, const float* Y, int 
   return clipk_check_launch();
 }
 
+// ---- hard-negative-weighted pair (simce_hard.hip): the same shapes and workspace scheme as the class-aware pair
+extern "C" int clipk_simce_lse_hard_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                                           const float* scale, float beta, int label_offset, const int64_t* cls_x,
+                                           const int64_t* cls_y, float* part, float* lse_h, float* pos, float* coef,
+                                           void* stream);
+extern "C" int clipk_simce_grad_hard_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                                            const float* scale, float beta, int label_offset, const float* coef_x,
+                                            const float* coef_y, const int64_t* cls_x, const int64_t* cls_y, float w_row,
+                                            float w_col, float inv_bg, const float* upstream, float* slab,
+                                            float* dsc_part, void* stream);
+
+extern "C" size_t clipk_simce_hard_workspace(int Mx, int Nkeys, int P) {
+  if (!cls_shape_ok(Mx, Nkeys, P)) return 0;
+  int nqb, ks2, ks3, tps, nt;
+  clipk_simce_tiled_plan(Mx, Nkeys, &nqb, &ks2, &tps, &nt);
+  clipk_simce_grad_tiled_plan(Mx, Nkeys, &nqb, &ks3, &tps, &nt);
+  const size_t a = (size_t)ks2 * Mx * 4 * sizeof(float);                   // (m, a, c, n) partials
+  const size_t c = (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float);    // dX slabs + dscale partials
+  return a > c ? a : c;
+}
+
+static bool hard_beta_ok(float beta) { return beta >= 0.f && beta <= 3.402823466e+38f; }   // finite, not NaN
+
+extern "C" int clipk_simce_lse_hard(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                                    const float* scale, float beta, int label_offset, const int64_t* cls_x,
+                                    const int64_t* cls_y, float* lse_h, float* pos, float* coef, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  if (!X || !Y || !scale || !lse_h || !pos || !coef || !workspace || Nc < 0 || (Nc > 0 && !Yc)) return CLIPK_ERR_BAD_ARG;
+  if ((cls_x == nullptr) != (cls_y == nullptr) || !hard_beta_ok(beta)) return CLIPK_ERR_BAD_ARG;
+  if (!cls_shape_ok(Mx, Ny + Nc, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (label_offset < 0 || (long)label_offset + Mx > Ny) return CLIPK_ERR_BAD_ARG;   // every row has its diagonal key
+  if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc))) return CLIPK_ERR_BAD_ARG;
+  int nqb, ks2, tps, nt;
+  clipk_simce_tiled_plan(Mx, Ny + Nc, &nqb, &ks2, &tps, &nt);
+  if (workspace_bytes < (size_t)ks2 * Mx * 4 * sizeof(float)) return CLIPK_ERR_BAD_ARG;
+  return clipk_simce_lse_hard_launch(X, Mx, Y, Ny, Yc, Nc, P, scale, beta, label_offset, cls_x, cls_y, (float*)workspace,
+                                     lse_h, pos, coef, stream);
+}
+
+extern "C" int clipk_simce_grad_hard(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                                     const float* scale, float beta, int label_offset, const float* coef_x,
+                                     const float* coef_y, const int64_t* cls_x, const int64_t* cls_y, float w_row,
+                                     float w_col, float inv_bg, const float* upstream, float* dX, float* dscale_partial,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  if (!X || !Y || !scale || !coef_x || !coef_y || !dX || !workspace || Nc < 0 || (Nc > 0 && !Yc)) return CLIPK_ERR_BAD_ARG;
+  if ((cls_x == nullptr) != (cls_y == nullptr) || !hard_beta_ok(beta)) return CLIPK_ERR_BAD_ARG;
+  if (!cls_shape_ok(Mx, Ny + Nc, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (label_offset < 0 || (long)label_offset + Mx > Ny) return CLIPK_ERR_BAD_ARG;
+  if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc)) || !aligned16(dX) || !aligned16(workspace))
+    return CLIPK_ERR_BAD_ARG;
+  int nqb, ks3, tps, nt;
+  clipk_simce_grad_tiled_plan(Mx, Ny + Nc, &nqb, &ks3, &tps, &nt);
+  if (workspace_bytes < (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float)) return CLIPK_ERR_BAD_ARG;
+  float* slab = (float*)workspace;
+  float* dscp = slab + (size_t)ks3 * Mx * P;
+  int rc = clipk_simce_grad_hard_launch(X, Mx, Y, Ny, Yc, Nc, P, scale, beta, label_offset, coef_x, coef_y, cls_x, cls_y,
+                                        w_row, w_col, inv_bg, upstream, slab, dscp, stream);
+  if (rc) return rc;
+  long n4 = (long)Mx * P / 4;
+  int blocks = (int)((n4 + 63) / 64); if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(simce_grad_finalize, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)slab,
+                     (const float*)dscp, ks3, Mx, P, scale, dX, dscale_partial, 0L, 0L);
+  return clipk_check_launch();
+}
+
 // loss = (w_row * sum(lse_r - pos_r) + w_col * sum(lse_c - pos_c)) / bg in ONE launch (fixed summation order: strided
 // partial sums per thread, then a tree over the 256 threads): the reference's two F.cross_entropy means and their
 // average (rna_clip_codes.ipynb:1952-1953, old/ablation.py:16) were eight elementwise / reduce launches of 4.5 us each on

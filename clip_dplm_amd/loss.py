@@ -8,6 +8,8 @@ Reference losses covered (weights select the variant):
   * class-aware / label-smoothed InfoNCE          class_ids=, same_class=, label_smoothing= (include/clipk.h:
                                                   clipk_simce_lse_cls): pairs that share a partner stop being each
                                                   other's negatives ("mask") or become positives ("positive")
+  * hard-negative-weighted InfoNCE                run1/full.py:347 'hard_negative', configuration_hybrid_clip.py:105-106
+                                                  hard_negative_beta= (include/clipk.h: clipk_simce_lse_hard)
 
 Multi-GPU scheme: one all-gather of the stacked embeddings [2, B_l, P], one
 all-gather of the two LSE vectors [2, B_l]; every rank then computes the COMPLETE gradient of the global
@@ -163,6 +165,79 @@ class ClassAwareClipLossFn(torch.autograd.Function):
         return da, db, dscale, None, None, None, None, None, None, None
 
 
+_NULL_COEF = {}
+
+
+def _null_coef(like: torch.Tensor) -> torch.Tensor:
+    """Read-only coefficients (q, k1, k2) = (0, -inf, -inf) of like's shape [3, n], made once per (device, n): the
+    one-sided loss's unused direction (exp(... - inf) = 0, as _inf_like for the plain loss)."""
+    key = (str(like.device), like.shape[1])
+    v = _NULL_COEF.get(key)
+    if v is None:
+        v = torch.full(tuple(like.shape), float("-inf"), dtype=torch.float32, device=like.device)
+        v[0] = 0.0
+        _NULL_COEF[key] = v
+    return v
+
+
+class HardNegativeClipLossFn(torch.autograd.Function):
+    """ClipLossFn with hard-negative importance weights (clipk_simce_lse_hard / clipk_simce_grad_hard), optionally with
+    class ids ("mask": same-class keys leave the negatives first).  Multi-GPU: the ids take one more all-gather, the
+    per-row coefficients of both directions travel in the one statistics gather ([W, 6, Bl]) the LSE vectors take in
+    ClipLossFn (the gradient pass needs the coefficients only)."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, beta, ids, w_row, w_col, cache, group):
+        a, b = a.contiguous(), b.contiguous()
+        cache = None if cache is None else cache.contiguous()
+        scale = scale.reshape(1).contiguous()
+        bl = a.shape[0]
+        if group is not None:
+            world, rank = dist.get_world_size(group), dist.get_rank(group)
+            both = _gather_cat(torch.stack([a, b]), group)                 # [W, 2, Bl, P]
+            a_g = both[:, 0].reshape(world * bl, -1)
+            b_g = both[:, 1].reshape(world * bl, -1)
+            ids_g = None if ids is None else _gather_cat(ids, group).reshape(-1)
+        else:
+            world, rank, a_g, b_g, ids_g = 1, 0, a, b, ids
+        off = rank * bl
+        bg = world * bl
+        kw = dict(cls_x=ids, cls_y=ids_g, label_offset=off)
+        lse_r, pos_r, coef_r = _kernels.simce_lse_hard(a, b_g, scale, beta, cache=cache, **kw)
+        if w_col != 0.0:
+            lse_c, pos_c, coef_c = _kernels.simce_lse_hard(b, a_g, scale, beta, **kw)
+        else:
+            lse_c, pos_c, coef_c = None, None, _null_coef(coef_r)     # the unused direction contributes nothing
+        if group is None:
+            out = _kernels.ce_combine(lse_r, pos_r, lse_c, pos_c, w_row, w_col, bg)
+            coef_r_g, coef_c_g = coef_r, coef_c
+        else:
+            local = w_row * (lse_r - pos_r).sum()
+            if pos_c is not None:
+                local = local + w_col * (lse_c - pos_c).sum()
+            stats = _gather_cat(torch.cat([coef_r, coef_c]), group)                  # [W, 6, Bl]
+            coef_r_g = stats[:, :3].permute(1, 0, 2).reshape(3, -1).contiguous()
+            coef_c_g = stats[:, 3:].permute(1, 0, 2).reshape(3, -1).contiguous()
+            dist.all_reduce(local, group=group)
+            out = local / bg
+        ctx.meta = (beta, w_row, w_col, off, bg, cache)
+        ctx.save_for_backward(a, b, a_g, b_g, scale, ids, ids_g, coef_r, coef_c, coef_r_g, coef_c_g)
+        return out
+
+    @staticmethod
+    def backward(ctx, dloss):
+        a, b, a_g, b_g, scale, ids, ids_g, coef_r, coef_c, coef_r_g, coef_c_g = ctx.saved_tensors
+        beta, w_row, w_col, off, bg, cache = ctx.meta
+        g = dloss.reshape(1).contiguous() if dloss.numel() == 1 else None
+        kw = dict(cls_x=ids, cls_y=ids_g, label_offset=off, upstream=g)
+        # rows of a: their own direction has the cache keys; the column direction is the keys' (rows of b) own loss
+        da, dsa = _kernels.simce_grad_hard(a, b_g, scale, beta, coef_r, coef_c_g, w_row, w_col, 1.0 / bg, cache=cache, **kw)
+        # rows of b are the queries of the column direction
+        db, _ = _kernels.simce_grad_hard(b, a_g, scale, beta, coef_c, coef_r_g, w_col, w_row, 1.0 / bg, **kw)
+        dscale = dsa.sum().reshape(1)
+        return da, db, dscale, None, None, None, None, None, None
+
+
 SAME_CLASS_MODES = ("mask", "positive")
 
 
@@ -200,11 +275,36 @@ def _check_class_args(a, b, cache, class_ids, same_class, label_smoothing):
     return class_ids.to(torch.int64).contiguous(), eps
 
 
+def _check_hard_args(a, b, cache, same_class, eps, hard_negative_beta) -> float:
+    """Validate hard_negative_beta and what it may be combined with (ValueError); returns beta as a float."""
+    beta = hard_negative_beta
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0.0 <= float(beta) < float("inf"):
+        raise ValueError(f"hard_negative_beta must be a finite number >= 0, got {beta!r}")
+    beta = float(beta)
+    if beta == 0.0:
+        return beta
+    if same_class == "positive":
+        raise ValueError('hard_negative_beta > 0 cannot be combined with same_class="positive"')
+    if eps > 0.0:
+        raise ValueError("hard_negative_beta > 0 cannot be combined with label_smoothing > 0")
+    if a.dim() != 2 or a.shape != b.shape:
+        raise ValueError(f"embeddings must be two [B, P] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    for name, t in (("a_embeds", a), ("b_embeds", b), ("cache", cache)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"hard-negative InfoNCE takes float32 embeddings, {name} is {t.dtype}")
+    P = a.shape[1]
+    if cache is not None and (cache.dim() != 2 or cache.shape[1] != P):
+        raise ValueError(f"cache must be [Nc, {P}], got {tuple(cache.shape)}")
+    if P % 4 or P > 512:
+        raise ValueError(f"hard-negative InfoNCE supports P % 4 == 0 and P <= 512, got P = {P}")
+    return beta
+
+
 def clip_loss(a_embeds: torch.Tensor, b_embeds: torch.Tensor, logit_scale_exp: torch.Tensor, *,
               symmetric: bool = True, cache: Optional[torch.Tensor] = None, group=None,
               w_row: Optional[float] = None, w_col: Optional[float] = None,
               class_ids: Optional[torch.Tensor] = None, same_class: str = "mask",
-              label_smoothing: float = 0.0) -> torch.Tensor:
+              label_smoothing: float = 0.0, hard_negative_beta: float = 0.0) -> torch.Tensor:
     """InfoNCE over L2-normalised embeddings [B_local, P] (f32).  `logit_scale_exp` = exp(logit_scale)
     (already clamped if the model clamps, old/clip_opt.py:100).  With `group`, the batch is the concatenation
     over ranks in rank order and the returned value is the global-batch loss on every rank.
@@ -212,14 +312,22 @@ def clip_loss(a_embeds: torch.Tensor, b_embeds: torch.Tensor, logit_scale_exp: t
     class_ids: integer [B_local] on the embeddings' device, one id per pair (pairs that share a partner share an id).
     same_class="mask" drops the other same-class keys from each row's softmax; "positive" keeps them and spreads the
     target over them (supervised contrastive).  label_smoothing: eps in [0, 1), torch's convention (eps / N on every
-    key of the row's softmax).  Cache rows carry no class.  Defaults: exactly the plain loss and its kernels."""
+    key of the row's softmax).  Cache rows carry no class.  hard_negative_beta: beta >= 0 of the hard-negative
+    importance weights exp(beta S) / mean exp(beta S) on each row's negatives (include/clipk.h: clipk_simce_lse_hard;
+    the reference's 'hard_negative' variant, its hard_negative_weight); with class_ids ("mask" only) the same-class keys
+    leave the negatives first; not combinable with same_class="positive" or label_smoothing.  Defaults: exactly the
+    plain loss and its kernels."""
     ids, eps = _check_class_args(a_embeds, b_embeds, cache, class_ids, same_class, label_smoothing)
+    beta = _check_hard_args(a_embeds, b_embeds, cache, same_class, eps, hard_negative_beta)
     if w_row is None:
         w_row, w_col = (0.5, 0.5) if symmetric else (1.0, 0.0)
     if group is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         group = dist.group.WORLD
     if group is not None and dist.get_world_size(group) == 1 and not os.environ.get("CLIPK_FORCE_DIST"):
         group = None                         # (CLIPK_FORCE_DIST keeps the collective path for 1-rank RCCL rehearsals)
+    if beta > 0.0:
+        return HardNegativeClipLossFn.apply(a_embeds, b_embeds, logit_scale_exp, beta, ids, float(w_row), float(w_col),
+                                            cache, group)
     if ids is None and eps == 0.0:
         return ClipLossFn.apply(a_embeds, b_embeds, logit_scale_exp, float(w_row), float(w_col), cache, group)
     return ClassAwareClipLossFn.apply(a_embeds, b_embeds, logit_scale_exp, ids, same_class, eps, float(w_row),
@@ -227,16 +335,18 @@ def clip_loss(a_embeds: torch.Tensor, b_embeds: torch.Tensor, logit_scale_exp: t
 
 
 def contrastive_loss(x: torch.Tensor, y: torch.Tensor, temperature: float = 0.1, queue: Optional[torch.Tensor] = None,
-                     group=None) -> torch.Tensor:
+                     group=None, hard_negative_beta: float = 0.0) -> torch.Tensor:
     """tong/utils/losses.py:4-19: InfoNCE with an optional memory queue — both inputs L2-normalised, the queue rows
     appended to the keys as extra negatives (detached), one-sided CE(x y^T / temperature, arange).  Same fused kernels as
-    clip_loss (w_row = 1, w_col = 0, cache = queue): neither the [B, B + Q] logits nor the concatenated keys exist."""
+    clip_loss (w_row = 1, w_col = 0, cache = queue): neither the [B, B + Q] logits nor the concatenated keys exist.
+    hard_negative_beta > 0: clip_loss's hard-negative weights; the queue rows are negatives like the batch's."""
     from . import functional as KF
     scale = torch.full((1,), 1.0 / float(temperature), dtype=torch.float32, device=x.device)
     # a private copy, as the reference's `queue.clone().detach()`: the queue is overwritten in place by the next
     # enqueue, which may come before this loss's backward
     cache = None if queue is None else queue.detach().to(dtype=torch.float32).clone()
-    return clip_loss(KF.l2_normalize(x), KF.l2_normalize(y), scale, symmetric=False, cache=cache, group=group)
+    return clip_loss(KF.l2_normalize(x), KF.l2_normalize(y), scale, symmetric=False, cache=cache, group=group,
+                     hard_negative_beta=hard_negative_beta)
 
 
 _TRI_PAIRS = ((0, 1), (1, 0), (0, 2), (2, 0), (1, 2), (2, 1))      # (cell,pert) (pert,cell) (cell,prot) ...

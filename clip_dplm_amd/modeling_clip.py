@@ -129,13 +129,14 @@ class _PairCLIPModule(nn.Module):
         return {f"logits_per_{self.A}_{self.B}": logits, f"{self.A}_embeds": ea, f"{self.B}_embeds": eb}
 
     def loss(self, a_values, b_values, symmetric: bool = False, group=None, class_ids=None, same_class: str = "mask",
-             label_smoothing: float = 0.0):
+             label_smoothing: float = 0.0, hard_negative_beta: float = 0.0):
         """Training fast path: fused similarity + CE.  symmetric=False is the reference's caller
         (old/ablation.py:16, one-sided CE); symmetric=True is rna_clip_codes.ipynb:1952-1953.  class_ids /
-        same_class / label_smoothing: the class-aware loss of clip_loss."""
+        same_class / label_smoothing: the class-aware loss of clip_loss; hard_negative_beta: its hard-negative
+        weights (run1/full.py:347; opt in with config.hard_negative_beta)."""
         ea, eb = self.embed(a_values, b_values)
         return clip_loss(ea, eb, self.logit_scale.exp(), symmetric=symmetric, group=group, class_ids=class_ids,
-                         same_class=same_class, label_smoothing=label_smoothing)
+                         same_class=same_class, label_smoothing=label_smoothing, hard_negative_beta=hard_negative_beta)
 
 
 class RNAProteinCLIPModule(_PairCLIPModule):
@@ -297,14 +298,17 @@ class OptimizedCLIPModule(nn.Module):
         return out
 
     def loss(self, diffmap_values, protein_values, group=None, class_ids=None, same_class: str = "mask",
-             label_smoothing: float = 0.0):
+             label_smoothing: float = 0.0, hard_negative_beta: float = 0.0):
         """Fused equivalent of optimized_clip_loss(self(diffmap, protein)) without materialised logits.  class_ids /
-        same_class / label_smoothing: the class-aware loss of clip_loss (the cache rows stay plain negatives)."""
+        same_class / label_smoothing: the class-aware loss of clip_loss (the cache rows stay plain negatives);
+        hard_negative_beta: its hard-negative weights (the cache rows are weighted like the batch's negatives).  The
+        config's use_hard_negatives is not read here: pass hard_negative_beta=config.hard_negative_beta to opt in."""
         ed, ep = self.embed(diffmap_values, protein_values)
         self.update_cache(ep)
         cache = self.cache_rows()
         return clip_loss(ed, ep, self.logit_scale.exp().clamp(max=100), symmetric=True, cache=cache, group=group,
-                         class_ids=class_ids, same_class=same_class, label_smoothing=label_smoothing)
+                         class_ids=class_ids, same_class=same_class, label_smoothing=label_smoothing,
+                         hard_negative_beta=hard_negative_beta)
 
 
 def optimized_clip_loss(outputs, temperature=0.07):

@@ -92,9 +92,11 @@ class RNARBPCLIPModel(nn.Module):
         # == enc[:, 0] in the notebook's layout (one position: a view - a select's backward is a zero-fill + a copy launch)
         return y.view(y.shape[1], y.shape[2]) if y.shape[0] == 1 else y[0]
 
-    def forward(self, rna_emb, rbp_emb, class_ids=None, same_class: str = "mask", label_smoothing: float = 0.0):
+    def forward(self, rna_emb, rbp_emb, class_ids=None, same_class: str = "mask", label_smoothing: float = 0.0,
+                hard_negative_beta: float = 0.0):
         """(rna_embed, rbp_embed, loss).  class_ids [B] (e.g. the RBP id of each pair), same_class and label_smoothing
-        select the class-aware loss (loss.clip_loss); the defaults are the notebook's plain symmetric InfoNCE."""
+        select the class-aware loss, hard_negative_beta > 0 the hard-negative-weighted one (loss.clip_loss); the defaults
+        are the notebook's plain symmetric InfoNCE."""
         if self.dual_stream and rna_emb.is_cuda:
             if self._streams is None:
                 self._streams = KF.branch_streams(2)
@@ -107,7 +109,7 @@ class RNARBPCLIPModel(nn.Module):
             rna_embed = KF.l2_normalize(self.rna_projection(self._encode(self.rna_encoder, rna_emb)))
             rbp_embed = KF.l2_normalize(self.rbp_projection(self._encode(self.rbp_encoder, rbp_emb)))
         loss = clip_loss(rna_embed, rbp_embed, self.logit_scale.exp(), symmetric=True, group=None, class_ids=class_ids,
-                         same_class=same_class, label_smoothing=label_smoothing)
+                         same_class=same_class, label_smoothing=label_smoothing, hard_negative_beta=hard_negative_beta)
         return rna_embed, rbp_embed, loss
 
 
@@ -245,10 +247,11 @@ class ProteinRNACLIP(nn.Module):
         return er, ep
 
     def loss_packed(self, rna_packed, rna_cu, rna_max_len, protein_ids_packed, protein_cu, protein_max_len, group=None,
-                    symmetric: bool = True, class_ids=None, same_class: str = "mask", label_smoothing: float = 0.0):
+                    symmetric: bool = True, class_ids=None, same_class: str = "mask", label_smoothing: float = 0.0,
+                    hard_negative_beta: float = 0.0):
         er, ep = self.embed_packed(rna_packed, rna_cu, rna_max_len, protein_ids_packed, protein_cu, protein_max_len)
         return clip_loss(er, ep, self.logit_scale.exp(), symmetric=symmetric, group=group, class_ids=class_ids,
-                         same_class=same_class, label_smoothing=label_smoothing)
+                         same_class=same_class, label_smoothing=label_smoothing, hard_negative_beta=hard_negative_beta)
 
     def forward(self, rna_values, protein_ids, rna_mask=None, protein_mask=None):
         er, ep = self.embed(rna_values, protein_ids, rna_mask, protein_mask)
@@ -256,7 +259,7 @@ class ProteinRNACLIP(nn.Module):
                 "rna_embeds": er, "protein_embeds": ep}
 
     def loss(self, rna_values, protein_ids, rna_mask=None, protein_mask=None, group=None, symmetric: bool = True,
-             class_ids=None, same_class: str = "mask", label_smoothing: float = 0.0):
+             class_ids=None, same_class: str = "mask", label_smoothing: float = 0.0, hard_negative_beta: float = 0.0):
         er, ep = self.embed(rna_values, protein_ids, rna_mask, protein_mask)
         return clip_loss(er, ep, self.logit_scale.exp(), symmetric=symmetric, group=group, class_ids=class_ids,
-                         same_class=same_class, label_smoothing=label_smoothing)
+                         same_class=same_class, label_smoothing=label_smoothing, hard_negative_beta=hard_negative_beta)

@@ -387,6 +387,58 @@ def simce_grad_cls(x, y, scale, lse_x, lse_y, cnt_x, cnt_y, w_row, w_col, inv_bg
     return dx, dsc
 
 
+def _hard_beta(beta) -> float:
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0.0 <= float(beta) < float("inf"):
+        raise ValueError(f"beta must be a finite number >= 0, got {beta!r}")
+    return float(beta)
+
+
+def simce_lse_hard(x, y, scale, beta, cls_x=None, cls_y=None, label_offset=0, cache=None):
+    """Hard-negative-weighted LSE pass (include/clipk.h: clipk_simce_lse_hard): (lse_h, pos, coef); lse_h, pos f32
+    [Mx], coef f32 [3, Mx] = (q, k1, k2), the per-row coefficients of simce_grad_hard.  cls_x [Mx] / cls_y [Ny]: device
+    int64 class ids, both or neither (None: all distinct); same-class batch keys leave the negatives, cache rows never."""
+    Mx, Ny, P, Nc = _cls_args(x, y, scale, cache, cls_x, cls_y, "mask", 0.0)
+    beta = _hard_beta(beta)
+    _need_cuda(x, y, scale, cache, cls_x, cls_y)
+    lse = torch.empty(Mx, dtype=torch.float32, device=x.device)
+    pos = torch.empty(Mx, dtype=torch.float32, device=x.device)
+    coef = torch.empty(3, Mx, dtype=torch.float32, device=x.device)
+    lib = _lib()
+    nbytes = lib.clipk_simce_hard_workspace(Mx, Ny + Nc, P)
+    if nbytes == 0:
+        raise _ffi.ClipkError(f"simce (hard-negative): unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
+    ws = workspace(nbytes, x.device, "simce")
+    check(lib.clipk_simce_lse_hard(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), beta,
+                                   label_offset, ptr(cls_x), ptr(cls_y), lse.data_ptr(), pos.data_ptr(), coef.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), _stream()), "clipk_simce_lse_hard")
+    return lse, pos, coef
+
+
+def simce_grad_hard(x, y, scale, beta, coef_x, coef_y, w_row, w_col, inv_bg, cls_x=None, cls_y=None, label_offset=0,
+                    cache=None, upstream=None):
+    """Hard-negative-weighted gradient pass (include/clipk.h: clipk_simce_grad_hard): (dx, dscale partials).  coef_x
+    [3, Mx]: simce_lse_hard's coefficients of the rows; coef_y [3, Ny]: those of every batch key's own direction."""
+    Mx, Ny, P, Nc = _cls_args(x, y, scale, cache, cls_x, cls_y, "mask", 0.0, (("upstream", upstream, 1),))
+    beta = _hard_beta(beta)
+    for name, t, n in (("coef_x", coef_x, Mx), ("coef_y", coef_y, Ny)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (3, n) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape (3, {n}), got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    _need_cuda(x, y, scale, coef_x, coef_y, cls_x, cls_y, cache, upstream)
+    dx = torch.empty_like(x)
+    dsc = torch.empty(Mx, dtype=torch.float32, device=x.device)
+    lib = _lib()
+    nbytes = lib.clipk_simce_hard_workspace(Mx, Ny + Nc, P)
+    if nbytes == 0:
+        raise _ffi.ClipkError(f"simce (hard-negative): unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
+    ws = workspace(nbytes, x.device, "simce")
+    check(lib.clipk_simce_grad_hard(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), beta,
+                                    label_offset, coef_x.data_ptr(), coef_y.data_ptr(), ptr(cls_x), ptr(cls_y),
+                                    float(w_row), float(w_col), float(inv_bg), ptr(upstream), dx.data_ptr(),
+                                    dsc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipk_simce_grad_hard")
+    return dx, dsc
+
+
 def _pairs_arrays(pairs):
     flat = [int(v) for pr in pairs for v in pr]
     rev = [pairs.index((b, a)) if (b, a) in pairs else i for i, (a, b) in enumerate(pairs)]

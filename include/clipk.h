@@ -205,6 +205,43 @@ int clipk_simce_grad_cls(const float* X, int Mx, const float* Y, int Ny, const f
                          const float* upstream, float* dX /*[Mx,P]*/, float* dscale_partial /*[Mx]*/,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Hard-negative-weighted InfoNCE: the 'hard_negative' loss variant of run1/full.py:347, switched on by
+ * use_hard_negatives / hard_negative_weight (run1/configuration_hybrid_clip.py:105-106; tong/configs/default.yaml:55).
+ * The reference names the variant and its weight only; the arithmetic is the importance weighting of Robinson, Chuang,
+ * Sra and Jegelka, "Contrastive Learning with Hard Negative Samples" (ICLR 2021) with tau_plus = 0, beta their
+ * concentration parameter.  For query row i, diagonal key l = label_offset + i, S[i,j] = scale * <X_i, Y_j> over the Ny
+ * batch keys and then the Nc cache keys:
+ *   Neg_i   = { j != l } minus, with class ids, { j < Ny : cls_y[j] == cls_x[i] }   (the "mask" rule; cache keys stay)
+ *   n_i     = |Neg_i|
+ *   A_i     = log sum_{Neg_i} exp(beta S[i,j]),   C_i = log sum_{Neg_i} exp((1 + beta) S[i,j])
+ *   logNg_i = log n_i + C_i - A_i      = log sum_{Neg_i} w_ij exp S[i,j],  w_ij = exp(beta S_ij) / mean_{Neg_i} exp(beta S_ik)
+ *   lse_h[i] = logaddexp(S[i,l], logNg_i),   pos[i] = S[i,l],   loss_i = lse_h[i] - pos[i]
+ *   n_i = 0: logNg_i = -inf, loss_i = 0, zero gradient.
+ * beta = 0 is the plain loss; for beta >= 0, loss_i >= the plain loss_i.  The batch loss is clipk_ce_combine.
+ * coef [3][Mx]: what the gradient pass needs of a row, q = exp(logNg - lse_h), k1 = log(q (1 + beta)) - C,
+ * k2 = log(q beta) - A (-inf where the factor is 0).
+ * beta >= 0 and finite (else CLIPK_ERR_BAD_ARG); cls_x [Mx], cls_y [Ny]: device int64, both or neither;
+ * label_offset + Mx <= Ny; P % 4 == 0, P <= 512 (else CLIPK_ERR_UNSUPPORTED).  workspace:
+ * clipk_simce_hard_workspace(Mx, Ny + Nc, P) bytes (covers both passes).  Exact-f32 MFMA on the tiling of
+ * clipk_simce_lse; no atomics, no allocation, no synchronisation; key-split partials merge in a fixed order. */
+size_t clipk_simce_hard_workspace(int Mx, int Nkeys, int P);
+int clipk_simce_lse_hard(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                         const float* scale, float beta, int label_offset, const int64_t* cls_x, const int64_t* cls_y,
+                         float* lse_h /*[Mx]*/, float* pos /*[Mx]*/, float* coef /*[3][Mx]*/, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* Gradient of (w_row * sum_i loss_i + w_col * sum_j loss'_j) * inv_bg (* upstream) w.r.t. the rows of X, the column
+ * direction being every key's own loss over the pair rows (no cache there).  Per direction, on its negatives,
+ *   g[i,j] = q_i [(1 + beta) exp((1 + beta) S_ij - C_i) - beta exp(beta S_ij - A_i)]
+ *          = exp((1 + beta) S_ij + k1_i) - exp(beta S_ij + k2_i),     g[i,l] = -q_i,  g = 0 on masked keys
+ *   G[i,j] = (w_row g_row[i,j] + w_col g_col[j,i]) * inv_bg (* upstream)
+ * and dX, dscale_partial follow from G as in clipk_simce_grad.  coef_x [3][Mx]: the rows' coefficients; coef_y [3][Ny]:
+ * those of every batch key's own direction (with w_col == 0: q = 0, k1 = k2 = -inf). */
+int clipk_simce_grad_hard(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
+                          const float* scale, float beta, int label_offset, const float* coef_x, const float* coef_y,
+                          const int64_t* cls_x, const int64_t* cls_y, float w_row, float w_col, float inv_bg,
+                          const float* upstream, float* dX /*[Mx,P]*/, float* dscale_partial /*[Mx]*/,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Batched form for several same-shape contrastive problems on one logit scale — the tri-modal ContrastiveModel of
  * current/tf_clip_codes (1).ipynb:13150-13163 (cell x pert, cell x protein, pert x protein, each symmetric) is six
  * directed problems (X = E[pairs[2i]], Y = E[pairs[2i+1]]), computed by ONE launch per pass (grid z = problem):
