@@ -19,7 +19,7 @@ summed across ranks afterwards by the optimiser's reduce-scatter.
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -39,79 +39,83 @@ def _gather_cat(t: torch.Tensor, group) -> torch.Tensor:
     return out.view((world,) + tuple(t.shape))
 
 
-_INF = {}
+_CONST = {}
 
 
-def _inf_like(t: torch.Tensor) -> torch.Tensor:
-    """A read-only +inf vector of t's shape, made once per (device, length): the one-sided loss's unused direction."""
-    key = (str(t.device), t.numel())
-    v = _INF.get(key)
+def _const_like(t: torch.Tensor, fill: float, row0: Optional[float] = None) -> torch.Tensor:
+    """A read-only f32 tensor of t's shape filled with `fill` (row 0 with `row0` where given), made once per (device,
+    shape, values): the statistic of the one-sided loss's unused direction."""
+    key = (str(t.device), tuple(t.shape), fill, row0)
+    v = _CONST.get(key)
     if v is None:
-        v = _INF[key] = torch.full((t.numel(),), float("inf"), dtype=torch.float32, device=t.device)
-    return v.view(t.shape)
+        v = _CONST[key] = torch.full(tuple(t.shape), fill, dtype=torch.float32, device=t.device)
+        if row0 is not None:
+            v[0] = row0
+    return v
 
 
-class ClipLossFn(torch.autograd.Function):
+class _Variant(NamedTuple):
+    """What tells one InfoNCE variant from another inside InfoNCEFn.  `stat` is the tuple of per-row tensors (last
+    dimension: the rows) that travel from the LSE pass to the gradient pass, of one direction.
+      lse(x, keys, scale, off, cache, ids_x, ids_keys) -> (lse, tgt, stat)
+      null(stat_r) -> stat of the unused direction of the one-sided loss (it contributes nothing)
+      grad(x, keys, scale, stat_x, stat_keys, w_x, w_keys, inv_bg, nkeys, off, cache, ids_x, ids_keys, upstream)
+          -> (dx, dscale partials); nkeys: the key count of the keys' own direction."""
+    lse: Callable
+    null: Callable
+    grad: Callable
+
+
+def _plain_lse(x, keys, scale, off, cache, ids_x, ids_keys):
+    lse, pos = _kernels.simce_lse(x, keys, scale, label_offset=off, cache=cache)
+    return lse, pos, (lse,)
+
+
+_PLAIN = _Variant(
+    lse=_plain_lse,
+    null=lambda stat: (_const_like(stat[0], float("inf")),),              # exp(s - inf) = 0
+    grad=lambda x, keys, scale, sx, sk, w_x, w_keys, inv_bg, nkeys, off, cache, ids_x, ids_keys, g:
+        _kernels.simce_grad(x, keys, scale, sx[0], sk[0], w_x, w_keys, inv_bg, label_offset=off, cache=cache, upstream=g))
+
+
+def _class_aware(same_class: str, eps: float) -> _Variant:
+    """Class ids on the pairs and / or label smoothing (clipk_simce_lse_cls / clipk_simce_grad_cls): stat = (lse, cnt),
+    the same-class counts travel with the LSE vectors."""
+    def lse(x, keys, scale, off, cache, ids_x, ids_keys):
+        lse, tgt, cnt = _kernels.simce_lse_cls(x, keys, scale, cache=cache, cls_x=ids_x, cls_y=ids_keys,
+                                               same_class=same_class, eps=eps, label_offset=off)
+        return lse, tgt, (lse, cnt)
+
+    def grad(x, keys, scale, sx, sk, w_x, w_keys, inv_bg, nkeys, off, cache, ids_x, ids_keys, g):
+        return _kernels.simce_grad_cls(x, keys, scale, sx[0], sk[0], sx[1], sk[1], w_x, w_keys, inv_bg, nkeys, cache=cache,
+                                       cls_x=ids_x, cls_y=ids_keys, same_class=same_class, eps=eps, label_offset=off,
+                                       upstream=g)
+    return _Variant(lse, lambda stat: (_const_like(stat[0], float("inf")), stat[1]), grad)
+
+
+def _hard_negative(beta: float) -> _Variant:
+    """Hard-negative importance weights (clipk_simce_lse_hard / clipk_simce_grad_hard), optionally with class ids
+    ("mask": same-class keys leave the negatives first): stat = (coef [3, rows],), the gradient pass needs the per-row
+    coefficients (q, k1, k2) only; (0, -inf, -inf) contribute nothing."""
+    def lse(x, keys, scale, off, cache, ids_x, ids_keys):
+        lse, pos, coef = _kernels.simce_lse_hard(x, keys, scale, beta, cache=cache, cls_x=ids_x, cls_y=ids_keys,
+                                                 label_offset=off)
+        return lse, pos, (coef,)
+
+    def grad(x, keys, scale, sx, sk, w_x, w_keys, inv_bg, nkeys, off, cache, ids_x, ids_keys, g):
+        return _kernels.simce_grad_hard(x, keys, scale, beta, sx[0], sk[0], w_x, w_keys, inv_bg, cache=cache, cls_x=ids_x,
+                                        cls_y=ids_keys, label_offset=off, upstream=g)
+    return _Variant(lse, lambda stat: (_const_like(stat[0], float("-inf"), 0.0),), grad)
+
+
+class InfoNCEFn(torch.autograd.Function):
+    """The fused InfoNCE of every variant (_Variant): two directed LSE passes, the loss, two gradient passes with the
+    roles of the two sides swapped.  Multi-GPU: one all-gather of the embeddings [W, 2, Bl, P], one of the class ids
+    where there are any, one of both directions' statistics ([W, 2, Bl] plain, [W, 4, Bl] class-aware, [W, 6, Bl]
+    hard-negative) and one all-reduce of the local sum."""
+
     @staticmethod
-    def forward(ctx, a, b, scale, w_row, w_col, cache, group):
-        a, b = a.contiguous(), b.contiguous()
-        scale = scale.reshape(1).contiguous()
-        bl = a.shape[0]
-        if group is not None:
-            world, rank = dist.get_world_size(group), dist.get_rank(group)
-            both = _gather_cat(torch.stack([a, b]), group)                 # [W, 2, Bl, P]
-            a_g = both[:, 0].reshape(world * bl, -1)
-            b_g = both[:, 1].reshape(world * bl, -1)
-        else:
-            world, rank, a_g, b_g = 1, 0, a, b
-        off = rank * bl
-        bg = world * bl
-        lse_r, pos_r = _kernels.simce_lse(a, b_g, scale, label_offset=off, cache=cache)
-        pos_c = None
-        if w_col != 0.0:
-            lse_c, pos_c = _kernels.simce_lse(b, a_g, scale, label_offset=off)
-        else:
-            lse_c = _inf_like(lse_r)                       # exp(s - inf) = 0: the unused direction contributes nothing
-        if group is None:                                  # single process: sums, weights and the mean in one launch
-            out = _kernels.ce_combine(lse_r, pos_r, lse_c if pos_c is not None else None, pos_c, w_row, w_col, bg)
-            ctx.meta = (w_row, w_col, off, bg, cache)
-            ctx.save_for_backward(a, b, a_g, b_g, scale, lse_r, lse_c, lse_r, lse_c)
-            return out
-        local = w_row * (lse_r - pos_r).sum()
-        if pos_c is not None:
-            local = local + w_col * (lse_c - pos_c).sum()
-        if group is not None:
-            lses = _gather_cat(torch.stack([lse_r, lse_c]), group)          # [W, 2, Bl]
-            lse_r_g = lses[:, 0].reshape(-1).contiguous()
-            lse_c_g = lses[:, 1].reshape(-1).contiguous()
-            dist.all_reduce(local, group=group)
-        else:
-            lse_r_g, lse_c_g = lse_r, lse_c
-        ctx.meta = (w_row, w_col, off, bg, cache)
-        ctx.save_for_backward(a, b, a_g, b_g, scale, lse_r, lse_c, lse_r_g, lse_c_g)
-        return local / bg
-
-    @staticmethod
-    def backward(ctx, dloss):
-        a, b, a_g, b_g, scale, lse_r, lse_c, lse_r_g, lse_c_g = ctx.saved_tensors
-        w_row, w_col, off, bg, cache = ctx.meta
-        # rows of a: row-direction softmax uses their own LSE, column direction the keys' LSE
-        # the incoming gradient (1.0 from loss.backward()) is folded into the kernels' 1 / Bg factor: no `grad * g` launches
-        g = dloss.reshape(1).contiguous() if dloss.numel() == 1 else None
-        da, dsa = _kernels.simce_grad(a, b_g, scale, lse_r, lse_c_g, w_row, w_col, 1.0 / bg, label_offset=off, cache=cache,
-                                      upstream=g)
-        # rows of b are the queries of the column direction
-        db, _ = _kernels.simce_grad(b, a_g, scale, lse_c, lse_r_g, w_col, w_row, 1.0 / bg, label_offset=off, upstream=g)
-        dscale = dsa.sum().reshape(1)          # this rank's rows only; the optimiser sums parameter grads over ranks
-        return da, db, dscale, None, None, None, None
-
-
-class ClassAwareClipLossFn(torch.autograd.Function):
-    """ClipLossFn with class ids on the pairs and / or label smoothing (clipk_simce_lse_cls / clipk_simce_grad_cls).
-    Multi-GPU: the ids take one more all-gather, the same-class counts travel with the LSE gather ([W, 4, Bl])."""
-
-    @staticmethod
-    def forward(ctx, a, b, scale, ids, same_class, eps, w_row, w_col, cache, group):
+    def forward(ctx, a, b, scale, variant, ids, w_row, w_col, cache, group):
         a, b = a.contiguous(), b.contiguous()
         cache = None if cache is None else cache.contiguous()
         scale = scale.reshape(1).contiguous()
@@ -126,119 +130,62 @@ class ClassAwareClipLossFn(torch.autograd.Function):
             world, rank, a_g, b_g, ids_g = 1, 0, a, b, ids
         off = rank * bl
         bg = world * bl
-        nc = 0 if cache is None else cache.shape[0]
-        kw = dict(cls_x=ids, cls_y=ids_g, same_class=same_class, eps=eps, label_offset=off)
-        lse_r, tgt_r, cnt_r = _kernels.simce_lse_cls(a, b_g, scale, cache=cache, **kw)
+        lse_r, tgt_r, stat_r = variant.lse(a, b_g, scale, off, cache, ids, ids_g)
         if w_col != 0.0:
-            lse_c, tgt_c, cnt_c = _kernels.simce_lse_cls(b, a_g, scale, **kw)
+            lse_c, tgt_c, stat_c = variant.lse(b, a_g, scale, off, None, ids, ids_g)
         else:
-            lse_c, tgt_c, cnt_c = _inf_like(lse_r), None, cnt_r       # the unused direction contributes nothing
-        if group is None:
-            out = _kernels.ce_combine(lse_r, tgt_r, lse_c if tgt_c is not None else None, tgt_c, w_row, w_col, bg)
-            lse_r_g, lse_c_g, cnt_r_g, cnt_c_g = lse_r, lse_c, cnt_r, cnt_c
+            lse_c, tgt_c, stat_c = None, None, variant.null(stat_r)
+        if group is None:                                  # single process: sums, weights and the mean in one launch
+            out = _kernels.ce_combine(lse_r, tgt_r, lse_c, tgt_c, w_row, w_col, bg)
+            stat_r_g, stat_c_g = stat_r, stat_c
         else:
             local = w_row * (lse_r - tgt_r).sum()
             if tgt_c is not None:
                 local = local + w_col * (lse_c - tgt_c).sum()
-            stats = _gather_cat(torch.stack([lse_r, lse_c, cnt_r, cnt_c]), group)    # [W, 4, Bl]
-            lse_r_g, lse_c_g, cnt_r_g, cnt_c_g = (stats[:, k].reshape(-1).contiguous() for k in range(4))
+            # one gather of both directions' rows, [W, K, Bl], laid out back to each tensor's [..., W * Bl]
+            each = [t for pair in zip(stat_r, stat_c) for t in pair]
+            stats = _gather_cat(torch.cat([t.reshape(-1, bl) for t in each]), group)
+            stats = [g.permute(1, 0, 2).reshape(t.shape[:-1] + (bg,)).contiguous()
+                     for g, t in zip(stats.split([t.numel() // bl for t in each], dim=1), each)]
+            stat_r_g, stat_c_g = tuple(stats[0::2]), tuple(stats[1::2])
             dist.all_reduce(local, group=group)
             out = local / bg
-        ctx.meta = (same_class, eps, w_row, w_col, off, bg, nc, cache)
-        ctx.save_for_backward(a, b, a_g, b_g, scale, ids, ids_g, lse_r, lse_c, cnt_r, cnt_c, lse_r_g, lse_c_g, cnt_r_g,
-                              cnt_c_g)
+        ctx.meta = (variant, w_row, w_col, off, bg, cache)
+        ctx.save_for_backward(a, b, a_g, b_g, scale, ids, ids_g, *stat_r, *stat_c, *stat_r_g, *stat_c_g)
         return out
 
     @staticmethod
     def backward(ctx, dloss):
-        a, b, a_g, b_g, scale, ids, ids_g, lse_r, lse_c, cnt_r, cnt_c, lse_r_g, lse_c_g, cnt_r_g, cnt_c_g = ctx.saved_tensors
-        same_class, eps, w_row, w_col, off, bg, nc, cache = ctx.meta
+        a, b, a_g, b_g, scale, ids, ids_g, *stats = ctx.saved_tensors
+        variant, w_row, w_col, off, bg, cache = ctx.meta
+        n = len(stats) // 4
+        stat_r, stat_c, stat_r_g, stat_c_g = (stats[k * n:(k + 1) * n] for k in range(4))
+        nc = 0 if cache is None else cache.shape[0]
+        # the incoming gradient (1.0 from loss.backward()) is folded into the kernels' 1 / Bg factor: no `grad * g` launches
         g = dloss.reshape(1).contiguous() if dloss.numel() == 1 else None
-        kw = dict(cls_x=ids, cls_y=ids_g, same_class=same_class, eps=eps, label_offset=off, upstream=g)
-        # rows of a: their own direction has the cache keys, the column direction (rows of b) has the Bg rows of a
-        da, dsa = _kernels.simce_grad_cls(a, b_g, scale, lse_r, lse_c_g, cnt_r, cnt_c_g, w_row, w_col, 1.0 / bg, bg,
-                                          cache=cache, **kw)
+        # rows of a: their own direction has the cache keys; the column direction (rows of b) has the Bg rows of a
+        da, dsa = variant.grad(a, b_g, scale, stat_r, stat_c_g, w_row, w_col, 1.0 / bg, bg, off, cache, ids, ids_g, g)
         # rows of b are the queries of the column direction; the keys' (a's) own direction has Bg + Nc keys
-        db, _ = _kernels.simce_grad_cls(b, a_g, scale, lse_c, lse_r_g, cnt_c, cnt_r_g, w_col, w_row, 1.0 / bg, bg + nc,
-                                        **kw)
-        dscale = dsa.sum().reshape(1)
-        return da, db, dscale, None, None, None, None, None, None, None
-
-
-_NULL_COEF = {}
-
-
-def _null_coef(like: torch.Tensor) -> torch.Tensor:
-    """Read-only coefficients (q, k1, k2) = (0, -inf, -inf) of like's shape [3, n], made once per (device, n): the
-    one-sided loss's unused direction (exp(... - inf) = 0, as _inf_like for the plain loss)."""
-    key = (str(like.device), like.shape[1])
-    v = _NULL_COEF.get(key)
-    if v is None:
-        v = torch.full(tuple(like.shape), float("-inf"), dtype=torch.float32, device=like.device)
-        v[0] = 0.0
-        _NULL_COEF[key] = v
-    return v
-
-
-class HardNegativeClipLossFn(torch.autograd.Function):
-    """ClipLossFn with hard-negative importance weights (clipk_simce_lse_hard / clipk_simce_grad_hard), optionally with
-    class ids ("mask": same-class keys leave the negatives first).  Multi-GPU: the ids take one more all-gather, the
-    per-row coefficients of both directions travel in the one statistics gather ([W, 6, Bl]) the LSE vectors take in
-    ClipLossFn (the gradient pass needs the coefficients only)."""
-
-    @staticmethod
-    def forward(ctx, a, b, scale, beta, ids, w_row, w_col, cache, group):
-        a, b = a.contiguous(), b.contiguous()
-        cache = None if cache is None else cache.contiguous()
-        scale = scale.reshape(1).contiguous()
-        bl = a.shape[0]
-        if group is not None:
-            world, rank = dist.get_world_size(group), dist.get_rank(group)
-            both = _gather_cat(torch.stack([a, b]), group)                 # [W, 2, Bl, P]
-            a_g = both[:, 0].reshape(world * bl, -1)
-            b_g = both[:, 1].reshape(world * bl, -1)
-            ids_g = None if ids is None else _gather_cat(ids, group).reshape(-1)
-        else:
-            world, rank, a_g, b_g, ids_g = 1, 0, a, b, ids
-        off = rank * bl
-        bg = world * bl
-        kw = dict(cls_x=ids, cls_y=ids_g, label_offset=off)
-        lse_r, pos_r, coef_r = _kernels.simce_lse_hard(a, b_g, scale, beta, cache=cache, **kw)
-        if w_col != 0.0:
-            lse_c, pos_c, coef_c = _kernels.simce_lse_hard(b, a_g, scale, beta, **kw)
-        else:
-            lse_c, pos_c, coef_c = None, None, _null_coef(coef_r)     # the unused direction contributes nothing
-        if group is None:
-            out = _kernels.ce_combine(lse_r, pos_r, lse_c, pos_c, w_row, w_col, bg)
-            coef_r_g, coef_c_g = coef_r, coef_c
-        else:
-            local = w_row * (lse_r - pos_r).sum()
-            if pos_c is not None:
-                local = local + w_col * (lse_c - pos_c).sum()
-            stats = _gather_cat(torch.cat([coef_r, coef_c]), group)                  # [W, 6, Bl]
-            coef_r_g = stats[:, :3].permute(1, 0, 2).reshape(3, -1).contiguous()
-            coef_c_g = stats[:, 3:].permute(1, 0, 2).reshape(3, -1).contiguous()
-            dist.all_reduce(local, group=group)
-            out = local / bg
-        ctx.meta = (beta, w_row, w_col, off, bg, cache)
-        ctx.save_for_backward(a, b, a_g, b_g, scale, ids, ids_g, coef_r, coef_c, coef_r_g, coef_c_g)
-        return out
-
-    @staticmethod
-    def backward(ctx, dloss):
-        a, b, a_g, b_g, scale, ids, ids_g, coef_r, coef_c, coef_r_g, coef_c_g = ctx.saved_tensors
-        beta, w_row, w_col, off, bg, cache = ctx.meta
-        g = dloss.reshape(1).contiguous() if dloss.numel() == 1 else None
-        kw = dict(cls_x=ids, cls_y=ids_g, label_offset=off, upstream=g)
-        # rows of a: their own direction has the cache keys; the column direction is the keys' (rows of b) own loss
-        da, dsa = _kernels.simce_grad_hard(a, b_g, scale, beta, coef_r, coef_c_g, w_row, w_col, 1.0 / bg, cache=cache, **kw)
-        # rows of b are the queries of the column direction
-        db, _ = _kernels.simce_grad_hard(b, a_g, scale, beta, coef_c, coef_r_g, w_col, w_row, 1.0 / bg, **kw)
-        dscale = dsa.sum().reshape(1)
+        db, _ = variant.grad(b, a_g, scale, stat_c, stat_r_g, w_col, w_row, 1.0 / bg, bg + nc, off, None, ids, ids_g, g)
+        dscale = dsa.sum().reshape(1)          # this rank's rows only; the optimiser sums parameter grads over ranks
         return da, db, dscale, None, None, None, None, None, None
 
 
 SAME_CLASS_MODES = ("mask", "positive")
+
+
+def _check_embeddings(a, b, cache, what: str) -> None:
+    """Shapes, dtypes and P of the embeddings and the cache for the class-aware and hard-negative kernels (ValueError)."""
+    if a.dim() != 2 or a.shape != b.shape:
+        raise ValueError(f"embeddings must be two [B, P] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    for name, t in (("a_embeds", a), ("b_embeds", b), ("cache", cache)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"{what} takes float32 embeddings, {name} is {t.dtype}")
+    P = a.shape[1]
+    if cache is not None and (cache.dim() != 2 or cache.shape[1] != P):
+        raise ValueError(f"cache must be [Nc, {P}], got {tuple(cache.shape)}")
+    if P % 4 or P > 512:
+        raise ValueError(f"{what} supports P % 4 == 0 and P <= 512, got P = {P}")
 
 
 def _check_class_args(a, b, cache, class_ids, same_class, label_smoothing):
@@ -252,16 +199,7 @@ def _check_class_args(a, b, cache, class_ids, same_class, label_smoothing):
         raise ValueError(f"label_smoothing must be in [0, 1), got {eps}")
     if class_ids is None and eps == 0.0:
         return None, eps
-    if a.dim() != 2 or a.shape != b.shape:
-        raise ValueError(f"embeddings must be two [B, P] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
-    for name, t in (("a_embeds", a), ("b_embeds", b), ("cache", cache)):
-        if t is not None and t.dtype != torch.float32:
-            raise ValueError(f"class-aware / label-smoothed InfoNCE takes float32 embeddings, {name} is {t.dtype}")
-    P = a.shape[1]
-    if cache is not None and (cache.dim() != 2 or cache.shape[1] != P):
-        raise ValueError(f"cache must be [Nc, {P}], got {tuple(cache.shape)}")
-    if P % 4 or P > 512:
-        raise ValueError(f"class-aware / label-smoothed InfoNCE supports P % 4 == 0 and P <= 512, got P = {P}")
+    _check_embeddings(a, b, cache, "class-aware / label-smoothed InfoNCE")
     if class_ids is None:
         return None, eps
     if not torch.is_tensor(class_ids):
@@ -287,16 +225,7 @@ def _check_hard_args(a, b, cache, same_class, eps, hard_negative_beta) -> float:
         raise ValueError('hard_negative_beta > 0 cannot be combined with same_class="positive"')
     if eps > 0.0:
         raise ValueError("hard_negative_beta > 0 cannot be combined with label_smoothing > 0")
-    if a.dim() != 2 or a.shape != b.shape:
-        raise ValueError(f"embeddings must be two [B, P] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
-    for name, t in (("a_embeds", a), ("b_embeds", b), ("cache", cache)):
-        if t is not None and t.dtype != torch.float32:
-            raise ValueError(f"hard-negative InfoNCE takes float32 embeddings, {name} is {t.dtype}")
-    P = a.shape[1]
-    if cache is not None and (cache.dim() != 2 or cache.shape[1] != P):
-        raise ValueError(f"cache must be [Nc, {P}], got {tuple(cache.shape)}")
-    if P % 4 or P > 512:
-        raise ValueError(f"hard-negative InfoNCE supports P % 4 == 0 and P <= 512, got P = {P}")
+    _check_embeddings(a, b, cache, "hard-negative InfoNCE")
     return beta
 
 
@@ -326,12 +255,12 @@ def clip_loss(a_embeds: torch.Tensor, b_embeds: torch.Tensor, logit_scale_exp: t
     if group is not None and dist.get_world_size(group) == 1 and not os.environ.get("CLIPK_FORCE_DIST"):
         group = None                         # (CLIPK_FORCE_DIST keeps the collective path for 1-rank RCCL rehearsals)
     if beta > 0.0:
-        return HardNegativeClipLossFn.apply(a_embeds, b_embeds, logit_scale_exp, beta, ids, float(w_row), float(w_col),
-                                            cache, group)
-    if ids is None and eps == 0.0:
-        return ClipLossFn.apply(a_embeds, b_embeds, logit_scale_exp, float(w_row), float(w_col), cache, group)
-    return ClassAwareClipLossFn.apply(a_embeds, b_embeds, logit_scale_exp, ids, same_class, eps, float(w_row),
-                                      float(w_col), cache, group)
+        variant = _hard_negative(beta)
+    elif ids is None and eps == 0.0:
+        variant = _PLAIN
+    else:
+        variant = _class_aware(same_class, eps)
+    return InfoNCEFn.apply(a_embeds, b_embeds, logit_scale_exp, variant, ids, float(w_row), float(w_col), cache, group)
 
 
 def contrastive_loss(x: torch.Tensor, y: torch.Tensor, temperature: float = 0.1, queue: Optional[torch.Tensor] = None,

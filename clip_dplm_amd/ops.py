@@ -154,9 +154,10 @@ def keep_for_capture(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-def workspace(nbytes: int, device, tag: str = "ws") -> torch.Tensor:
-    """Grow-only per-(device, stream, tag) scratch buffer (kernels never allocate)."""
-    key = (str(device), _stream(), tag)
+def workspace(nbytes: int, device, tag: str = "ws", stream: Optional[int] = None) -> torch.Tensor:
+    """Grow-only per-(device, stream, tag) scratch buffer (kernels never allocate).  stream: the current stream's handle
+    where the caller has fetched it already."""
+    key = (str(device), _stream() if stream is None else stream, tag)
     buf = _WS.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 1 << 16), dtype=torch.uint8, device=device)
@@ -265,23 +266,40 @@ def gemm_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: Optional[torch.Tensor] = N
 
 
 # --------------------------------------------------------------------------------------------------
+# kind -> (the entry point that sizes its workspace, its name in error messages)
+_SIMCE_KINDS = {"plain": ("clipk_simce_workspace", "simce"),
+                "cls": ("clipk_simce_cls_workspace", "simce (class-aware)"),
+                "hard": ("clipk_simce_hard_workspace", "simce (hard-negative)")}
+
+
+def _simce(entry, kind, x, y, scale, cache, args, outs):
+    """The body the six simce wrappers share, after each has checked its operands: shapes, outputs, workspace, the call.
+    entry: the C entry point; kind: a key of _SIMCE_KINDS; args: the entry point's arguments between scale and the
+    outputs; outs: (torch.empty or torch.zeros, shape) per f32 output.  Returns the outputs."""
+    Mx, P = x.shape
+    Ny = y.shape[0]
+    Nc = 0 if cache is None else cache.shape[0]
+    dev = x.device
+    res = [new(*shape, dtype=torch.float32, device=dev) for new, shape in outs]      # sizes unpacked: cheaper to parse
+    lib = _lib()
+    ws_entry, what = _SIMCE_KINDS[kind]
+    nbytes = getattr(lib, ws_entry)(Mx, Ny + Nc, P)
+    if nbytes == 0:
+        raise _ffi.ClipkError(f"{what}: unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
+    stream = _stream()                                  # fetched once: for the workspace's key and for the launch
+    ws = workspace(nbytes, dev, "simce", stream)
+    check(getattr(lib, entry)(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), *args,
+                              *[t.data_ptr() for t in res], ws.data_ptr(), ws.numel(), stream), entry)
+    return tuple(res)
+
+
 def simce_lse(x, y, scale, label_offset=0, cache=None):
     """lse[i] = logsumexp_j scale*<x_i, keys_j>, pos[i] = scale*<x_i, y_{label_offset+i}>."""
     _need_cuda(x, y, scale, cache)
     assert x.dtype == torch.float32 and y.dtype == torch.float32 and x.is_contiguous() and y.is_contiguous()
-    Mx, P = x.shape
-    Ny = y.shape[0]
-    Nc = 0 if cache is None else cache.shape[0]
-    lse = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    pos = torch.zeros(Mx, dtype=torch.float32, device=x.device)
-    lib = _lib()
-    nbytes = lib.clipk_simce_workspace(Mx, Ny + Nc, P)
-    if nbytes == 0:
-        raise _ffi.ClipkError(f"simce: unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
-    ws = workspace(nbytes, x.device, "simce")
-    check(lib.clipk_simce_lse(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), label_offset,
-                              lse.data_ptr(), pos.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipk_simce_lse")
-    return lse, pos
+    rows = (x.shape[0],)
+    return _simce("clipk_simce_lse", "plain", x, y, scale, cache, (label_offset,),
+                  ((torch.empty, rows), (torch.zeros, rows)))                       # lse, pos
 
 
 def ce_combine(lse_r, pos_r, lse_c, pos_c, w_row, w_col, bg):
@@ -294,22 +312,16 @@ def ce_combine(lse_r, pos_r, lse_c, pos_c, w_row, w_col, bg):
     return out
 
 
+def _grad_outs(x):
+    return (torch.empty, x.shape), (torch.empty, x.shape[:1])               # dx, dscale partials
+
+
 def simce_grad(x, y, scale, lse_x, lse_y, w_row, w_col, inv_bg, label_offset=0, cache=None, upstream=None):
     """upstream: 1-element device tensor multiplied into the gradient inside the kernel (the loss' grad_output)."""
     _need_cuda(x, y, scale, lse_x, lse_y, cache, upstream)
-    Mx, P = x.shape
-    Ny = y.shape[0]
-    Nc = 0 if cache is None else cache.shape[0]
-    dx = torch.empty_like(x)
-    dsc = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    lib = _lib()
-    nbytes = lib.clipk_simce_workspace(Mx, Ny + Nc, P)
-    ws = workspace(nbytes, x.device, "simce")
-    check(lib.clipk_simce_grad_scaled(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), label_offset,
-                                      lse_x.data_ptr(), lse_y.data_ptr(), float(w_row), float(w_col), float(inv_bg),
-                                      ptr(upstream), dx.data_ptr(), dsc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-          "clipk_simce_grad_scaled")
-    return dx, dsc
+    return _simce("clipk_simce_grad_scaled", "plain", x, y, scale, cache,
+                  (label_offset, lse_x.data_ptr(), lse_y.data_ptr(), float(w_row), float(w_col), float(inv_bg),
+                   ptr(upstream)), _grad_outs(x))
 
 
 def _cls_args(x, y, scale, cache, cls_x, cls_y, same_class, eps, vectors=()):
@@ -341,50 +353,30 @@ def _cls_args(x, y, scale, cache, cls_x, cls_y, same_class, eps, vectors=()):
         raise ValueError(f"same_class must be one of {tuple(_ffi.SAME_CLASS)}, got {same_class!r}")
     if not 0.0 <= float(eps) < 1.0:
         raise ValueError(f"eps must be in [0, 1), got {eps}")
-    return Mx, Ny, P, 0 if cache is None else cache.shape[0]
 
 
 def simce_lse_cls(x, y, scale, cls_x=None, cls_y=None, same_class="mask", eps=0.0, label_offset=0, cache=None):
     """Class-aware LSE pass (include/clipk.h: clipk_simce_lse_cls): (lse, tgt, cnt), each f32 [Mx].  cls_x [Mx] /
     cls_y [Ny]: device int64 class ids, both or neither (None: all distinct); the cache rows carry no class."""
-    Mx, Ny, P, Nc = _cls_args(x, y, scale, cache, cls_x, cls_y, same_class, eps)
+    _cls_args(x, y, scale, cache, cls_x, cls_y, same_class, eps)
     _need_cuda(x, y, scale, cache, cls_x, cls_y)
-    lse = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    tgt = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    cnt = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    lib = _lib()
-    nbytes = lib.clipk_simce_cls_workspace(Mx, Ny + Nc, P)
-    if nbytes == 0:
-        raise _ffi.ClipkError(f"simce (class-aware): unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
-    ws = workspace(nbytes, x.device, "simce")
-    check(lib.clipk_simce_lse_cls(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), label_offset,
-                                  ptr(cls_x), ptr(cls_y), _ffi.SAME_CLASS[same_class], float(eps), lse.data_ptr(),
-                                  tgt.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-          "clipk_simce_lse_cls")
-    return lse, tgt, cnt
+    return _simce("clipk_simce_lse_cls", "cls", x, y, scale, cache,
+                  (label_offset, ptr(cls_x), ptr(cls_y), _ffi.SAME_CLASS[same_class], float(eps)),
+                  ((torch.empty, (x.shape[0],)),) * 3)
 
 
 def simce_grad_cls(x, y, scale, lse_x, lse_y, cnt_x, cnt_y, w_row, w_col, inv_bg, nkeys_y, cls_x=None, cls_y=None,
                    same_class="mask", eps=0.0, label_offset=0, cache=None, upstream=None):
     """Class-aware gradient pass (include/clipk.h: clipk_simce_grad_cls): (dx, dscale partials).  nkeys_y: the key
     count of the column direction (its rows' denominator before masking)."""
-    Mx, Ny, P, Nc = _cls_args(x, y, scale, cache, cls_x, cls_y, same_class, eps,
-                              (("lse_x", lse_x, x.shape[0]), ("lse_y", lse_y, y.shape[0]), ("cnt_x", cnt_x, x.shape[0]),
-                               ("cnt_y", cnt_y, y.shape[0]), ("upstream", upstream, 1)))
+    _cls_args(x, y, scale, cache, cls_x, cls_y, same_class, eps,
+              (("lse_x", lse_x, x.shape[0]), ("lse_y", lse_y, y.shape[0]), ("cnt_x", cnt_x, x.shape[0]),
+               ("cnt_y", cnt_y, y.shape[0]), ("upstream", upstream, 1)))
     _need_cuda(x, y, scale, lse_x, lse_y, cnt_x, cnt_y, cls_x, cls_y, cache, upstream)
-    dx = torch.empty_like(x)
-    dsc = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    lib = _lib()
-    nbytes = lib.clipk_simce_cls_workspace(Mx, Ny + Nc, P)
-    if nbytes == 0:
-        raise _ffi.ClipkError(f"simce (class-aware): unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
-    ws = workspace(nbytes, x.device, "simce")
-    check(lib.clipk_simce_grad_cls(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), label_offset,
-                                   lse_x.data_ptr(), lse_y.data_ptr(), ptr(cnt_x), ptr(cnt_y), ptr(cls_x), ptr(cls_y),
-                                   _ffi.SAME_CLASS[same_class], float(eps), int(nkeys_y), float(w_row), float(w_col),
-                                   float(inv_bg), ptr(upstream), dx.data_ptr(), dsc.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   _stream()), "clipk_simce_grad_cls")
-    return dx, dsc
+    return _simce("clipk_simce_grad_cls", "cls", x, y, scale, cache,
+                  (label_offset, lse_x.data_ptr(), lse_y.data_ptr(), ptr(cnt_x), ptr(cnt_y), ptr(cls_x), ptr(cls_y),
+                   _ffi.SAME_CLASS[same_class], float(eps), int(nkeys_y), float(w_row), float(w_col), float(inv_bg),
+                   ptr(upstream)), _grad_outs(x))
 
 
 def _hard_beta(beta) -> float:
@@ -397,46 +389,28 @@ def simce_lse_hard(x, y, scale, beta, cls_x=None, cls_y=None, label_offset=0, ca
     """Hard-negative-weighted LSE pass (include/clipk.h: clipk_simce_lse_hard): (lse_h, pos, coef); lse_h, pos f32
     [Mx], coef f32 [3, Mx] = (q, k1, k2), the per-row coefficients of simce_grad_hard.  cls_x [Mx] / cls_y [Ny]: device
     int64 class ids, both or neither (None: all distinct); same-class batch keys leave the negatives, cache rows never."""
-    Mx, Ny, P, Nc = _cls_args(x, y, scale, cache, cls_x, cls_y, "mask", 0.0)
+    _cls_args(x, y, scale, cache, cls_x, cls_y, "mask", 0.0)
     beta = _hard_beta(beta)
     _need_cuda(x, y, scale, cache, cls_x, cls_y)
-    lse = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    pos = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    coef = torch.empty(3, Mx, dtype=torch.float32, device=x.device)
-    lib = _lib()
-    nbytes = lib.clipk_simce_hard_workspace(Mx, Ny + Nc, P)
-    if nbytes == 0:
-        raise _ffi.ClipkError(f"simce (hard-negative): unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
-    ws = workspace(nbytes, x.device, "simce")
-    check(lib.clipk_simce_lse_hard(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), beta,
-                                   label_offset, ptr(cls_x), ptr(cls_y), lse.data_ptr(), pos.data_ptr(), coef.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), _stream()), "clipk_simce_lse_hard")
-    return lse, pos, coef
+    Mx = x.shape[0]
+    return _simce("clipk_simce_lse_hard", "hard", x, y, scale, cache, (beta, label_offset, ptr(cls_x), ptr(cls_y)),
+                  ((torch.empty, (Mx,)), (torch.empty, (Mx,)), (torch.empty, (3, Mx))))
 
 
 def simce_grad_hard(x, y, scale, beta, coef_x, coef_y, w_row, w_col, inv_bg, cls_x=None, cls_y=None, label_offset=0,
                     cache=None, upstream=None):
     """Hard-negative-weighted gradient pass (include/clipk.h: clipk_simce_grad_hard): (dx, dscale partials).  coef_x
     [3, Mx]: simce_lse_hard's coefficients of the rows; coef_y [3, Ny]: those of every batch key's own direction."""
-    Mx, Ny, P, Nc = _cls_args(x, y, scale, cache, cls_x, cls_y, "mask", 0.0, (("upstream", upstream, 1),))
+    _cls_args(x, y, scale, cache, cls_x, cls_y, "mask", 0.0, (("upstream", upstream, 1),))
     beta = _hard_beta(beta)
-    for name, t, n in (("coef_x", coef_x, Mx), ("coef_y", coef_y, Ny)):
+    for name, t, n in (("coef_x", coef_x, x.shape[0]), ("coef_y", coef_y, y.shape[0])):
         if t.dtype != torch.float32 or tuple(t.shape) != (3, n) or not t.is_contiguous():
             raise ValueError(f"{name} must be a contiguous float32 tensor of shape (3, {n}), got {t.dtype} "
                              f"{tuple(t.shape)}")
     _need_cuda(x, y, scale, coef_x, coef_y, cls_x, cls_y, cache, upstream)
-    dx = torch.empty_like(x)
-    dsc = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    lib = _lib()
-    nbytes = lib.clipk_simce_hard_workspace(Mx, Ny + Nc, P)
-    if nbytes == 0:
-        raise _ffi.ClipkError(f"simce (hard-negative): unsupported shape Mx={Mx} Nkeys={Ny + Nc} P={P}")
-    ws = workspace(nbytes, x.device, "simce")
-    check(lib.clipk_simce_grad_hard(x.data_ptr(), Mx, y.data_ptr(), Ny, ptr(cache), Nc, P, scale.data_ptr(), beta,
-                                    label_offset, coef_x.data_ptr(), coef_y.data_ptr(), ptr(cls_x), ptr(cls_y),
-                                    float(w_row), float(w_col), float(inv_bg), ptr(upstream), dx.data_ptr(),
-                                    dsc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipk_simce_grad_hard")
-    return dx, dsc
+    return _simce("clipk_simce_grad_hard", "hard", x, y, scale, cache,
+                  (beta, label_offset, coef_x.data_ptr(), coef_y.data_ptr(), ptr(cls_x), ptr(cls_y), float(w_row),
+                   float(w_col), float(inv_bg), ptr(upstream)), _grad_outs(x))
 
 
 def _pairs_arrays(pairs):

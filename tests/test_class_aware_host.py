@@ -7,35 +7,17 @@ the column direction's key counts): distributed loss and gradients == the single
 """
 import os
 import sys
-import tempfile
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import class_aware_ref as R  # noqa: E402
-
-
-def _install(set_attr=setattr):
-    sys.path[:0] = [ROOT, HERE]
-    import ops_emulator
-    from clip_dplm_amd import ops
-    for n in ops_emulator._NAMES:
-        if hasattr(ops, n) and n != "KernelTimer":
-            set_attr(ops, n, getattr(ops_emulator, n))
-    set_attr(ops, "simce_lse_cls", R.simce_lse_cls)
-    set_attr(ops, "simce_grad_cls", R.simce_grad_cls)
-
-
-def _unit(n, p, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.nn.functional.normalize(torch.randn(n, p, generator=g, dtype=torch.float64), dim=-1).float()
+from host_harness import (clip_loss_cases, install as _install, run_ranks, spy_gathers, trap_calls,  # noqa: E402
+                          unit as _unit)
 
 
 def _reference(a, b, s, ids, same_class, eps, symmetric):
@@ -108,17 +90,8 @@ def test_class_aware_ops_check_their_operands():
 
 def test_default_call_never_reaches_class_aware_ops(monkeypatch):
     _install(monkeypatch.setattr)
-    from clip_dplm_amd import ops
     from clip_dplm_amd.loss import clip_loss
-    calls = []
-
-    def trap(name):
-        def f(*args, **kw):
-            calls.append(name)
-            return getattr(R, name)(*args, **kw)
-        return f
-    monkeypatch.setattr(ops, "simce_lse_cls", trap("simce_lse_cls"))
-    monkeypatch.setattr(ops, "simce_grad_cls", trap("simce_grad_cls"))
+    calls = trap_calls(monkeypatch.setattr, ("simce_lse_cls", "simce_grad_cls"))
     a0, b0 = _unit(24, 16, 5), _unit(24, 16, 6)
     for kw in (dict(), dict(same_class="positive"), dict(class_ids=None, label_smoothing=0.0)):
         a, b = a0.clone().requires_grad_(True), b0.clone().requires_grad_(True)
@@ -142,47 +115,16 @@ def test_default_call_never_reaches_class_aware_ops(monkeypatch):
 CASES = (("mask", 0.1, True), ("positive", 0.0, True), ("positive", 0.1, False))
 
 
-def _worker(rank, world, initfile, results):
-    torch.set_num_threads(1)
-    _install()
-    dist.init_process_group("gloo", init_method=f"file://{initfile}", rank=rank, world_size=world)
-    try:
-        from clip_dplm_amd import loss as L
-        gathered = []
-        plain_gather = L._gather_cat
-
-        def spy(t, group):
-            gathered.append(t.dtype)
-            return plain_gather(t, group)
-        L._gather_cat = spy
-        Bl, P = 12, 16
-        a_g, b_g = _unit(world * Bl, P, 1), _unit(world * Bl, P, 2)
-        ids_g = torch.arange(world * Bl) % 5                         # every class has members on both ranks
-        sl = slice(rank * Bl, (rank + 1) * Bl)
-        out = {}
-        for k, (same_class, eps, symmetric) in enumerate(CASES):
-            gathered.clear()
-            a = a_g[sl].clone().requires_grad_(True)
-            b = b_g[sl].clone().requires_grad_(True)
-            s = torch.tensor(14.2849, requires_grad=True)
-            loss = L.clip_loss(a, b, s, symmetric=symmetric, group=dist.group.WORLD, class_ids=ids_g[sl].clone(),
-                               same_class=same_class, label_smoothing=eps)
-            loss.backward()
-            out[k] = (loss.item(), a.grad.clone(), b.grad.clone(), s.grad.clone(), list(gathered))
-        results[rank] = out
-    finally:
-        dist.destroy_process_group()
+def _rank_body(rank, world):
+    from clip_dplm_amd import loss as L
+    cases = [(True, False, dict(same_class=c, label_smoothing=eps, symmetric=sym)) for c, eps, sym in CASES]
+    return clip_loss_cases(cases, spy_gathers(L), rank, world)
 
 
 @pytest.mark.timeout(300)
 def test_world2_class_aware_matches_single_process():
     world, Bl, P = 2, 12, 16
-    mp.set_sharing_strategy("file_system")
-    with tempfile.TemporaryDirectory() as d:
-        mgr = mp.Manager()
-        results = mgr.dict()
-        mp.spawn(_worker, args=(world, os.path.join(d, "init"), results), nprocs=world, join=True)
-        res = [results[r] for r in range(world)]
+    res = run_ranks(_rank_body, world)
     a, b = _unit(world * Bl, P, 1), _unit(world * Bl, P, 2)
     ids = torch.arange(world * Bl) % 5
     for k, (same_class, eps, symmetric) in enumerate(CASES):
@@ -192,7 +134,7 @@ def test_world2_class_aware_matches_single_process():
         ds = 0.0
         for r in range(world):
             loss, da, db, dsr, gathered = res[r][k]
-            assert gathered == [torch.float32, torch.int64, torch.float32], gathered   # embeddings, ids, LSE + counts
+            assert [dt for dt, _ in gathered] == [torch.float32, torch.int64, torch.float32]   # embeds, ids, LSE + counts
             assert abs(loss - L) < 1e-5, (k, r, loss, L)                               # the global loss on every rank
             sl = slice(r * Bl, (r + 1) * Bl)
             assert torch.allclose(da.double(), ga[sl], atol=1e-6), (k, r)

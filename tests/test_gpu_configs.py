@@ -164,7 +164,7 @@ def test_c3_simce_rank_block_vs_f64(dev, rank, Bl):
 
 
 def test_c3_global_loss_from_8_virtual_ranks(dev):
-    """The whole config-3 loss assembled the way loss.ClipLossFn does per rank (row + column LSE of each rank's 512
+    """The whole config-3 loss assembled the way loss.InfoNCEFn does per rank (row + column LSE of each rank's 512
     pairs against the 4096 gathered keys), summed over 8 virtual ranks == f64 symmetric CE of the 4096 x 4096 logits."""
     from clip_dplm_amd import ops
     Bl, W, P, scale = 512, 8, 512, 14.2849

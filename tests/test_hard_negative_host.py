@@ -9,41 +9,20 @@ rows gathered once).
 """
 import os
 import sys
-import tempfile
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 import torch.nn.functional as F
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import hard_negative_ref as R  # noqa: E402
+from host_harness import (clip_loss_cases, install as _install, run_ranks, spy_gathers, trap_calls,  # noqa: E402
+                          unit as _unit)
 
 SCALE = 14.2849
-
-
-def _install(set_attr=setattr):
-    sys.path[:0] = [ROOT, HERE]
-    import ops_emulator
-    from clip_dplm_amd import ops
-    for n in ops_emulator._NAMES:
-        if hasattr(ops, n) and n != "KernelTimer":
-            set_attr(ops, n, getattr(ops_emulator, n))
-    import class_aware_ref
-    set_attr(ops, "simce_lse_cls", class_aware_ref.simce_lse_cls)
-    set_attr(ops, "simce_grad_cls", class_aware_ref.simce_grad_cls)
-    set_attr(ops, "simce_lse_hard", R.simce_lse_hard)
-    set_attr(ops, "simce_grad_hard", R.simce_grad_hard)
-
-
-def _unit(n, p, seed, dtype=torch.float32):
-    g = torch.Generator().manual_seed(seed)
-    return F.normalize(torch.randn(n, p, generator=g, dtype=torch.float64), dim=-1).to(dtype)
 
 
 def _case(Mx=48, Ny=56, Nc=12, P=24, off=5, classes=7, seed=0):
@@ -109,7 +88,7 @@ def test_ref_closed_form_gradient_equals_autograd(beta):
 
 
 def test_ref_standins_give_autograd_of_global_loss():
-    """The two stand-ins chained as loss.HardNegativeClipLossFn chains the kernels: G of both directions, dX, dscale."""
+    """The two stand-ins chained as loss.InfoNCEFn chains the hard-negative kernels: G of both directions, dX, dscale."""
     B, Nc, P, beta = 40, 9, 16, 0.5
     a, b, cache = _unit(B, P, 1, torch.float64), _unit(B, P, 2, torch.float64), _unit(Nc, P, 3, torch.float64)
     ids = torch.arange(B) % 6
@@ -234,17 +213,8 @@ def _reference(a, b, s, ids, beta, symmetric, cache=None):
 
 def test_beta0_never_reaches_hard_ops_and_beta_does(monkeypatch):
     _install(monkeypatch.setattr)
-    from clip_dplm_amd import ops
     from clip_dplm_amd.loss import clip_loss, contrastive_loss
-    calls = []
-
-    def trap(name):
-        def f(*args, **kw):
-            calls.append(name)
-            return getattr(R, name)(*args, **kw)
-        return f
-    monkeypatch.setattr(ops, "simce_lse_hard", trap("simce_lse_hard"))
-    monkeypatch.setattr(ops, "simce_grad_hard", trap("simce_grad_hard"))
+    calls = trap_calls(monkeypatch.setattr, ("simce_lse_hard", "simce_grad_hard"))
     a0, b0 = _unit(24, 16, 5), _unit(24, 16, 6)
     ids = torch.tensor([0, 1, 2] * 8)
     for kw in (dict(), dict(hard_negative_beta=0.0), dict(hard_negative_beta=0, class_ids=ids),
@@ -279,47 +249,16 @@ def test_beta0_never_reaches_hard_ops_and_beta_does(monkeypatch):
 CASES = ((True, 0.5, True), (False, 1.0, True), (True, 0.5, False), (False, 0.5, False))      # (ids, beta, symmetric)
 
 
-def _worker(rank, world, initfile, results):
-    torch.set_num_threads(1)
-    _install()
-    dist.init_process_group("gloo", init_method=f"file://{initfile}", rank=rank, world_size=world)
-    try:
-        from clip_dplm_amd import loss as L
-        gathered = []
-        plain_gather = L._gather_cat
-
-        def spy(t, group):
-            gathered.append((t.dtype, tuple(t.shape)))
-            return plain_gather(t, group)
-        L._gather_cat = spy
-        Bl, P = 12, 16
-        a_g, b_g = _unit(world * Bl, P, 1), _unit(world * Bl, P, 2)
-        ids_g = torch.arange(world * Bl) % 5                         # every class has members on both ranks
-        sl = slice(rank * Bl, (rank + 1) * Bl)
-        out = {}
-        for k, (with_ids, beta, symmetric) in enumerate(CASES):
-            gathered.clear()
-            a = a_g[sl].clone().requires_grad_(True)
-            b = b_g[sl].clone().requires_grad_(True)
-            s = torch.tensor(SCALE, requires_grad=True)
-            loss = L.clip_loss(a, b, s, symmetric=symmetric, group=dist.group.WORLD,
-                               class_ids=ids_g[sl].clone() if with_ids else None, hard_negative_beta=beta)
-            loss.backward()
-            out[k] = (loss.item(), a.grad.clone(), b.grad.clone(), s.grad.clone(), list(gathered))
-        results[rank] = out
-    finally:
-        dist.destroy_process_group()
+def _rank_body(rank, world):
+    from clip_dplm_amd import loss as L
+    cases = [(with_ids, False, dict(hard_negative_beta=beta, symmetric=sym)) for with_ids, beta, sym in CASES]
+    return clip_loss_cases(cases, spy_gathers(L), rank, world)
 
 
 @pytest.mark.timeout(300)
 def test_world2_hard_negative_matches_single_process():
     world, Bl, P = 2, 12, 16
-    mp.set_sharing_strategy("file_system")
-    with tempfile.TemporaryDirectory() as d:
-        mgr = mp.Manager()
-        results = mgr.dict()
-        mp.spawn(_worker, args=(world, os.path.join(d, "init"), results), nprocs=world, join=True)
-        res = [results[r] for r in range(world)]
+    res = run_ranks(_rank_body, world)
     a, b = _unit(world * Bl, P, 1), _unit(world * Bl, P, 2)
     ids = torch.arange(world * Bl) % 5
     for k, (with_ids, beta, symmetric) in enumerate(CASES):
