@@ -73,6 +73,16 @@ SIGNATURES = {
     "clipk_simce_lse_pairs": (_i, [_vp, _i, _i, _i, C.POINTER(_i), _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_simce_grad_pairs": (_i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _vp, _f, _f, _f, _vp, _vp,
                                     _vp, _sz, _vp]),
+    "clipk_simce_pairs_cls_workspace": (_sz, [_i, _i, _i]),
+    "clipk_simce_lse_pairs_cls": (_i, [_vp, _i, _i, _i, C.POINTER(_i), _i, _vp, C.POINTER(_vp), _i, _f, _vp, _vp, _vp, _vp,
+                                       _sz, _vp]),
+    "clipk_simce_grad_pairs_cls": (_i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, C.POINTER(_vp), _i, _f, _vp,
+                                        _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_simce_pairs_hard_workspace": (_sz, [_i, _i, _i]),
+    "clipk_simce_lse_pairs_hard": (_i, [_vp, _i, _i, _i, C.POINTER(_i), _i, _vp, _f, C.POINTER(_vp), _vp, _vp, _vp, _vp,
+                                        _sz, _vp]),
+    "clipk_simce_grad_pairs_hard": (_i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _f, C.POINTER(_vp), _vp,
+                                         _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_sim_logits": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i64, _vp]),
     "clipk_sim_topk_workspace": (_sz, [_i, _i, _i, _i]),
     "clipk_sim_topk": (_i, [_vp, _i, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -288,3 +288,15 @@ static inline void clipk_once_per_device(std::atomic<uint64_t>& mask, F&& f) {
   }
 }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// ---- problem table of the batched class-aware / hard-negative similarity launches (simce_tiled.hip, simce_hard.hip;
+// blockIdx.z = problem): same-shape problems X = E[xa[z]], Y = E[ya[z]] over E [nmod][B][P], one id vector per problem
+// (null: all distinct) for its queries and its keys, rev[z] = the problem with X and Y exchanged (whose statistics are
+// those of this problem's keys).  nz == 0: the single problem the kernel's other arguments describe.
+constexpr int CLIPK_PAIRZ_MAX = 6;
+struct PairZ {
+  int nz;
+  int xa[CLIPK_PAIRZ_MAX], ya[CLIPK_PAIRZ_MAX], rev[CLIPK_PAIRZ_MAX];
+  const int64_t* ids[CLIPK_PAIRZ_MAX];
+  const float* E;
+};

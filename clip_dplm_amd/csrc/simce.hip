@@ -291,6 +291,9 @@ __global__ __launch_bounds__(256) void simce_lse_finalize_cls(const float* part_
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= Mx) return;
+  part_ml += (long)blockIdx.y * ksplit * Mx * 2;  // batched launch: blockIdx.y = problem
+  part_t += (long)blockIdx.y * ksplit * Mx * 3;
+  lse += (long)blockIdx.y * Mx; tgt += (long)blockIdx.y * Mx; cnt += (long)blockIdx.y * Mx;
   float m = -INFINITY;
   for (int s = lane; s < ksplit; s += 64) m = fmaxf(m, part_ml[((long)s * Mx + i) * 2]);
   m = wave_max(m);
@@ -777,6 +780,142 @@ extern "C" int clipk_simce_grad_pairs(const float* E, int nmod, int B, int P, co
                      (const float*)sp.slab, (const float*)sp.dsc_part, pl.ksplit, B, P, scale, dX, dscale_partial,
                      z_slab, z_dsc);
   return clipk_check_launch();
+}
+
+// ---- the batched form of the class-aware and the hard-negative pair (clipk_simce_{lse,grad}_pairs_{cls,hard}): the
+// tiled kernels with a problem index (simce_tiled.hip, simce_hard.hip), one launch per pass plus one finalize, the key
+// splits of clipk_simce_pairs_tiled_plan (chosen for the whole grid)
+extern "C" void clipk_simce_pairs_tiled_plan(int npairs, int B, int* nqb, int* ksplit, int* tps, int* ntiles);
+extern "C" int clipk_simce_lse_tiled_pairs_cls_launch(const PairZ* zt, int B, int P, const float* scale, int same_positive,
+                                                      float* part_ml, float* part_t, float* pos, void* stream);
+extern "C" int clipk_simce_grad_tiled_pairs_cls_launch(const PairZ* zt, int B, int P, const float* scale, const float* lse,
+                                                       const float* cnt, int same_positive, float eps, float w_row,
+                                                       float w_col, float inv_bg, const float* upstream, float* slab,
+                                                       float* dsc_part, void* stream);
+extern "C" int clipk_simce_lse_pairs_hard_launch(const PairZ* zt, int B, int P, const float* scale, float beta, float* part,
+                                                 float* lse_h, float* pos, float* coef, void* stream);
+extern "C" int clipk_simce_grad_pairs_hard_launch(const PairZ* zt, int B, int P, const float* scale, float beta,
+                                                  const float* coef, float w_row, float w_col, float inv_bg,
+                                                  const float* upstream, float* slab, float* dsc_part, void* stream);
+
+// lse_floats: partial floats per (split, row) of the LSE pass (5 class-aware, 4 hard-negative)
+static size_t pairs_tiled_workspace(int npairs, int B, int P, int lse_floats) {
+  if (npairs <= 0 || npairs > MAXZ || !cls_shape_ok(B, B, P)) return 0;
+  int nqb, ks, tps, nt;
+  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  const size_t a = (size_t)npairs * ks * B * lse_floats * sizeof(float);
+  const size_t c = (size_t)npairs * ks * B * ((size_t)P + 1) * sizeof(float);      // dX slabs + dscale partials
+  return a > c ? a : c;
+}
+extern "C" size_t clipk_simce_pairs_cls_workspace(int npairs, int B, int P) { return pairs_tiled_workspace(npairs, B, P, 5); }
+extern "C" size_t clipk_simce_pairs_hard_workspace(int npairs, int B, int P) { return pairs_tiled_workspace(npairs, B, P, 4); }
+
+// the problem table from the host arrays; reverse == nullptr: the LSE pass, which does not read it.  A problem and its
+// reverse are the two directions of one pair: they carry one id vector (`same` must be symmetric).
+static int pairs_table(const float* E, int nmod, int B, int P, const int* pairs, const int* reverse, int npairs,
+                       const int64_t* const* ids, PairZ* zt) {
+  if (!E || !pairs || !ids || npairs <= 0 || npairs > MAXZ || nmod <= 0) return CLIPK_ERR_BAD_ARG;
+  if (!cls_shape_ok(B, B, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (!aligned16(E)) return CLIPK_ERR_BAD_ARG;
+  *zt = PairZ{};
+  zt->nz = npairs; zt->E = E;
+  for (int i = 0; i < npairs; ++i) {
+    const int a = pairs[2 * i], b = pairs[2 * i + 1];
+    if (a < 0 || a >= nmod || b < 0 || b >= nmod) return CLIPK_ERR_BAD_ARG;
+    zt->xa[i] = a; zt->ya[i] = b; zt->ids[i] = ids[i];
+    if (reverse) {
+      const int r = reverse[i];
+      if (r < 0 || r >= npairs || ids[r] != ids[i]) return CLIPK_ERR_BAD_ARG;
+      zt->rev[i] = r;
+    }
+  }
+  return CLIPK_OK;
+}
+
+static int pairs_grad_finalize(const float* slab, const float* dscp, int npairs, int ks, int B, int P, const float* scale,
+                               float* dX, float* dscale_partial, void* stream) {
+  long n4 = (long)B * P / 4;
+  int blocks = (int)((n4 + 63) / 64); if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(simce_grad_finalize, dim3(blocks, npairs), dim3(256), 0, (hipStream_t)stream, slab, dscp, ks, B, P,
+                     scale, dX, dscale_partial, (long)ks * B * P, (long)ks * B);
+  return clipk_check_launch();
+}
+
+extern "C" int clipk_simce_lse_pairs_cls(const float* E, int nmod, int B, int P, const int* pairs, int npairs,
+                                         const float* scale, const int64_t* const* ids, int same_class, float eps,
+                                         float* lse, float* tgt, float* cnt, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  if (!scale || !lse || !tgt || !cnt || !workspace) return CLIPK_ERR_BAD_ARG;
+  if (!cls_args_ok(nullptr, nullptr, same_class, eps)) return CLIPK_ERR_BAD_ARG;
+  PairZ zt;
+  int rc = pairs_table(E, nmod, B, P, pairs, nullptr, npairs, ids, &zt);
+  if (rc) return rc;
+  int nqb, ks, tps, nt;
+  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  if (workspace_bytes < (size_t)npairs * ks * B * 5 * sizeof(float)) return CLIPK_ERR_BAD_ARG;
+  float* part_ml = (float*)workspace;
+  float* part_t = part_ml + (size_t)npairs * ks * B * 2;
+  const int positive = same_class == CLIPK_SAME_CLASS_POSITIVE;
+  rc = clipk_simce_lse_tiled_pairs_cls_launch(&zt, B, P, scale, positive, part_ml, part_t, tgt, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(simce_lse_finalize_cls, dim3((B + 3) / 4, npairs), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)part_ml, (const float*)part_t, ks, B, B, positive, eps, lse, tgt, cnt);
+  return clipk_check_launch();
+}
+
+extern "C" int clipk_simce_grad_pairs_cls(const float* E, int nmod, int B, int P, const int* pairs, const int* reverse,
+                                          int npairs, const float* scale, const int64_t* const* ids, int same_class,
+                                          float eps, const float* lse, const float* cnt, float w_row, float w_col,
+                                          float inv_bg, const float* upstream, float* dX, float* dscale_partial,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  if (!reverse || !scale || !lse || !cnt || !dX || !workspace) return CLIPK_ERR_BAD_ARG;
+  if (!cls_args_ok(nullptr, nullptr, same_class, eps)) return CLIPK_ERR_BAD_ARG;
+  PairZ zt;
+  int rc = pairs_table(E, nmod, B, P, pairs, reverse, npairs, ids, &zt);
+  if (rc) return rc;
+  if (!aligned16(dX) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
+  int nqb, ks, tps, nt;
+  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  if (workspace_bytes < (size_t)npairs * ks * B * ((size_t)P + 1) * sizeof(float)) return CLIPK_ERR_BAD_ARG;
+  float* slab = (float*)workspace;
+  float* dscp = slab + (size_t)npairs * ks * B * P;
+  rc = clipk_simce_grad_tiled_pairs_cls_launch(&zt, B, P, scale, lse, cnt, same_class == CLIPK_SAME_CLASS_POSITIVE, eps,
+                                               w_row, w_col, inv_bg, upstream, slab, dscp, stream);
+  if (rc) return rc;
+  return pairs_grad_finalize(slab, dscp, npairs, ks, B, P, scale, dX, dscale_partial, stream);
+}
+
+extern "C" int clipk_simce_lse_pairs_hard(const float* E, int nmod, int B, int P, const int* pairs, int npairs,
+                                          const float* scale, float beta, const int64_t* const* ids, float* lse_h,
+                                          float* pos, float* coef, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!scale || !lse_h || !pos || !coef || !workspace || !hard_beta_ok(beta)) return CLIPK_ERR_BAD_ARG;
+  PairZ zt;
+  int rc = pairs_table(E, nmod, B, P, pairs, nullptr, npairs, ids, &zt);
+  if (rc) return rc;
+  int nqb, ks, tps, nt;
+  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  if (workspace_bytes < (size_t)npairs * ks * B * 4 * sizeof(float)) return CLIPK_ERR_BAD_ARG;
+  return clipk_simce_lse_pairs_hard_launch(&zt, B, P, scale, beta, (float*)workspace, lse_h, pos, coef, stream);
+}
+
+extern "C" int clipk_simce_grad_pairs_hard(const float* E, int nmod, int B, int P, const int* pairs, const int* reverse,
+                                           int npairs, const float* scale, float beta, const int64_t* const* ids,
+                                           const float* coef, float w_row, float w_col, float inv_bg,
+                                           const float* upstream, float* dX, float* dscale_partial, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+  if (!reverse || !scale || !coef || !dX || !workspace || !hard_beta_ok(beta)) return CLIPK_ERR_BAD_ARG;
+  PairZ zt;
+  int rc = pairs_table(E, nmod, B, P, pairs, reverse, npairs, ids, &zt);
+  if (rc) return rc;
+  if (!aligned16(dX) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
+  int nqb, ks, tps, nt;
+  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  if (workspace_bytes < (size_t)npairs * ks * B * ((size_t)P + 1) * sizeof(float)) return CLIPK_ERR_BAD_ARG;
+  float* slab = (float*)workspace;
+  float* dscp = slab + (size_t)npairs * ks * B * P;
+  rc = clipk_simce_grad_pairs_hard_launch(&zt, B, P, scale, beta, coef, w_row, w_col, inv_bg, upstream, slab, dscp, stream);
+  if (rc) return rc;
+  return pairs_grad_finalize(slab, dscp, npairs, ks, B, P, scale, dX, dscale_partial, stream);
 }
 
 extern "C" int clipk_sim_logits(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale,

@@ -33,6 +33,7 @@ struct HLP {
   float* pos;          // [Mx]
   int tiles_per_split, ntiles;
   const int64_t* cls_x; const int64_t* cls_y;   // [Mx] / [Ny] class ids, or both null (all distinct)
+  PairZ z;                                      // batched launch: part / pos hold the problems one after another
 };
 
 // (m, a, c) <- merge with (mo, ao, co); an empty side has m = -inf and zero sums (selected out: 0 * -inf at beta = 0)
@@ -46,7 +47,17 @@ __device__ __forceinline__ void hard_merge(float& m, float& a, float& c, float m
   m = mn; a = an; c = cn;
 }
 
-__global__ __launch_bounds__(256, 2) void simce_lse_hard_kernel(const HLP p) {
+// ZB: the batched launch, blockIdx.z = problem of p.z; the single-problem instantiation has none of its code
+template <bool ZB>
+__global__ __launch_bounds__(256, 2) void simce_lse_hard_kernel(const HLP pa) {
+  HLP p = pa;
+  if constexpr (ZB) {                                                     // this workgroup's problem
+    const int z = blockIdx.z;
+    p.X = pa.z.E + (long)pa.z.xa[z] * p.Mx * p.P;
+    p.Y = p.Yc = pa.z.E + (long)pa.z.ya[z] * p.Ny * p.P;
+    p.cls_x = p.cls_y = pa.z.ids[z];
+    p.part += (long)z * gridDim.y * p.Mx * 4; p.pos += (long)z * p.Mx;
+  }
   constexpr int BKL = 32;
   __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (BKL + 4)];   // 2 buffers x (keys | queries)
   __shared__ float mrg[4][TQ];                                            // key-wave 1's m | a | c | n per query
@@ -146,6 +157,8 @@ __global__ __launch_bounds__(256) void simce_lse_hard_finalize(const float* part
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= Mx) return;
+  part += (long)blockIdx.y * ksplit * Mx * 4;     // batched launch: blockIdx.y = problem
+  pos += (long)blockIdx.y * Mx; lse_h += (long)blockIdx.y * Mx; coef += (long)blockIdx.y * 3 * Mx;
   const float b1 = 1.f + beta;
   float m = -INFINITY;
   for (int s = lane; s < ksplit; s += 64) m = fmaxf(m, part[((long)s * Mx + i) * 4]);
@@ -194,6 +207,9 @@ struct HGP {
   float* dsc_part;     // [ksplit][Mx]
   int tiles_per_split, ntiles;
   const int64_t* cls_x; const int64_t* cls_y;
+  // batched launch: coef_x = coef_y = coef [nz][3][Mx], upstream [nz] (or null), slab and dsc_part hold the problems one
+  // after another
+  PairZ z;
 };
 
 constexpr int GPMAX = 512;                         // contraction / output width limit
@@ -202,7 +218,19 @@ constexpr int KSB = 16;                            // keys per staged block of t
 constexpr int BKG = 16;                            // K-step of the S tile (LDS budget: 2 workgroups per CU)
 constexpr int GRAD_LDS_FLOATS = 2 * 2 * 64 * (BKG + 4) + TK * TQ + KSB * YH_LD + 2 * TQ;
 
-__global__ __launch_bounds__(256, 2) void simce_grad_hard_kernel(const HGP p) {
+template <bool ZB>
+__global__ __launch_bounds__(256, 2) void simce_grad_hard_kernel(const HGP pa) {
+  HGP p = pa;
+  if constexpr (ZB) {                                                     // this workgroup's problem
+    const int z = blockIdx.z, r = pa.z.rev[z];
+    const long zs = (long)z * gridDim.y * p.Mx;                           // rows of key-split partials before it
+    p.X = pa.z.E + (long)pa.z.xa[z] * p.Mx * p.P;
+    p.Y = p.Yc = pa.z.E + (long)pa.z.ya[z] * p.Ny * p.P;
+    p.cls_x = p.cls_y = pa.z.ids[z];
+    p.coef_x = pa.coef_x + (long)z * 3 * p.Mx; p.coef_y = pa.coef_x + (long)r * 3 * p.Mx;   // the keys': the reverse problem's
+    if (pa.upstream) p.upstream = pa.upstream + z;
+    p.slab += zs * p.P; p.dsc_part += zs;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* smem = reinterpret_cast<float*>(smem_raw);                      // K-loop buffers
   float* gl = smem + 2 * 2 * 64 * (BKG + 4);                              // G tile [64 keys][64 queries]
@@ -341,6 +369,17 @@ __global__ __launch_bounds__(256, 2) void simce_grad_hard_kernel(const HGP p) {
 
 extern "C" void clipk_simce_tiled_plan(int Mx, int Nkeys, int* nqb, int* ksplit, int* tps, int* ntiles);
 extern "C" void clipk_simce_grad_tiled_plan(int Mx, int Nkeys, int* nqb, int* ksplit, int* tps, int* ntiles);
+extern "C" void clipk_simce_pairs_tiled_plan(int npairs, int B, int* nqb, int* ksplit, int* tps, int* ntiles);
+
+// the gradient kernel's 70 KiB of dynamic LDS, allowed once per device
+template <bool ZB>
+static void hard_grad_attr() {
+  static std::atomic<uint64_t> attr_set{0};
+  clipk_once_per_device(attr_set, [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(simce_grad_hard_kernel<ZB>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(GRAD_LDS_FLOATS * sizeof(float)));
+  });
+}
 
 // the tiled pass and its finalize; part: [ksplit][Mx][4] with ksplit of clipk_simce_tiled_plan
 extern "C" int clipk_simce_lse_hard_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
@@ -353,7 +392,7 @@ extern "C" int clipk_simce_lse_hard_launch(const float* X, int Mx, const float* 
   p.cls_x = cls_x; p.cls_y = cls_y;
   int nqb, ksplit;
   clipk_simce_tiled_plan(Mx, Ny + Nc, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
-  hipLaunchKernelGGL(simce_lse_hard_kernel, dim3(nqb, ksplit), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(simce_lse_hard_kernel<false>, dim3(nqb, ksplit), dim3(256), 0, (hipStream_t)stream, p);
   int rc = clipk_check_launch();
   if (rc) return rc;
   hipLaunchKernelGGL(simce_lse_hard_finalize, dim3((Mx + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)part,
@@ -375,12 +414,41 @@ extern "C" int clipk_simce_grad_hard_launch(const float* X, int Mx, const float*
   p.cls_x = cls_x; p.cls_y = cls_y;
   int nqb, ksplit;
   clipk_simce_grad_tiled_plan(Mx, Ny + Nc, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
-  const size_t lds = (size_t)GRAD_LDS_FLOATS * sizeof(float);
-  static std::atomic<uint64_t> attr_set{0};
-  clipk_once_per_device(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(simce_grad_hard_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
-  hipLaunchKernelGGL(simce_grad_hard_kernel, dim3(nqb, ksplit), dim3(256), lds, (hipStream_t)stream, p);
+  hard_grad_attr<false>();
+  hipLaunchKernelGGL(simce_grad_hard_kernel<false>, dim3(nqb, ksplit), dim3(256), (size_t)GRAD_LDS_FLOATS * sizeof(float),
+                     (hipStream_t)stream, p);
+  return clipk_check_launch();
+}
+
+// ---- batched launches (clipk_simce_{lse,grad}_pairs_hard): zt.nz problems of shape B x B over zt.E in one grid, the
+// splits of clipk_simce_pairs_tiled_plan; per-problem outputs and partials follow one another
+extern "C" int clipk_simce_lse_pairs_hard_launch(const PairZ* zt, int B, int P, const float* scale, float beta, float* part,
+                                                 float* lse_h, float* pos, float* coef, void* stream) {
+  HLP p{};
+  p.Mx = B; p.Ny = B; p.Nc = 0; p.P = P; p.scale = scale; p.label_offset = 0; p.beta = beta;
+  p.part = part; p.pos = pos; p.z = *zt;
+  int nqb, ksplit;
+  clipk_simce_pairs_tiled_plan(zt->nz, B, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  hipLaunchKernelGGL(simce_lse_hard_kernel<true>, dim3(nqb, ksplit, zt->nz), dim3(256), 0, (hipStream_t)stream, p);
+  int rc = clipk_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(simce_lse_hard_finalize, dim3((B + 3) / 4, zt->nz), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)part, ksplit, B, beta, (const float*)pos, lse_h, coef);
+  return clipk_check_launch();
+}
+
+extern "C" int clipk_simce_grad_pairs_hard_launch(const PairZ* zt, int B, int P, const float* scale, float beta,
+                                                  const float* coef, float w_row, float w_col, float inv_bg,
+                                                  const float* upstream, float* slab, float* dsc_part, void* stream) {
+  if (P > GPMAX) return CLIPK_ERR_UNSUPPORTED;
+  HGP p{};
+  p.Mx = B; p.Ny = B; p.Nc = 0; p.P = P; p.scale = scale; p.label_offset = 0; p.beta = beta;
+  p.coef_x = coef; p.coef_y = coef; p.w_row = w_row; p.w_col = w_col; p.inv_bg = inv_bg; p.upstream = upstream;
+  p.slab = slab; p.dsc_part = dsc_part; p.z = *zt;
+  int nqb, ksplit;
+  clipk_simce_pairs_tiled_plan(zt->nz, B, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  hard_grad_attr<true>();
+  hipLaunchKernelGGL(simce_grad_hard_kernel<true>, dim3(nqb, ksplit, zt->nz), dim3(256), (size_t)GRAD_LDS_FLOATS * sizeof(float),
+                     (hipStream_t)stream, p);
   return clipk_check_launch();
 }

@@ -26,6 +26,12 @@ namespace {
 
 constexpr int TQ = 64, TK = 64;                   // queries per workgroup, keys per tile
 
+// a * b as one rounded f32 product, never the first half of a contracted fma
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 struct LP {
   const float* X; int Mx;
   const float* Y; int Ny;
@@ -39,10 +45,21 @@ struct LP {
   const int64_t* cls_x; const int64_t* cls_y;   // [Mx] / [Ny] class ids, or both null (all distinct)
   int same_positive;                            // 0: same-class keys leave the denominator ("mask"), 1: they stay
   float* part_t;                                // [ksplit][Mx][3]: sum_{D_i} S, sum_{same} S, #same
+  PairZ z;                                      // batched launch: part_ml / part_t / pos hold the problems one after another
 };
 
-template <bool CLS>
-__global__ __launch_bounds__(256, 2) void simce_lse_tiled_kernel(const LP p) {
+// ZB (with CLS): the batched launch, blockIdx.z = problem of p.z; the single-problem instantiations have none of its code
+template <bool CLS, bool ZB = false>
+__global__ __launch_bounds__(256, 2) void simce_lse_tiled_kernel(const LP pa) {
+  LP p = pa;
+  if constexpr (ZB) {                                                     // this workgroup's problem
+    const int z = blockIdx.z;
+    const long zs = (long)z * gridDim.y * p.Mx;                           // rows of key-split partials before it
+    p.X = pa.z.E + (long)pa.z.xa[z] * p.Mx * p.P;
+    p.Y = p.Yc = pa.z.E + (long)pa.z.ya[z] * p.Ny * p.P;
+    p.cls_x = p.cls_y = pa.z.ids[z];
+    p.part_ml += zs * 2; p.part_t += zs * 3; p.pos += (long)z * p.Mx;
+  }
   constexpr int BKL = 32;                                                 // 16 MFMAs per wave between barriers
   __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (BKL + 4)];   // 2 buffers x (keys | queries)
   __shared__ float mrg[2][CLS ? 5 : 2][TQ];                               // [key-wave][m | l (| sd | ss | c)][query]
@@ -185,6 +202,9 @@ struct GP2 {
   int same_positive;
   float eps;
   float nkeys_y;                                // key count of the column direction (its denominator before masking)
+  // batched launch: lse_x = lse_y = lse [nz][Mx], cnt_x = cnt_y = cnt [nz][Mx], upstream [nz] (or null), slab and
+  // dsc_part hold the problems one after another
+  PairZ z;
 };
 
 constexpr int GPMAX = 512;                         // contraction / output width limit of the tiled gradient pass
@@ -193,8 +213,20 @@ constexpr int KSB = 16;                            // keys per staged block of t
 constexpr int BKG = 16;                            // K-step of the gradient pass's S tile (LDS budget: 2 workgroups per CU)
 constexpr int GRAD_LDS_FLOATS = 2 * 2 * 64 * (BKG + 4) + TK * TQ + KSB * YH_LD + 2 * TQ;
 
-template <bool CLS>
-__global__ __launch_bounds__(256, 2) void simce_grad_tiled_kernel(const GP2 p) {
+template <bool CLS, bool ZB = false>
+__global__ __launch_bounds__(256, 2) void simce_grad_tiled_kernel(const GP2 pa) {
+  GP2 p = pa;
+  if constexpr (ZB) {                                                     // this workgroup's problem
+    const int z = blockIdx.z, r = pa.z.rev[z];
+    const long zs = (long)z * gridDim.y * p.Mx;                           // rows of key-split partials before it
+    p.X = pa.z.E + (long)pa.z.xa[z] * p.Mx * p.P;
+    p.Y = p.Yc = pa.z.E + (long)pa.z.ya[z] * p.Ny * p.P;
+    p.cls_x = p.cls_y = pa.z.ids[z];
+    p.lse_x = pa.lse_x + (long)z * p.Mx; p.lse_y = pa.lse_x + (long)r * p.Mx;   // the keys' LSE: the reverse problem's
+    p.cnt_x = pa.cnt_x + (long)z * p.Mx; p.cnt_y = pa.cnt_x + (long)r * p.Mx;
+    if (pa.upstream) p.upstream = pa.upstream + z;
+    p.slab += zs * p.P; p.dsc_part += zs;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* smem = reinterpret_cast<float*>(smem_raw);                      // K-loop buffers
   float* gl = smem + 2 * 2 * 64 * (BKG + 4);                              // G tile [64 keys][64 queries]
@@ -261,12 +293,16 @@ __global__ __launch_bounds__(256, 2) void simce_grad_tiled_kernel(const GP2 p) {
           const bool same = diag || (kin && p.cls_y && p.cls_y[key] == cq);
           const bool in_d = p.same_positive || !same || diag;
           const float hard = p.same_positive ? (same ? inv_cx : 0.f) : (diag ? 1.f : 0.f);
-          gv = p.w_row * ((in_d ? expf(sv - lse_xi) : 0.f) - ((1.f - p.eps) * hard + (in_d ? eps_nx : 0.f)));
+          // batched launch: the logit ROUNDED, as the LSE pass saw it, so that a row whose denominator is its own key
+          // alone (lse = that logit) gets exp(0) - 1 = 0 exactly; in the single-problem instantiation the compiler
+          // contracts scale * acc - lse (an unrounded product: 2e-9 in dX for such a row), and its bits are pinned
+          const float sl = ZB ? mul_rounded(scale, acc[r]) : sv;
+          gv = p.w_row * ((in_d ? expf(sl - lse_xi) : 0.f) - ((1.f - p.eps) * hard + (in_d ? eps_nx : 0.f)));
           if (kin) {
             const float cy = p.cnt_y ? p.cnt_y[key] : 1.f;
             const float hy = p.same_positive ? (same ? 1.f / cy : 0.f) : (diag ? 1.f : 0.f);
             const float ny = p.same_positive ? p.nkeys_y : p.nkeys_y - (cy - 1.f);
-            gv += p.w_col * ((in_d ? expf(sv - p.lse_y[key]) : 0.f) - ((1.f - p.eps) * hy + (in_d ? p.eps / ny : 0.f)));
+            gv += p.w_col * ((in_d ? expf(sl - p.lse_y[key]) : 0.f) - ((1.f - p.eps) * hy + (in_d ? p.eps / ny : 0.f)));
           }
           gv *= ibg;
         }
@@ -372,18 +408,33 @@ extern "C" void clipk_simce_grad_tiled_plan(int Mx, int Nkeys, int* nqb, int* ks
   *ksplit = (*ntiles + *tps - 1) / *tps;
 }
 
+// the same for npairs same-shape B x B problems in one grid (blockIdx.z = problem): the splits are chosen for the WHOLE
+// grid nqb x ksplit x npairs (two workgroups per CU), not as if each problem had the chip to itself
+extern "C" void clipk_simce_pairs_tiled_plan(int npairs, int B, int* nqb, int* ksplit, int* tps, int* ntiles) {
+  *nqb = (B + TQ - 1) / TQ;
+  *ntiles = (B + TK - 1) / TK;
+  const int wgs = *nqb * (npairs > 0 ? npairs : 1);
+  int ks = (512 + wgs - 1) / wgs;
+  if (ks > *ntiles) ks = *ntiles;
+  if (ks < 1) ks = 1;
+  *tps = (*ntiles + ks - 1) / ks;
+  *ksplit = (*ntiles + *tps - 1) / *tps;
+}
+
 namespace {
-template <bool CLS>
+template <bool CLS, bool ZB = false>
 int grad_tiled_launch(GP2& p, int Mx, int Nkeys, void* stream) {
   int nqb, ksplit;
-  clipk_simce_grad_tiled_plan(Mx, Nkeys, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  if constexpr (ZB) clipk_simce_pairs_tiled_plan(p.z.nz, Mx, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  else clipk_simce_grad_tiled_plan(Mx, Nkeys, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
   const size_t lds = (size_t)GRAD_LDS_FLOATS * sizeof(float);
   static std::atomic<uint64_t> attr_set{0};
   clipk_once_per_device(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(simce_grad_tiled_kernel<CLS>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(simce_grad_tiled_kernel<CLS, ZB>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
-  hipLaunchKernelGGL(simce_grad_tiled_kernel<CLS>, dim3(nqb, ksplit), dim3(256), lds, (hipStream_t)stream, p);
+  hipLaunchKernelGGL((simce_grad_tiled_kernel<CLS, ZB>), dim3(nqb, ksplit, ZB ? p.z.nz : 1), dim3(256), lds,
+                     (hipStream_t)stream, p);
   return clipk_check_launch();
 }
 }  // namespace
@@ -441,4 +492,30 @@ extern "C" int clipk_simce_lse_tiled_cls_launch(const float* X, int Mx, const fl
   clipk_simce_tiled_plan(Mx, Ny + Nc, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
   hipLaunchKernelGGL(simce_lse_tiled_kernel<true>, dim3(nqb, ksplit), dim3(256), 0, (hipStream_t)stream, p);
   return clipk_check_launch();
+}
+
+// ---- batched class-aware launches (clipk_simce_{lse,grad}_pairs_cls): zt.nz problems of shape B x B over zt.E, the
+// splits of clipk_simce_pairs_tiled_plan; per-problem outputs and partials follow one another
+extern "C" int clipk_simce_lse_tiled_pairs_cls_launch(const PairZ* zt, int B, int P, const float* scale, int same_positive,
+                                                      float* part_ml, float* part_t, float* pos, void* stream) {
+  LP p{};
+  p.Mx = B; p.Ny = B; p.Nc = 0; p.P = P; p.scale = scale; p.label_offset = 0;
+  p.part_ml = part_ml; p.part_t = part_t; p.pos = pos; p.same_positive = same_positive; p.z = *zt;
+  int nqb, ksplit;
+  clipk_simce_pairs_tiled_plan(zt->nz, B, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  hipLaunchKernelGGL((simce_lse_tiled_kernel<true, true>), dim3(nqb, ksplit, zt->nz), dim3(256), 0, (hipStream_t)stream, p);
+  return clipk_check_launch();
+}
+
+extern "C" int clipk_simce_grad_tiled_pairs_cls_launch(const PairZ* zt, int B, int P, const float* scale, const float* lse,
+                                                       const float* cnt, int same_positive, float eps, float w_row,
+                                                       float w_col, float inv_bg, const float* upstream, float* slab,
+                                                       float* dsc_part, void* stream) {
+  if (P > GPMAX) return CLIPK_ERR_UNSUPPORTED;
+  GP2 p{};
+  p.Mx = B; p.Ny = B; p.Nc = 0; p.P = P; p.scale = scale; p.label_offset = 0;
+  p.lse_x = lse; p.lse_y = lse; p.cnt_x = cnt; p.cnt_y = cnt; p.same_positive = same_positive; p.eps = eps;
+  p.nkeys_y = (float)B; p.w_row = w_row; p.w_col = w_col; p.inv_bg = inv_bg; p.upstream = upstream;
+  p.slab = slab; p.dsc_part = dsc_part; p.z = *zt;
+  return grad_tiled_launch<true, true>(p, B, B, stream);
 }

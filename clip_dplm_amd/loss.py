@@ -281,48 +281,140 @@ def contrastive_loss(x: torch.Tensor, y: torch.Tensor, temperature: float = 0.1,
 _TRI_PAIRS = ((0, 1), (1, 0), (0, 2), (2, 0), (1, 2), (2, 1))      # (cell,pert) (pert,cell) (cell,prot) ...
 
 
+class _TriVariant(NamedTuple):
+    """What tells one variant of the batched tri-modal loss from another inside TriModalLossFn (the _Variant of the six
+    directed problems of _TRI_PAIRS).  `stat`: the tensors [6, ...] that travel from the LSE pass to the gradient pass.
+      lse(E, scale, ids6) -> (lse, tgt, stat)
+      grad(E, scale, stat, inv_b, ids6, upstream) -> (dX [6, B, P], dscale partials [6, B]); upstream: f32 [6], the
+          incoming gradient of each problem's loss
+      folds: grad multiplies upstream in, inside the kernel; else the caller does, on [B, P]."""
+    lse: Callable
+    grad: Callable
+    folds: bool
+
+
+def _tri_plain_lse(E, scale, ids6):
+    lse, pos = _kernels.simce_lse_pairs(E, _TRI_PAIRS, scale)
+    return lse, pos, (lse,)
+
+
+_TRI_PLAIN = _TriVariant(
+    lse=_tri_plain_lse,
+    grad=lambda E, scale, stat, inv_b, ids6, g: _kernels.simce_grad_pairs(E, _TRI_PAIRS, scale, stat[0], 0.5, 0.5, inv_b),
+    folds=False)
+
+
+def _tri_class_aware(same_class: str, eps: float) -> _TriVariant:
+    """clipk_simce_{lse,grad}_pairs_cls: stat = (lse, cnt)."""
+    def lse(E, scale, ids6):
+        lse, tgt, cnt = _kernels.simce_lse_pairs_cls(E, _TRI_PAIRS, scale, ids=ids6, same_class=same_class, eps=eps)
+        return lse, tgt, (lse, cnt)
+
+    def grad(E, scale, stat, inv_b, ids6, g):
+        return _kernels.simce_grad_pairs_cls(E, _TRI_PAIRS, scale, stat[0], stat[1], 0.5, 0.5, inv_b, ids=ids6,
+                                             same_class=same_class, eps=eps, upstream=g)
+    return _TriVariant(lse, grad, True)
+
+
+def _tri_hard_negative(beta: float) -> _TriVariant:
+    """clipk_simce_{lse,grad}_pairs_hard: stat = (coef [6, 3, B],)."""
+    def lse(E, scale, ids6):
+        lse, pos, coef = _kernels.simce_lse_pairs_hard(E, _TRI_PAIRS, scale, beta, ids=ids6)
+        return lse, pos, (coef,)
+
+    def grad(E, scale, stat, inv_b, ids6, g):
+        return _kernels.simce_grad_pairs_hard(E, _TRI_PAIRS, scale, beta, stat[0], 0.5, 0.5, inv_b, ids=ids6, upstream=g)
+    return _TriVariant(lse, grad, True)
+
+
 class TriModalLossFn(torch.autograd.Function):
-    """The three pairwise symmetric InfoNCE losses of current/tf_clip_codes (1).ipynb:13150-13163 on ONE logit scale:
-    six directed similarity + LSE problems in one launch (clipk_simce_lse_pairs), six gradient problems in one more
-    (clipk_simce_grad_pairs).  Returns (cell_pert, cell_protein, pert_protein) losses; any combination of upstream
-    gradients is honoured."""
+    """The three pairwise symmetric InfoNCE losses of current/tf_clip_codes (1).ipynb:13150-13163 on ONE logit scale, of
+    every variant (_TriVariant): six directed similarity + LSE problems in one launch (clipk_simce_lse_pairs[_cls|_hard]),
+    six gradient problems in one more (clipk_simce_grad_pairs[...]).  ids: the id vectors of (cell, pert), (cell, protein)
+    and (pert, protein), each int64 [B] or None (all distinct).  Returns (cell_pert, cell_protein, pert_protein) losses;
+    any combination of upstream gradients is honoured."""
 
     @staticmethod
-    def forward(ctx, cell, pert, prot, scale):
+    def forward(ctx, cell, pert, prot, scale, variant=_TRI_PLAIN, ids_cp=None, ids_ce=None, ids_pe=None):
         E = torch.stack([cell, pert, prot]).contiguous()                # [3, B, P]
         sc = scale.reshape(1).contiguous()
-        lse, pos = _kernels.simce_lse_pairs(E, _TRI_PAIRS, sc)
-        per = (lse - pos).mean(1)                                       # six one-directional CE values
-        ctx.save_for_backward(E, sc, lse)
+        lse, tgt, stat = variant.lse(E, sc, (ids_cp, ids_cp, ids_ce, ids_ce, ids_pe, ids_pe))
+        per = (lse - tgt).mean(1)                                       # six one-directional CE values
+        ctx.save_for_backward(E, sc, ids_cp, ids_ce, ids_pe, *stat)
         ctx.scale_shape = scale.shape
+        ctx.variant = variant
         return 0.5 * (per[0] + per[1]), 0.5 * (per[2] + per[3]), 0.5 * (per[4] + per[5])
 
     @staticmethod
     def backward(ctx, g_cp, g_ce, g_pe):
-        E, sc, lse = ctx.saved_tensors
+        E, sc, ids_cp, ids_ce, ids_pe, *stat = ctx.saved_tensors
+        variant = ctx.variant
         B = E.shape[1]
-        dX, dsc = _kernels.simce_grad_pairs(E, _TRI_PAIRS, sc, lse, 0.5, 0.5, 1.0 / B)
+        ids6 = (ids_cp, ids_cp, ids_ce, ids_ce, ids_pe, ids_pe)
         # problem (a, b) holds d L_ab / d E_a complete (both directions): combine per modality — [B, P] adds: plumbing
-        dcell = g_cp * dX[0] + g_ce * dX[2]
-        dpert = g_cp * dX[1] + g_pe * dX[4]
-        dprot = g_ce * dX[3] + g_pe * dX[5]
-        dscale = (g_cp * dsc[0].sum() + g_ce * dsc[2].sum() + g_pe * dsc[4].sum()).reshape(ctx.scale_shape)
-        return dcell, dpert, dprot, dscale
+        if variant.folds:                       # the three incoming gradients go into the kernel, one per problem
+            g = torch.stack([g_cp, g_cp, g_ce, g_ce, g_pe, g_pe]).to(torch.float32)
+            dX, dsc = variant.grad(E, sc, stat, 1.0 / B, ids6, g)
+            dcell, dpert, dprot = dX[0] + dX[2], dX[1] + dX[4], dX[3] + dX[5]
+            dscale = dsc[0::2].sum().reshape(ctx.scale_shape)
+        else:
+            dX, dsc = variant.grad(E, sc, stat, 1.0 / B, ids6, None)
+            dcell = g_cp * dX[0] + g_ce * dX[2]
+            dpert = g_cp * dX[1] + g_pe * dX[4]
+            dprot = g_ce * dX[3] + g_pe * dX[5]
+            dscale = (g_cp * dsc[0].sum() + g_ce * dsc[2].sum() + g_pe * dsc[4].sum()).reshape(ctx.scale_shape)
+        return dcell, dpert, dprot, dscale, None, None, None, None
+
+
+TRI_PAIR_KEYS = ("cell_pert", "cell_protein", "pert_protein")
+
+
+def _tri_class_ids(class_ids) -> tuple:
+    """class_ids of tri_modal_loss -> the three pairs' ids in the order of TRI_PAIR_KEYS (ValueError on an unknown key)."""
+    if class_ids is None or torch.is_tensor(class_ids):
+        if torch.is_tensor(class_ids) and class_ids.dtype in (torch.int32, torch.int16, torch.int8, torch.uint8):
+            class_ids = class_ids.to(torch.int64)              # once for the three pairs, not once per pair
+        return (class_ids,) * 3
+    if not hasattr(class_ids, "keys"):
+        raise ValueError(f"class_ids must be a tensor or a mapping with keys among {TRI_PAIR_KEYS}, got "
+                         f"{type(class_ids).__name__}")
+    unknown = [k for k in class_ids.keys() if k not in TRI_PAIR_KEYS]
+    if unknown:
+        raise ValueError(f"class_ids has keys {unknown}; the pairs are {TRI_PAIR_KEYS}")
+    return tuple(class_ids.get(k) for k in TRI_PAIR_KEYS)
 
 
 def tri_modal_loss(cell_embed: torch.Tensor, pert_embed: torch.Tensor, protein_embed: torch.Tensor,
-                   logit_scale_exp: torch.Tensor, group=None):
+                   logit_scale_exp: torch.Tensor, group=None, *, class_ids=None, same_class: str = "mask",
+                   label_smoothing: float = 0.0, hard_negative_beta: float = 0.0):
     """Tri-modal contrastive objective of current/tf_clip_codes (1).ipynb:13150-13176: three pairwise symmetric
     InfoNCE losses sharing one logit_scale on the fused similarity + CE kernels (no B x B logits).  Single process:
     one batched launch per pass for all three pairs (TriModalLossFn); with a process group: three global-batch
-    clip_loss calls.  Returns the loss entries of the reference's ContrastiveModel.forward dict."""
+    clip_loss calls.  Returns the loss entries of the reference's ContrastiveModel.forward dict.
+
+    class_ids, same_class, label_smoothing, hard_negative_beta: clip_loss's, applied to every pair.  class_ids is one
+    integer tensor [B] used for all three pairs (a PerturbAtlas batch, whose perturbation and protein rows repeat, one
+    per cell: class_ids=pert_id), or a mapping with keys among "cell_pert", "cell_protein", "pert_protein"; a pair
+    without ids is all distinct.  Defaults: exactly the plain loss and its kernels."""
+    pairs = ((cell_embed, pert_embed), (cell_embed, protein_embed), (pert_embed, protein_embed))
+    ids = []
+    for (a, b), t in zip(pairs, _tri_class_ids(class_ids)):
+        t, eps = _check_class_args(a, b, None, t, same_class, label_smoothing)
+        ids.append(t)
+    for a, b in pairs[:2]:                                 # (they cover the three embeddings)
+        beta = _check_hard_args(a, b, None, same_class, eps, hard_negative_beta)
     if group is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         group = dist.group.WORLD
     if group is not None and dist.get_world_size(group) > 1:
-        cp = clip_loss(cell_embed, pert_embed, logit_scale_exp, symmetric=True, group=group)
-        ce = clip_loss(cell_embed, protein_embed, logit_scale_exp, symmetric=True, group=group)
-        pe = clip_loss(pert_embed, protein_embed, logit_scale_exp, symmetric=True, group=group)
+        kw = dict(symmetric=True, group=group, same_class=same_class, label_smoothing=label_smoothing,
+                  hard_negative_beta=hard_negative_beta)
+        cp, ce, pe = (clip_loss(a, b, logit_scale_exp, class_ids=t, **kw) for (a, b), t in zip(pairs, ids))
     else:
-        cp, ce, pe = TriModalLossFn.apply(cell_embed.contiguous(), pert_embed.contiguous(), protein_embed.contiguous(),
-                                          logit_scale_exp)
+        args = (cell_embed.contiguous(), pert_embed.contiguous(), protein_embed.contiguous(), logit_scale_exp)
+        if beta > 0.0:
+            cp, ce, pe = TriModalLossFn.apply(*args, _tri_hard_negative(beta), *ids)
+        elif eps > 0.0 or any(t is not None for t in ids):
+            cp, ce, pe = TriModalLossFn.apply(*args, _tri_class_aware(same_class, eps), *ids)
+        else:
+            cp, ce, pe = TriModalLossFn.apply(*args)
     return {"loss": cp + ce + pe, "cell_pert_loss": cp, "cell_protein_loss": ce, "pert_protein_loss": pe}

@@ -182,7 +182,10 @@ class ContrastiveModel(nn.Module):
     def _sl(self, x):
         return x[:, :1] if (self.slice_first_position and x.dim() == 3) else x
 
-    def forward(self, cell_state, connectivity, gene_esm_embeddings, gene_values, protein_emb, group=None):
+    def forward(self, cell_state, connectivity, gene_esm_embeddings, gene_values, protein_emb, group=None, *,
+                class_ids=None, same_class="mask", label_smoothing=0.0, hard_negative_beta=0.0):
+        """class_ids, same_class, label_smoothing, hard_negative_beta: loss.tri_modal_loss's (a PerturbAtlas batch, whose
+        perturbation and protein rows repeat, one per cell: class_ids=pert_id); the output dict is the same."""
         if self.slice_first_position and gene_esm_embeddings.dim() == 3:
             gene_esm_embeddings, gene_values = gene_esm_embeddings[:, :1], gene_values[:, :1]
         cell = lambda: KF.l2_normalize(self.cell_projection(self._first(self.cell_encoder(cell_state, connectivity))))
@@ -197,5 +200,7 @@ class ContrastiveModel(nn.Module):
         else:
             cell_embed, pert_embed, protein_embed = cell(), pert(), prot()
         out = {"cell_embed": cell_embed, "pert_embed": pert_embed, "protein_embed": protein_embed}
-        out.update(tri_modal_loss(cell_embed, pert_embed, protein_embed, self.logit_scale.exp(), group=group))
+        out.update(tri_modal_loss(cell_embed, pert_embed, protein_embed, self.logit_scale.exp(), group=group,
+                                  class_ids=class_ids, same_class=same_class, label_smoothing=label_smoothing,
+                                  hard_negative_beta=hard_negative_beta))
         return out

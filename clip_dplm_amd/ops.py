@@ -454,6 +454,107 @@ def simce_grad_pairs(E, pairs, scale, lse, w_row, w_col, inv_bg):
     return dX, dsc
 
 
+def _pairs_variant_args(E, pairs, scale, ids, same_class="mask", eps=0.0, tensors=()):
+    """Shapes and dtypes of the batched class-aware / hard-negative passes' operands (the kernels read them as raw f32 /
+    int64 arrays of these lengths): ValueError on anything else.  ids: None or one entry per problem, each None or int64
+    [B]; both directions of a pair carry the same ids.  tensors: (name, tensor or None, shape) of further f32 inputs.
+    Returns (the host pairs array, the reverse array, the host array of id pointers)."""
+    if E.dtype != torch.float32 or E.dim() != 3 or not E.is_contiguous():
+        raise ValueError(f"E must be a contiguous float32 [nmod, B, P] tensor, got {E.dtype} {tuple(E.shape)}")
+    nmod, B, P = E.shape
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    n = len(pairs)
+    if not 1 <= n <= 6:
+        raise ValueError(f"1 to 6 problems per launch, got {n}")
+    if any(not (0 <= a < nmod and 0 <= b < nmod) for a, b in pairs):
+        raise ValueError(f"pairs index the {nmod} modalities of E, got {pairs}")
+    if B == 0 or P == 0 or P % 4 or P > 512:
+        raise ValueError(f"the batched class-aware / hard-negative passes support B > 0, P % 4 == 0 and P <= 512, got "
+                         f"B = {B}, P = {P}")
+    if scale.dtype != torch.float32 or scale.numel() != 1:
+        raise ValueError(f"scale must be a 1-element float32 tensor, got {scale.dtype} {tuple(scale.shape)}")
+    ids = [None] * n if ids is None else list(ids)
+    if len(ids) != n:
+        raise ValueError(f"ids: one entry (a tensor or None) per problem, got {len(ids)} for {n} problems")
+    for i, t in enumerate(ids):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (B,)
+                              or not t.is_contiguous()):
+            raise ValueError(f"ids[{i}] must be a contiguous int64 tensor of shape ({B},) or None, got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+    pa, ra = _pairs_arrays(pairs)
+    for i, r in enumerate(ra):
+        if ptr(ids[i]) != ptr(ids[r]):
+            raise ValueError(f"problems {i} and {r} are the two directions of one pair: they must carry the same ids")
+    for name, t, shape in tensors:
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape}, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    if same_class not in _ffi.SAME_CLASS:
+        raise ValueError(f"same_class must be one of {tuple(_ffi.SAME_CLASS)}, got {same_class!r}")
+    if not 0.0 <= float(eps) < 1.0:
+        raise ValueError(f"eps must be in [0, 1), got {eps}")
+    _need_cuda(E, scale, *ids, *[t for _, t, _ in tensors])
+    return pa, ra, (C.c_void_p * n)(*[ptr(t) for t in ids])
+
+
+def _simce_pairs(entry, kind, E, n, args, outs):
+    """The call the four batched variant wrappers share: outputs (f32, torch.empty), workspace, the entry point.  args:
+    its arguments between P and the outputs."""
+    nmod, B, P = E.shape
+    res = [torch.empty(shape, dtype=torch.float32, device=E.device) for shape in outs]
+    lib = _lib()
+    nbytes = getattr(lib, f"clipk_simce_pairs_{kind}_workspace")(n, B, P)
+    if nbytes == 0:
+        raise _ffi.ClipkError(f"simce pairs ({kind}): unsupported shape npairs={n} B={B} P={P}")
+    stream = _stream()
+    ws = workspace(nbytes, E.device, "simce", stream)
+    check(getattr(lib, entry)(E.data_ptr(), nmod, B, P, *args, *[t.data_ptr() for t in res], ws.data_ptr(), ws.numel(),
+                              stream), entry)
+    return tuple(res)
+
+
+def simce_lse_pairs_cls(E, pairs, scale, ids=None, same_class="mask", eps=0.0):
+    """Batched class-aware LSE pass (include/clipk.h: clipk_simce_lse_pairs_cls): (lse, tgt, cnt), each f32 [npairs, B].
+    ids: per problem a device int64 [B] or None (all distinct)."""
+    pa, _, ia = _pairs_variant_args(E, pairs, scale, ids, same_class, eps)
+    n, B = len(pairs), E.shape[1]
+    return _simce_pairs("clipk_simce_lse_pairs_cls", "cls", E, n,
+                        (pa, n, scale.data_ptr(), ia, _ffi.SAME_CLASS[same_class], float(eps)), ((n, B),) * 3)
+
+
+def simce_grad_pairs_cls(E, pairs, scale, lse, cnt, w_row, w_col, inv_bg, ids=None, same_class="mask", eps=0.0,
+                         upstream=None):
+    """Batched class-aware gradient pass (clipk_simce_grad_pairs_cls): dX [npairs, B, P], dscale partials [npairs, B].
+    lse, cnt: simce_lse_pairs_cls's; upstream: f32 [npairs] multiplied into each problem's gradient, or None."""
+    n, (_, B, P) = len(pairs), E.shape
+    pa, ra, ia = _pairs_variant_args(E, pairs, scale, ids, same_class, eps,
+                                     (("lse", lse, (n, B)), ("cnt", cnt, (n, B)), ("upstream", upstream, (n,))))
+    return _simce_pairs("clipk_simce_grad_pairs_cls", "cls", E, n,
+                        (pa, ra, n, scale.data_ptr(), ia, _ffi.SAME_CLASS[same_class], float(eps), lse.data_ptr(),
+                         cnt.data_ptr(), float(w_row), float(w_col), float(inv_bg), ptr(upstream)), ((n, B, P), (n, B)))
+
+
+def simce_lse_pairs_hard(E, pairs, scale, beta, ids=None):
+    """Batched hard-negative LSE pass (clipk_simce_lse_pairs_hard): lse_h, pos f32 [npairs, B], coef f32 [npairs, 3, B]."""
+    beta = _hard_beta(beta)
+    pa, _, ia = _pairs_variant_args(E, pairs, scale, ids)
+    n, B = len(pairs), E.shape[1]
+    return _simce_pairs("clipk_simce_lse_pairs_hard", "hard", E, n, (pa, n, scale.data_ptr(), beta, ia),
+                        ((n, B), (n, B), (n, 3, B)))
+
+
+def simce_grad_pairs_hard(E, pairs, scale, beta, coef, w_row, w_col, inv_bg, ids=None, upstream=None):
+    """Batched hard-negative gradient pass (clipk_simce_grad_pairs_hard): dX [npairs, B, P], dscale partials
+    [npairs, B].  coef: simce_lse_pairs_hard's; upstream: f32 [npairs] or None."""
+    beta = _hard_beta(beta)
+    n, (_, B, P) = len(pairs), E.shape
+    pa, ra, ia = _pairs_variant_args(E, pairs, scale, ids, tensors=(("coef", coef, (n, 3, B)),
+                                                                     ("upstream", upstream, (n,))))
+    return _simce_pairs("clipk_simce_grad_pairs_hard", "hard", E, n,
+                        (pa, ra, n, scale.data_ptr(), beta, ia, coef.data_ptr(), float(w_row), float(w_col),
+                         float(inv_bg), ptr(upstream)), ((n, B, P), (n, B)))
+
+
 def sim_logits(x, y, scale):
     _need_cuda(x, y, scale)
     Mx, P = x.shape

@@ -258,6 +258,41 @@ int clipk_simce_grad_pairs(const float* E, int nmod, int B, int P, const int* pa
                            float inv_bg, float* dX /*[npairs][B][P]*/, float* dscale_partial /*[npairs][B]*/,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* The batched form of the class-aware and of the hard-negative pair: the same npairs <= 6 same-shape problems over
+ * E [nmod][B][P], each with the definitions of clipk_simce_{lse,grad}_cls resp. clipk_simce_{lse,grad}_hard for
+ * Mx = Ny = B, Nc = 0, label_offset = 0 and cls_x = cls_y = ids[i] - nothing new is defined.  In a PerturbAtlas batch
+ * the perturbation and protein rows repeat, one per cell: without ids every row of pert x protein is asked to rank its
+ * key above exact copies of it.
+ *   ids: HOST array of npairs DEVICE pointers to int64 [B]; an entry may be NULL (that problem: all distinct).  A
+ *        problem and its reverse are the two directions of one pair and carry the same pointer (else CLIPK_ERR_BAD_ARG
+ *        from the gradient entries).  same_class, eps, beta and the scale are shared by all problems.
+ *   upstream: device [npairs] or NULL: the gradient of problem i is multiplied by upstream[i] inside the kernel (the
+ *        incoming gradient of the loss the problem belongs to), as clipk_simce_grad_scaled does with its one scalar.
+ *   outputs: lse, tgt, cnt, lse_h, pos [npairs][B]; coef [npairs][3][B]; dX [npairs][B][P]; dscale_partial [npairs][B].
+ *        grad takes the LSE pass's lse and cnt (cls) resp. coef (hard) whole: problem i reads row i for its queries
+ *        and row reverse[i] for its keys.
+ * One launch per pass (grid z = problem) plus one finalize each; the key splits are chosen for the whole grid
+ * nqb x ksplit x npairs, and their partials merge in a fixed order: deterministic.  No atomics, no allocation, no
+ * synchronisation.  P % 4 == 0, P <= 512 (else CLIPK_ERR_UNSUPPORTED); bad pairs / reverse / npairs: CLIPK_ERR_BAD_ARG.
+ * workspace: clipk_simce_pairs_cls_workspace resp. clipk_simce_pairs_hard_workspace bytes (each covers both passes). */
+size_t clipk_simce_pairs_cls_workspace(int npairs, int B, int P);
+int clipk_simce_lse_pairs_cls(const float* E, int nmod, int B, int P, const int* pairs, int npairs, const float* scale,
+                              const int64_t* const* ids, int same_class, float eps, float* lse, float* tgt, float* cnt,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int clipk_simce_grad_pairs_cls(const float* E, int nmod, int B, int P, const int* pairs, const int* reverse, int npairs,
+                               const float* scale, const int64_t* const* ids, int same_class, float eps,
+                               const float* lse, const float* cnt, float w_row, float w_col, float inv_bg,
+                               const float* upstream, float* dX, float* dscale_partial, void* workspace,
+                               size_t workspace_bytes, void* stream);
+size_t clipk_simce_pairs_hard_workspace(int npairs, int B, int P);
+int clipk_simce_lse_pairs_hard(const float* E, int nmod, int B, int P, const int* pairs, int npairs, const float* scale,
+                               float beta, const int64_t* const* ids, float* lse_h, float* pos, float* coef,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int clipk_simce_grad_pairs_hard(const float* E, int nmod, int B, int P, const int* pairs, const int* reverse, int npairs,
+                                const float* scale, float beta, const int64_t* const* ids, const float* coef, float w_row,
+                                float w_col, float inv_bg, const float* upstream, float* dX, float* dscale_partial,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* Materialised logits for the drop-in module API (old/clip.py:67 returns them):
  *   S[Mx,Ny] = scale * X·Y^T, exact f32. */
 int clipk_sim_logits(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale,
