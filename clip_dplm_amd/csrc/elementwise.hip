@@ -127,6 +127,25 @@ __global__ void dropout_f32_kernel(const float* x, const float* addend, float* y
   }
 }
 
+// GELU'(x) below x = -4, where it is under 5e-4 and the ABSOLUTE error of the A&S erf (1.5e-7, common.h) is per cents of it:
+// many bf16 steps of the result this kernel rounds to.  Phi(x) + x phi(x) = phi(x) (R(|x|) - |x|) with the Mills ratio R
+// by its continued fraction to depth 4, as one rational in s = x^2 (relative error <= 1.8e-6 for |x| >= 4, nothing
+// cancels):  GELU'(x) = phi(x) (s^3 + 9 s^2 + 6 s - 8) / (x (s^2 + 10 s + 15)).
+// exp2 is taken 2^64 too large and the product scaled back: the raw v_exp_f32 flushes a subnormal result, the multiply
+// does not (results down to the smallest bf16 subnormal are reached at x = -13.7).  Beyond x = -20 the value is 0.
+__device__ __forceinline__ float gelu_grad_tail(float x) {
+  x = fmaxf(x, -20.0f);
+  const float s = x * x;
+  const float num = fmaf(fmaf(s + 9.0f, s, 6.0f), s, -8.0f);
+  const float den = x * fmaf(s + 10.0f, s, 15.0f);
+  const float e = __builtin_amdgcn_exp2f(fmaf(-0.72134752044448170368f * x, x, 64.0f));
+  return (0.39894228040143267794f * e) * num * __builtin_amdgcn_rcpf(den) * 0x1p-64f;
+}
+__device__ __forceinline__ float dact_grad(float x, int act) {
+  if (act == CLIPK_ACT_GELU) return x < -4.0f ? gelu_grad_tail(x) : gelu_erf_grad(x);
+  return act_grad(x, act);
+}
+
 // out_bf16 = dy * act'(aux): the activation backward between two Linear layers (dy f32 or bf16)
 template <bool DYBF16>
 __global__ void dact_kernel(const void* dy, const unsigned short* aux, int act, unsigned short* out, long n) {
@@ -147,13 +166,13 @@ __global__ void dact_kernel(const void* dy, const unsigned short* aux, int act, 
     u32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      o[e] = pack_bf16x2(d[2 * e] * act_grad(bf16_to_f32(x[e] & 0xffffu), act),
-                         d[2 * e + 1] * act_grad(bf16_to_f32(x[e] >> 16), act));
+      o[e] = pack_bf16x2(d[2 * e] * dact_grad(bf16_to_f32(x[e] & 0xffffu), act),
+                         d[2 * e + 1] * dact_grad(bf16_to_f32(x[e] >> 16), act));
     reinterpret_cast<u32x4*>(out)[i] = o;
   }
   for (long i = (n8 << 3) + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
     const float d = DYBF16 ? bf16_to_f32(reinterpret_cast<const unsigned short*>(dy)[i]) : reinterpret_cast<const float*>(dy)[i];
-    out[i] = f32_to_bf16(d * act_grad(bf16_to_f32(aux[i]), act));
+    out[i] = f32_to_bf16(d * dact_grad(bf16_to_f32(aux[i]), act));
   }
 }
 
@@ -168,7 +187,7 @@ __global__ void embed_fwd_kernel(const int64_t* ids, const float* table, const f
     const int64_t id = ids[t];
     float sc = row_scale ? row_scale[t / L] : 1.0f;
     if (mask && !mask[t]) sc = 0.f;
-    if ((int)id == mask_token_id) sc = 0.f;
+    if (id == (int64_t)mask_token_id) sc = 0.f;             // compared as int64: 2^32 + the mask token is no mask token
     // an id outside the table never reads memory: its row comes out as NaN, so the mistake surfaces in the loss
     // (F.embedding would trip a device assert; a silent wild read is the one thing that must not happen)
     const bool ok = id >= 0 && id < V;
@@ -194,7 +213,11 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const int64_t* ids, cons
   const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
   const long T = (long)B * L;
   for (long t = wave; t < T; t += nwaves) {
-    const int id = (int)ids[t];
+    // an id outside the table contributes nothing and touches no memory (tested as int64, before narrowing: the
+    // forward pass has already turned that token's row into NaN, embed_fwd_kernel)
+    const int64_t id64 = ids[t];
+    if (id64 < 0 || id64 >= V) continue;
+    const int id = (int)id64;
     float sc = row_scale ? row_scale[t / L] : 1.0f;
     if (mask && !mask[t]) sc = 0.f;
     if (id == mask_token_id) sc = 0.f;
@@ -248,7 +271,8 @@ __global__ __launch_bounds__(256, 3) void embed_bwd_mfma_kernel(const int64_t* i
       const long t = t0 + 8 * u + kk;
       const bool tok_ok = t < t_end;
       const unsigned tc = (unsigned)(tok_ok ? t : t_beg);      // B * L < 2^31 (launcher)
-      const int id = (int)ids[tc];
+      const int64_t id64 = ids[tc];
+      const int id = (id64 >= 0 && id64 < V) ? (int)id64 : -1;  // outside the table (as int64): matches no one-hot row
       float sc = row_scale ? row_scale[tc / (unsigned)L] : 1.0f;
       if (mask && !mask[tc]) sc = 0.f;
       if (id == mask_token_id || !tok_ok) sc = 0.f;
