@@ -24,6 +24,8 @@ from .retrieval import EmbeddingIndex, evaluate_retrieval, metrics_from_ranks, r
 from . import retrieval
 from .diagnostics import SimilarityStats, evaluate_embeddings, similarity_stats
 from . import diagnostics
+from .classifier import LinearClassifier, MLPClassifier, SimpleNonLinearClassifier, TransformerClassifier
+from . import classifier, probe
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -37,4 +39,5 @@ __all__ = [
     "GeneProjection", "create_esm_integration", "get_embeddings_batch", "MemoryQueue", "contrastive_loss", "set_linear_precision",
     "retrieval", "EmbeddingIndex", "evaluate_retrieval", "retrieval_metrics", "metrics_from_ranks",
     "diagnostics", "SimilarityStats", "similarity_stats", "evaluate_embeddings",
+    "classifier", "probe", "MLPClassifier", "TransformerClassifier", "LinearClassifier", "SimpleNonLinearClassifier",
 ]

@@ -133,6 +133,9 @@ SIGNATURES = {
     "clipk_colreduce_batched": (_i, [_vp, _i, _i, _vp]),
     "clipk_set_dropout_epoch": (_i, [_vp]),
     "clipk_gemm_wgrad_f32": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp]),
+    "clipk_linear_ce_workspace": (_sz, [_i, _i, _i, _i]),
+    "clipk_linear_ce_fwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "clipk_linear_ce_bwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_embed_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "clipk_embed_bwd_workspace": (_sz, [_i, _i, _i, _i]),
     "clipk_embed_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -312,6 +312,95 @@ def ce_combine(lse_r, pos_r, lse_c, pos_c, w_row, w_col, bg):
     return out
 
 
+def _linear_ce_args(x, weight, bias, labels, x2):
+    """Checks shared by linear_ce_fwd / linear_ce_bwd (ValueError: the caller's mistake; nothing is launched).  Label VALUES
+    are not looked at - that would be a host sync; a label outside [0, C) makes the loss NaN (include/clipk.h).
+    Returns (M, K1, K2, C)."""
+    for name, t in (("x", x), ("weight", weight), ("bias", bias), ("x2", x2)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"linear_ce: {name} must be float32, got {t.dtype}")
+    if x.dim() != 2 or weight.dim() != 2 or (x2 is not None and (x2.dim() != 2 or x2.shape[0] != x.shape[0])):
+        raise ValueError("linear_ce: x [M, K1], x2 [M, K2] and weight [C, K1 + K2] must be 2-D with the same M")
+    M, K1 = x.shape
+    K2 = 0 if x2 is None else x2.shape[1]
+    C = weight.shape[0]
+    if weight.shape[1] != K1 + K2 or (bias is not None and bias.shape != (C,)):
+        raise ValueError(f"linear_ce: weight {tuple(weight.shape)} / bias do not fit inputs of {K1} + {K2} columns")
+    if labels is not None:
+        if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.dtype.is_complex:
+            raise ValueError(f"linear_ce: labels must be an integer tensor, got {labels.dtype}")
+        if labels.shape != (M,):
+            raise ValueError(f"linear_ce: labels must have shape ({M},), got {tuple(labels.shape)}")
+    devs = {t.device for t in (x, weight, bias, labels, x2) if t is not None}
+    if len(devs) != 1:
+        raise ValueError(f"linear_ce: tensors on different devices: {sorted(map(str, devs))}")
+    if C > 64:
+        raise ValueError(f"linear_ce: {C} classes; the fused kernel takes at most 64")
+    if M < 1 or C < 1 or K1 < 1 or K1 % 4 or K2 % 4 or K1 + K2 > 4096:
+        raise ValueError(f"linear_ce: K1 = {K1}, K2 = {K2} must be multiples of 4 with K1 + K2 <= 4096 (M = {M}, C = {C})")
+    return M, K1, K2, C
+
+
+def _linear_ce_prep(x, weight, bias, labels, x2):
+    M, K1, K2, C = _linear_ce_args(x, weight, bias, labels, x2)
+    _need_cuda(x, weight, bias, labels, x2)
+    x, weight = x.contiguous(), weight.contiguous()
+    x2 = None if x2 is None or K2 == 0 else x2.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    labels = None if labels is None else labels.to(torch.int64).contiguous()
+    return (M, K1, K2 if x2 is not None else 0, C), x, weight, bias, labels, x2
+
+
+def linear_ce_fwd(x, weight, bias=None, labels=None, x2=None, want_logits=False, want_stats=True):
+    """One pass over [x | x2]: (lse [M], tgt [M] or None without labels, pred int64 [M], logits [M, C] or None) of
+    Z = [x | x2] weight^T + bias (include/clipk.h: clipk_linear_ce_fwd).  want_stats=False: the logits alone."""
+    (M, K1, K2, C), x, weight, bias, labels, x2 = _linear_ce_prep(x, weight, bias, labels, x2)
+    dev = x.device
+    lse = torch.empty(M, dtype=torch.float32, device=dev) if want_stats else None
+    tgt = torch.empty(M, dtype=torch.float32, device=dev) if want_stats and labels is not None else None
+    pred = torch.empty(M, dtype=torch.int64, device=dev) if want_stats else None
+    logits = torch.empty((M, C), dtype=torch.float32, device=dev) if want_logits or not want_stats else None
+    lib = _lib()
+    check(_timed("linear_ce_fwd", 2.0 * M * C * (K1 + K2),
+                 lambda: lib.clipk_linear_ce_fwd(x.data_ptr(), K1, ptr(x2), K2, weight.data_ptr(), ptr(bias), ptr(labels), M,
+                                                 C, ptr(lse), ptr(tgt), ptr(pred), ptr(logits), C, _stream()),
+                 4.0 * (M * (K1 + K2) + C * (K1 + K2))), "clipk_linear_ce_fwd")
+    return lse, tgt, pred, logits
+
+
+def linear_ce_bwd(x, weight, bias, labels, lse, g, x2=None, dw=None, dbias=None, accumulate=False, want_w=True,
+                  want_bias=True, want_dx=False, want_dx2=False):
+    """Gradients of mean(lse - tgt) times the device scalar g (clipk_linear_ce_bwd).  dw / dbias: write (accumulate: add)
+    into these tensors, e.g. the parameters' .grad; otherwise new tensors where want_w / want_bias.  Returns
+    (dw, dbias, dx, dx2), None where not asked for."""
+    (M, K1, K2, C), x, weight, bias, labels, x2 = _linear_ce_prep(x, weight, bias, labels, x2)
+    _need_cuda(x, lse, g, dw, dbias)
+    dev = x.device
+    assert lse.dtype == torch.float32 and lse.shape == (M,) and lse.is_contiguous()
+    assert g.dtype == torch.float32 and g.numel() == 1
+    if dw is None and want_w:
+        assert not accumulate, "accumulate with a new dw tensor"
+        dw = torch.empty((C, K1 + K2), dtype=torch.float32, device=dev)
+    if dbias is None and want_bias:
+        assert not accumulate, "accumulate with a new dbias tensor"
+        dbias = torch.empty(C, dtype=torch.float32, device=dev)
+    assert dw is None or (dw.dtype == torch.float32 and dw.shape == (C, K1 + K2) and dw.is_contiguous())
+    assert dbias is None or (dbias.dtype == torch.float32 and dbias.shape == (C,) and dbias.is_contiguous())
+    dx = torch.empty((M, K1), dtype=torch.float32, device=dev) if want_dx else None
+    dx2 = torch.empty((M, K2), dtype=torch.float32, device=dev) if want_dx2 and K2 else None
+    if dw is None and dbias is None and dx is None and dx2 is None:
+        return None, None, None, None
+    lib = _lib()
+    ws = workspace(lib.clipk_linear_ce_workspace(M, K1, K2, C), dev, "linear_ce")
+    check(_timed("linear_ce_bwd", 4.0 * M * C * (K1 + K2),
+                 lambda: lib.clipk_linear_ce_bwd(x.data_ptr(), K1, ptr(x2), K2, weight.data_ptr(), ptr(bias),
+                                                 labels.data_ptr(), M, C, lse.data_ptr(), g.data_ptr(), int(bool(accumulate)),
+                                                 ptr(dw), ptr(dbias), ptr(dx), ptr(dx2), ws.data_ptr(), ws.numel(),
+                                                 _stream()),
+                 8.0 * M * (K1 + K2)), "clipk_linear_ce_bwd")
+    return dw, dbias, dx, dx2
+
+
 def _grad_outs(x):
     return (torch.empty, x.shape), (torch.empty, x.shape[:1])               # dx, dscale partials
 

@@ -463,6 +463,48 @@ int clipk_ce_logits_bwd(const float* S, int64_t ld, int M, int N, const float* S
                         int label_offset_row, int label_offset_col, const float* gscale,
                         float* dS, int64_t ldd, float* dS2, int64_t ldd2, void* stream);
 
+/* Linear + cross-entropy against INTEGER labels, exact f32 (v_mfma_f32_16x16x4_f32, classes padded to the 16-wide tile):
+ * the last layer and the loss of every classifier head of old/classifier.py (nn.Linear(h, num_classes) at :14,31,40,52
+ * under nn.CrossEntropyLoss()(logits, labels) at old/ablation.py:30 and torch.max(logits, 1) at :45).
+ *   Z[i,c] = sum_{k<K1} X1[i,k] W[c,k] + sum_{k<K2} X2[i,k] W[c,K1+k] + bias[c]          i < M, c < C
+ * X1 [M,K1], X2 [M,K2] contiguous; X2 == NULL together with K2 == 0 is a single input, two inputs are the
+ * torch.cat([rna_embeds, protein_embeds], -1) of old/ablation.py:29,44 without the concatenation.  W [C, K1+K2] is the
+ * nn.Linear weight, bias [C] may be NULL, labels device int64 [M].
+ * fwd, one pass over X: lse[i] = logsumexp_c Z[i,c]; tgt[i] = Z[i, labels[i]]; pred[i] = the first-occurrence argmax of
+ *   row i (equal logits: the lower class, torch.max(logits, 1)'s rule); logits[i * ldz + c] = Z[i,c] if logits != NULL.
+ *   Each of lse / tgt / pred / logits may be NULL (not all); labels may be NULL when tgt is.  The mean loss is
+ *   clipk_ce_combine(lse, tgt, NULL, NULL, M, 1, 0, M).  No workspace.
+ * bwd: with G[i,c] = g[0] / M * (exp(Z[i,c] - lse[i]) - [c == labels[i]]) (g: device scalar, the upstream gradient; Z
+ *   recomputed with the forward's bits): dW[C,K] (+)= G^T [X1|X2], dbias[C] (+)= sum_i G, dX1 = G W[:, :K1],
+ *   dX2 = G W[:, K1:], each written only where its pointer is non-NULL (not all NULL); accumulate != 0 adds into dW /
+ *   dbias (a parameter's .grad) as clipk_gemm_wgrad_f32 does.  The cross-workgroup partial sums of dW / dbias go to the
+ *   workspace and are added in split order by a last kernel: no float atomics, bitwise reproducible run to run.
+ *   DEVIATION from "one pass": G needs a row's whole contraction before any of dW can be formed.  An X tile could wait
+ *   in LDS (32 rows x 1024 f32 = 128 of 160 KiB), but the dW partial (C x K f32: 256 KiB at C = 64, K = 1024, up to 1 MiB)
+ *   would have to stay in the registers of the one workgroup that tile leaves room for, which holds only for C <= 16,
+ *   K <= 1024.  So the backward reads X twice at every shape: once for Z -> G (G [M, 16 ceil(C/16)]
+ *   goes to the workspace), once for G^T X.
+ * A label outside [0, C): tgt = NaN (so the loss is NaN), the row adds nothing to any gradient (its dX rows are zero),
+ * pred is still valid; nothing is read or written out of bounds.
+ * Supported: 1 <= C <= 64, K1 % 4 == 0, K2 % 4 == 0, K1 + K2 <= 4096, M >= 1, X1 / X2 / W / dW / dX / workspace 16-byte
+ * aligned; anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED, and clipk_linear_ce_workspace returns 0.
+ * Never allocates, never synchronises, capturable.  workspace (bwd only): clipk_linear_ce_workspace(M, K1, K2, C) bytes.
+ * Accuracy (u = 2^-24): a logit is a chain of K fused multiply-adds in a fixed permutation of k and one addition of the
+ * bias: |Z~ - Z| <= (K + 4) u (sum_k |x_k w_k| + |b|); lse and tgt carry that error plus a few u of expf / logf.
+ * What bounds it (measured on an MI355X at M = 131072, K = 1024; record: profiles/probe/README.md): at C = 16 the X
+ * stream - the forward reads X at 3.9 TB/s, 63 % of the HBM copy rate, with the f32 matrix pipe at 20 % of its peak.  At
+ * C = 64 neither is saturated (1.8 TB/s, 59 of 155 TFLOP/s): per 16 rows x 16 columns of X a wave issues 4 ceil(C/16)
+ * MFMAs and re-reads ceil(C/16) float4s of W from cache, and that traffic and the unpipelined loop bind before the
+ * roughly balanced X stream and matrix pipe of the model do. */
+size_t clipk_linear_ce_workspace(int M, int K1, int K2, int C);
+int clipk_linear_ce_fwd(const float* X1, int K1, const float* X2, int K2, const float* W, const float* bias,
+                        const int64_t* labels, int M, int C, float* lse /*[M]*/, float* tgt /*[M]*/,
+                        int64_t* pred /*[M]*/, float* logits, int64_t ldz, void* stream);
+int clipk_linear_ce_bwd(const float* X1, int K1, const float* X2, int K2, const float* W, const float* bias,
+                        const int64_t* labels, int M, int C, const float* lse, const float* g, int accumulate,
+                        float* dW /*[C,K1+K2]*/, float* dbias /*[C]*/, float* dX1 /*[M,K1]*/, float* dX2 /*[M,K2]*/,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* out[cols, rows] = scale_dev[0] * in[rows, cols]^T (f32; scale_dev NULL = 1).  Operand preparation of the exact-f32
  * products that differentiate the materialised logits (d/dA = scale * dS · B, d/dB = scale * dS^T · A of
  * old/clip.py:67) and of the ICNN's transposed weights (triple_flow/2_icnn_core.py:181-211). */
