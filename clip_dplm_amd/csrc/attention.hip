@@ -2397,20 +2397,51 @@ static inline int set_dropout(AP& p, float dropout_p, unsigned seed) {
     return FN<160, 0, 0>(P, ST);                                            \
   } while (0)
 
-extern "C" int clipk_attn_fwd(const void* qkv, const uint8_t* key_mask, const float* rope_cos, const float* rope_sin,
-                              void* out, float* lse, int B, int L, int H, int D, float q_scale, float dropout_p,
-                              uint32_t dropout_seed, void* stream) {
-  if ((rope_cos == nullptr) != (rope_sin == nullptr)) return CLIPK_ERR_BAD_ARG;
+// What the six attention entry points share: the checks (one order, one set of codes for both layouts) and the AP fill.
+// Padded batch: cu == nullptr, T unused, L;  ATTN_PACKED: key_mask == nullptr, cu / T, L = max_len.
+// ATTN_ROT: the in-place-rotation entry points, RoPE tables required.  ATTN_BWD: dout / delta / dqkv are operands too
+// (forward: nullptr).
+enum { ATTN_PACKED = 1, ATTN_ROT = 2, ATTN_BWD = 4 };
+static int attn_params(AP& p, int kind, const void* qkv, const uint8_t* key_mask, const int* cu, int T,
+                       const float* rope_cos, const float* rope_sin, const void* out, const float* lse,
+                       const void* dout, float* delta, void* dqkv, int B, int L, int H, int D, float q_scale,
+                       int prerotated) {
+  const bool packed = kind & ATTN_PACKED, bwd = kind & ATTN_BWD;
+  if ((rope_cos == nullptr) != (rope_sin == nullptr) || ((kind & ATTN_ROT) && !rope_cos)) return CLIPK_ERR_BAD_ARG;
   const bool rope = rope_cos != nullptr;
   int rc = check_common(qkv, B, L, H, D, rope);
   if (rc) return rc;
+  if (packed && (!cu || T <= 0 || L > T)) return CLIPK_ERR_BAD_ARG;
   if (!out || !lse || !aligned16(out)) return CLIPK_ERR_BAD_ARG;
-  AP p{};
+  if (bwd && (!dout || !delta || !dqkv || !aligned16(dout) || !aligned16(dqkv))) return CLIPK_ERR_BAD_ARG;
   p.qkv = (const unsigned short*)qkv; p.key_mask = key_mask; p.cosT = rope_cos; p.sinT = rope_sin;
-  p.out = (unsigned short*)out; p.lse = lse; p.B = B; p.L = L; p.H = H; p.D = D; p.scale = q_scale;
-  rc = set_dropout(p, dropout_p, dropout_seed);
+  p.out = (unsigned short*)out; p.lse = const_cast<float*>(lse);
+  p.dout = (const unsigned short*)dout; p.delta = delta; p.dqkv = (unsigned short*)dqkv;
+  p.B = B; p.L = L; p.H = H; p.D = D; p.scale = q_scale;
+  p.cu = cu; p.T = T;
+  p.pre_rot = (rope && prerotated) ? (prerotated == 2 ? 2 : 1) : 0;
+  return CLIPK_OK;
+}
+
+// the whole-head forward that rotates q / k in place while it stages them (whole_fwd_applies shapes)
+static int launch_fwd_rot(const AP& p, hipStream_t st) {
+  switch (p.D) {
+    case 16: launch_fwd_whole<16, true>(p, st); break;
+    case 24: launch_fwd_whole<24, true>(p, st); break;
+    default: launch_fwd_whole<32, true>(p, st); break;
+  }
+  return clipk_check_launch();
+}
+
+extern "C" int clipk_attn_fwd(const void* qkv, const uint8_t* key_mask, const float* rope_cos, const float* rope_sin,
+                              void* out, float* lse, int B, int L, int H, int D, float q_scale, float dropout_p,
+                              uint32_t dropout_seed, void* stream) {
+  AP p{};
+  int rc = attn_params(p, 0, qkv, key_mask, nullptr, 0, rope_cos, rope_sin, out, lse, nullptr, nullptr, nullptr, B, L, H, D,
+                       q_scale, 0);
+  if (!rc) rc = set_dropout(p, dropout_p, dropout_seed);
   if (rc) return rc;
-  ATTN_DISPATCH(launch_fwd, D, rope, p, (hipStream_t)stream);
+  ATTN_DISPATCH(launch_fwd, D, p.cosT != nullptr, p, (hipStream_t)stream);
 }
 
 extern "C" int clipk_rope_qk(void* qkv, const float* rope_cos, const float* rope_sin, int B, int L, int H, int D,
@@ -2434,46 +2465,28 @@ extern "C" int clipk_rope_qk(void* qkv, const float* rope_cos, const float* rope
 
 extern "C" int clipk_attn_fwd_rot(void* qkv, const uint8_t* key_mask, const float* rope_cos, const float* rope_sin,
                                   void* out, float* lse, int B, int L, int H, int D, float q_scale, void* stream) {
-  if (!rope_cos || !rope_sin) return CLIPK_ERR_BAD_ARG;
-  int rc = check_common(qkv, B, L, H, D, true);
+  AP p{};
+  int rc = attn_params(p, ATTN_ROT, qkv, key_mask, nullptr, 0, rope_cos, rope_sin, out, lse, nullptr, nullptr, nullptr,
+                       B, L, H, D, q_scale, 0);
   if (rc) return rc;
-  if (!out || !lse || !aligned16(out)) return CLIPK_ERR_BAD_ARG;
   if (!whole_fwd_applies(L, D)) {                           // every other shape: the two calls it stands for
     rc = clipk_rope_qk(qkv, rope_cos, rope_sin, B, L, H, D, stream);
     if (rc) return rc;
     return clipk_attn_fwd(qkv, key_mask, nullptr, nullptr, out, lse, B, L, H, D, q_scale, 0.f, 0u, stream);
   }
-  AP p{};
-  p.qkv = (const unsigned short*)qkv; p.key_mask = key_mask; p.cosT = rope_cos; p.sinT = rope_sin;
-  p.out = (unsigned short*)out; p.lse = lse; p.B = B; p.L = L; p.H = H; p.D = D; p.scale = q_scale;
-  hipStream_t st = (hipStream_t)stream;
-  switch (D) {
-    case 16: launch_fwd_whole<16, true>(p, st); break;
-    case 24: launch_fwd_whole<24, true>(p, st); break;
-    default: launch_fwd_whole<32, true>(p, st); break;
-  }
-  return clipk_check_launch();
+  return launch_fwd_rot(p, (hipStream_t)stream);
 }
 
 extern "C" int clipk_attn_bwd(const void* qkv, const uint8_t* key_mask, const float* rope_cos, const float* rope_sin,
                               const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                               int B, int L, int H, int D, float q_scale, int prerotated, float dropout_p,
                               uint32_t dropout_seed, void* stream) {
-  if ((rope_cos == nullptr) != (rope_sin == nullptr)) return CLIPK_ERR_BAD_ARG;
-  const bool rope = rope_cos != nullptr;
-  int rc = check_common(qkv, B, L, H, D, rope);
-  if (rc) return rc;
-  if (!out || !dout || !lse || !delta || !dqkv) return CLIPK_ERR_BAD_ARG;
-  if (!aligned16(out) || !aligned16(dout) || !aligned16(dqkv)) return CLIPK_ERR_BAD_ARG;
   AP p{};
-  p.qkv = (const unsigned short*)qkv; p.key_mask = key_mask; p.cosT = rope_cos; p.sinT = rope_sin;
-  p.out = (unsigned short*)out; p.lse = const_cast<float*>(lse);
-  p.dout = (const unsigned short*)dout; p.delta = delta; p.dqkv = (unsigned short*)dqkv;
-  p.B = B; p.L = L; p.H = H; p.D = D; p.scale = q_scale;
-  p.pre_rot = (rope && prerotated) ? (prerotated == 2 ? 2 : 1) : 0;
-  rc = set_dropout(p, dropout_p, dropout_seed);
+  int rc = attn_params(p, ATTN_BWD, qkv, key_mask, nullptr, 0, rope_cos, rope_sin, out, lse, dout, delta, dqkv, B, L, H, D,
+                       q_scale, prerotated);
+  if (!rc) rc = set_dropout(p, dropout_p, dropout_seed);
   if (rc) return rc;
-  ATTN_DISPATCH(launch_bwd, D, rope, p, (hipStream_t)stream);
+  ATTN_DISPATCH(launch_bwd, D, p.cosT != nullptr, p, (hipStream_t)stream);
 }
 
 // ---- packed variable-length batches: no padded token ever exists, so the Linear / LayerNorm kernels see only real rows
@@ -2484,18 +2497,12 @@ extern "C" int clipk_attn_bwd(const void* qkv, const uint8_t* key_mask, const fl
 extern "C" int clipk_attn_varlen_fwd(const void* qkv, const int* cu_seqlens, const float* rope_cos, const float* rope_sin,
                                      void* out, float* lse, int B, int T, int max_len, int H, int D, float q_scale,
                                      float dropout_p, uint32_t dropout_seed, void* stream) {
-  if ((rope_cos == nullptr) != (rope_sin == nullptr)) return CLIPK_ERR_BAD_ARG;
-  const bool rope = rope_cos != nullptr;
-  int rc = check_common(qkv, B, max_len, H, D, rope);
-  if (rc) return rc;
-  if (!cu_seqlens || T <= 0 || max_len > T || !out || !lse || !aligned16(out)) return CLIPK_ERR_BAD_ARG;
   AP p{};
-  p.qkv = (const unsigned short*)qkv; p.key_mask = nullptr; p.cosT = rope_cos; p.sinT = rope_sin;
-  p.out = (unsigned short*)out; p.lse = lse; p.B = B; p.L = max_len; p.H = H; p.D = D; p.scale = q_scale;
-  p.cu = cu_seqlens; p.T = T;
-  rc = set_dropout(p, dropout_p, dropout_seed);
+  int rc = attn_params(p, ATTN_PACKED, qkv, nullptr, cu_seqlens, T, rope_cos, rope_sin, out, lse, nullptr, nullptr, nullptr,
+                       B, max_len, H, D, q_scale, 0);
+  if (!rc) rc = set_dropout(p, dropout_p, dropout_seed);
   if (rc) return rc;
-  ATTN_DISPATCH(launch_fwd, D, rope, p, (hipStream_t)stream);
+  ATTN_DISPATCH(launch_fwd, D, p.cosT != nullptr, p, (hipStream_t)stream);
 }
 
 // clipk_attn_fwd_rot for a packed batch: q / k of every sequence rotated IN PLACE (positions count from the sequence's
@@ -2505,42 +2512,22 @@ extern "C" int clipk_attn_varlen_fwd(const void* qkv, const int* cu_seqlens, con
 extern "C" int clipk_attn_varlen_fwd_rot(void* qkv, const int* cu_seqlens, const float* rope_cos, const float* rope_sin,
                                          void* out, float* lse, int B, int T, int max_len, int H, int D, float q_scale,
                                          void* stream) {
-  if (!rope_cos || !rope_sin) return CLIPK_ERR_BAD_ARG;
-  int rc = check_common(qkv, B, max_len, H, D, true);
-  if (rc) return rc;
-  if (!cu_seqlens || T <= 0 || max_len > T || !out || !lse || !aligned16(out)) return CLIPK_ERR_BAD_ARG;
-  if (!whole_fwd_applies(max_len, D)) return CLIPK_ERR_UNSUPPORTED;
   AP p{};
-  p.qkv = (const unsigned short*)qkv; p.key_mask = nullptr; p.cosT = rope_cos; p.sinT = rope_sin;
-  p.out = (unsigned short*)out; p.lse = lse; p.B = B; p.L = max_len; p.H = H; p.D = D; p.scale = q_scale;
-  p.cu = cu_seqlens; p.T = T;
-  hipStream_t st = (hipStream_t)stream;
-  switch (D) {
-    case 16: launch_fwd_whole<16, true>(p, st); break;
-    case 24: launch_fwd_whole<24, true>(p, st); break;
-    default: launch_fwd_whole<32, true>(p, st); break;
-  }
-  return clipk_check_launch();
+  int rc = attn_params(p, ATTN_PACKED | ATTN_ROT, qkv, nullptr, cu_seqlens, T, rope_cos, rope_sin, out, lse, nullptr,
+                       nullptr, nullptr, B, max_len, H, D, q_scale, 0);
+  if (rc) return rc;
+  if (!whole_fwd_applies(max_len, D)) return CLIPK_ERR_UNSUPPORTED;
+  return launch_fwd_rot(p, (hipStream_t)stream);
 }
 
 extern "C" int clipk_attn_varlen_bwd(const void* qkv, const int* cu_seqlens, const float* rope_cos, const float* rope_sin,
                                      const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                                      int B, int T, int max_len, int H, int D, float q_scale, int prerotated,
                                      float dropout_p, uint32_t dropout_seed, void* stream) {
-  if ((rope_cos == nullptr) != (rope_sin == nullptr)) return CLIPK_ERR_BAD_ARG;
-  const bool rope = rope_cos != nullptr;
-  int rc = check_common(qkv, B, max_len, H, D, rope);
-  if (rc) return rc;
-  if (!cu_seqlens || T <= 0 || max_len > T || !out || !dout || !lse || !delta || !dqkv) return CLIPK_ERR_BAD_ARG;
-  if (!aligned16(out) || !aligned16(dout) || !aligned16(dqkv)) return CLIPK_ERR_BAD_ARG;
   AP p{};
-  p.qkv = (const unsigned short*)qkv; p.key_mask = nullptr; p.cosT = rope_cos; p.sinT = rope_sin;
-  p.out = (unsigned short*)out; p.lse = const_cast<float*>(lse);
-  p.dout = (const unsigned short*)dout; p.delta = delta; p.dqkv = (unsigned short*)dqkv;
-  p.B = B; p.L = max_len; p.H = H; p.D = D; p.scale = q_scale;
-  p.cu = cu_seqlens; p.T = T;
-  p.pre_rot = (rope && prerotated) ? (prerotated == 2 ? 2 : 1) : 0;
-  rc = set_dropout(p, dropout_p, dropout_seed);
+  int rc = attn_params(p, ATTN_PACKED | ATTN_BWD, qkv, nullptr, cu_seqlens, T, rope_cos, rope_sin, out, lse, dout, delta,
+                       dqkv, B, max_len, H, D, q_scale, prerotated);
+  if (!rc) rc = set_dropout(p, dropout_p, dropout_seed);
   if (rc) return rc;
-  ATTN_DISPATCH(launch_bwd, D, rope, p, (hipStream_t)stream);
+  ATTN_DISPATCH(launch_bwd, D, p.cosT != nullptr, p, (hipStream_t)stream);
 }

@@ -45,7 +45,9 @@ DIRECT_PARAM_GRADS = True      # weight-gradient kernels accumulate straight int
 # with permuted rows, csrc/common.h il_src), so that RoPE runs in the projection's epilogue on neighbouring columns - on the
 # f32 value, before its one bf16 rounding - and the attention forward neither rotates nor writes rotated rows back.  q . k
 # is invariant under a common order of the head dim; the backward's RoPE^T and the weight-gradient rows undo the order.
-# Whole-head attention shapes only (128 < L <= 256, head dim <= 32); CLIPK_ROPE_INTERLEAVED=0 keeps the in-place rotation.
+# Taken by padded batches of any length whose head dim is a multiple of 8 other than 16 / 32 / 64 and whose width is a
+# multiple of 32, with PREROTATE_QK and ROPE_IN_QKV_EPILOGUE on (_rope_mode); CLIPK_ROPE_INTERLEAVED=0 keeps the in-place
+# rotation.
 ROPE_INTERLEAVED = os.environ.get("CLIPK_ROPE_INTERLEAVED", "1") != "0"
 
 
@@ -184,11 +186,62 @@ class _Lin:
 # =================================================================================================
 # ESM-2 (pre-LN) stack
 # =================================================================================================
-def _varlen_prerot(meta):
-    """Packed batch whose sequences all fit the whole-head attention kernels: q / k are rotated in place by the forward
-    kernel (clipk_attn_varlen_fwd_rot) and the backward runs one kernel per (sequence, head)."""
-    B, L, H, D, mask, rope, eps, seq = meta
-    return PREROTATE_QK and seq is not None and rope is not None and ops.varlen_whole_head_applies(seq[1], D)
+# How RoPE reaches q / k in one stack forward ("One attention path per stack forward"):
+_ROPE_NONE = 0           # no RoPE (every post-LN stack)
+_ROPE_EPILOGUE = 1       # padded, head dims that tile the qkv GEMM's 64-column wave slices: rotated in its epilogue
+_ROPE_INTERLEAVED = 2    # padded, the other head dims: pair-interleaved q / k, rotated in the epilogue (ROPE_INTERLEAVED)
+_ROPE_IN_PLACE = 3       # rotated once, in place, by the attention forward; `qkv` (saved for backward) holds rotated q / k
+_ROPE_STAGING = 4        # the attention kernels rotate every row they stage, forward and backward
+_PREROTATED = (0, 1, 2, 1, 0)        # the `prerotated` argument of the attention backward, by mode
+
+
+def _rope_mode(rope, seq, D, d):
+    if rope is None:
+        return _ROPE_NONE
+    if seq is not None:                                    # packed batch: the whole-head kernels rotate in place
+        return _ROPE_IN_PLACE if PREROTATE_QK and ops.varlen_whole_head_applies(seq[1], D) else _ROPE_STAGING
+    if PREROTATE_QK and ROPE_IN_QKV_EPILOGUE and D in (16, 32, 64):
+        return _ROPE_EPILOGUE
+    if (ROPE_INTERLEAVED and PREROTATE_QK and ROPE_IN_QKV_EPILOGUE and D % 8 == 0 and D not in (16, 32, 64)
+            and d % 32 == 0):
+        return _ROPE_INTERLEAVED
+    return _ROPE_IN_PLACE if PREROTATE_QK else _ROPE_STAGING
+
+
+class _Attn:
+    """The self-attention of ONE stack forward: geometry, layout (padded with `mask`, or packed with seq = (cu_seqlens,
+    max_len)) and the RoPE mode, chosen here once from the module switches and the shapes.  The stack's backward gets this
+    object from its forward and never looks at the switches again."""
+
+    def __init__(self, B, L, H, D, mask, seq, q_scale, rope=None, d=0):
+        self.B, self.L, self.H, self.D, self.mask, self.seq, self.q_scale, self.rope = B, L, H, D, mask, seq, q_scale, rope
+        self.mode = _rope_mode(rope, seq, D, d)
+        # operand of the qkv projection's RoPE epilogue (both epilogue modes rotate the leading 2 H D columns)
+        self.gemm_rope = (rope[0], rope[1], L, D, 2 * H * D) if self.mode in (_ROPE_EPILOGUE, _ROPE_INTERLEAVED) else None
+
+    def fwd(self, qkv, dropout=None):
+        """-> (ctx, lse).  In-place mode rotates the q / k sections of `qkv`."""
+        B, L, H, D = self.B, self.L, self.H, self.D
+        rope = self.rope if self.mode == _ROPE_STAGING else None
+        if self.seq is not None:
+            cu, max_len = self.seq
+            if self.mode == _ROPE_IN_PLACE:
+                return ops.attn_varlen_fwd_rot_(qkv, cu, max_len, H, D, self.rope, q_scale=self.q_scale)
+            return ops.attn_varlen_fwd(qkv, cu, max_len, H, D, rope=rope, q_scale=self.q_scale, dropout=dropout)
+        if self.mode == _ROPE_IN_PLACE:
+            # RoPE once: the attention kernels would otherwise rotate every K row 5x and every Q row 4x per layer while
+            # staging it (one call; for the short ESM heads also one kernel, which rotates the rows while it stages them)
+            return ops.attn_fwd_rot_(qkv, B, L, H, D, self.rope, key_mask=self.mask, q_scale=self.q_scale)
+        return ops.attn_fwd(qkv, B, L, H, D, key_mask=self.mask, rope=rope, q_scale=self.q_scale, dropout=dropout)
+
+    def bwd(self, qkv, ctx, dctx, lse, dropout=None):
+        """-> dqkv, for the `qkv` the forward of this object left behind."""
+        pre = _PREROTATED[self.mode]
+        if self.seq is not None:
+            return ops.attn_varlen_bwd(qkv, ctx, dctx, lse, self.seq[0], self.seq[1], self.H, self.D, rope=self.rope,
+                                       q_scale=self.q_scale, dropout=dropout, prerotated=pre)
+        return ops.attn_bwd(qkv, ctx, dctx, lse, self.B, self.L, self.H, self.D, key_mask=self.mask, rope=self.rope,
+                            q_scale=self.q_scale, prerotated=pre, dropout=dropout)
 
 
 # What the FFN keeps for its backward: the bf16 pre-activation u (GELU' recomputed from it), or - default - GELU'(u) itself
@@ -198,36 +251,12 @@ def _varlen_prerot(meta):
 GELU_AUX_U8 = os.environ.get("CLIPK_GELU_AUX", "u8") != "bf16"
 
 
-def _esm_layer_fwd(x, p, meta, keep=True):
+def _esm_layer_fwd(x, p, attn, eps, keep=True):
     """x: f32 [T,d].  p: dict of this layer's tensors.  Returns y f32 [T,d] and the saved activations."""
-    B, L, H, D, mask, rope, eps, seq = meta
     _, h1, m1, r1 = ops.layernorm_fwd(x, p["ln1_w"], p["ln1_b"], eps, want_f32=False, want_bf16=True)
-    if seq is None and PREROTATE_QK and ROPE_IN_QKV_EPILOGUE and rope is not None and D in (16, 32, 64):
-        # heads that tile the GEMM's 64-column wave slices (ESM-2-650M: 20 x 64): q / k leave the projection's epilogue
-        # already rotated - no second pass over them.  (hd = 24 of the 35M model does not tile: branch below.)
-        qkv = ops.gemm_nt(h1, p["qkv"].wb, bias=p["qkv"].b, rope=(rope[0], rope[1], L, D, 2 * H * D))
-        ctx, lse = ops.attn_fwd(qkv, B, L, H, D, key_mask=mask, rope=None, q_scale=D ** -0.5)
-        x2 = ops.gemm_nt(ctx, p["out"].wb, bias=p["out"].b, residual=x, out_dtype=torch.float32)
-        return _esm_layer_ffn_fwd(x, x2, p, eps, keep, (h1, m1, r1, qkv, ctx, lse))
-    if p["qkv"].il[1]:
-        # pair-interleaved q / k (see ROPE_INTERLEAVED): rotated in the projection's epilogue; attention as it is
-        il_hd, il_rows = p["qkv"].il
-        qkv = ops.gemm_nt(h1, p["qkv"].wb, bias=p["qkv_b_il"], rope=(rope[0], rope[1], L, D, il_rows), rope_interleaved=True)
-        ctx, lse = ops.attn_fwd(qkv, B, L, H, D, key_mask=mask, rope=None, q_scale=D ** -0.5)
-        x2 = ops.gemm_nt(ctx, p["out"].wb, bias=p["out"].b, residual=x, out_dtype=torch.float32)
-        return _esm_layer_ffn_fwd(x, x2, p, eps, keep, (h1, m1, r1, qkv, ctx, lse))
-    qkv = ops.gemm_nt(h1, p["qkv"].wb, bias=p["qkv"].b)
-    if seq is not None and _varlen_prerot(meta):           # packed batch of short sequences: whole-head kernel, q / k
-        ctx, lse = ops.attn_varlen_fwd_rot_(qkv, seq[0], seq[1], H, D, rope, q_scale=D ** -0.5)   # rotated in place
-    elif seq is not None:                                  # packed variable-length batch: rows [cu[b], cu[b+1])
-        ctx, lse = ops.attn_varlen_fwd(qkv, seq[0], seq[1], H, D, rope=rope, q_scale=D ** -0.5)
-    elif PREROTATE_QK and rope is not None:
-        # RoPE once, in place: the attention kernels would otherwise rotate every K row 5x and every Q row 4x per
-        # layer while staging it.  `qkv` (saved for backward) then holds rotated q / k.
-        # (one call; for the short ESM heads also one kernel, which rotates the rows while it stages them.)
-        ctx, lse = ops.attn_fwd_rot_(qkv, B, L, H, D, rope, key_mask=mask, q_scale=D ** -0.5)
-    else:
-        ctx, lse = ops.attn_fwd(qkv, B, L, H, D, key_mask=mask, rope=rope, q_scale=D ** -0.5)
+    il = attn.mode == _ROPE_INTERLEAVED                    # then the bias, like the weight copy, is in the il column order
+    qkv = ops.gemm_nt(h1, p["qkv"].wb, bias=p["qkv_b_il"] if il else p["qkv"].b, rope=attn.gemm_rope, rope_interleaved=il)
+    ctx, lse = attn.fwd(qkv)
     x2 = ops.gemm_nt(ctx, p["out"].wb, bias=p["out"].b, residual=x, out_dtype=torch.float32)
     return _esm_layer_ffn_fwd(x, x2, p, eps, keep, (h1, m1, r1, qkv, ctx, lse))
 
@@ -251,10 +280,9 @@ def _esm_layer_ffn_fwd(x, x2, p, eps, keep, att):
 ESM_BF16_GRAD_STREAM = os.environ.get("CLIPK_ESM_F32_GRAD_STREAM", "0") != "1"
 
 
-def _esm_layer_bwd(dy, dyb, p, saved, meta, need_dx_bf16, need_dx_f32=True):
+def _esm_layer_bwd(dy, dyb, p, saved, attn, need_dx_bf16, need_dx_f32=True):
     """dy f32 [T,d] or None (bf16 gradient stream) + its bf16 copy dyb.  Returns dx f32 (or None), dx bf16 (or None)
     and the parameter grads."""
-    B, L, H, D, mask, rope, eps, seq = meta
     x, h1, m1, r1, qkv, ctx, lse, x2, h2, m2, r2, g, u = saved
     if dyb is None:
         dyb = ops.to_bf16(dy)
@@ -268,12 +296,7 @@ def _esm_layer_bwd(dy, dyb, p, saved, meta, need_dx_bf16, need_dx_f32=True):
                                                   want_f32=not lowp, want_bf16=True)
     dctx = ops.gemm_nt(dx2b, p["out"].wtb)
     gr["out_w"], gr["out_b"] = _wgrad(dx2b, ctx, p["out"])
-    if seq is not None:
-        dqkv = ops.attn_varlen_bwd(qkv, ctx, dctx, lse, seq[0], seq[1], H, D, rope=rope, q_scale=D ** -0.5,
-                                   prerotated=_varlen_prerot(meta))
-    else:
-        dqkv = ops.attn_bwd(qkv, ctx, dctx, lse, B, L, H, D, key_mask=mask, rope=rope, q_scale=D ** -0.5,
-                            prerotated=2 if p["qkv"].il[1] else (PREROTATE_QK and rope is not None))
+    dqkv = attn.bwd(qkv, ctx, dctx, lse)
     dh1 = ops.gemm_nt(dqkv, p["qkv"].wtb)
     gr["qkv_w"], gr["qkv_b"] = _wgrad(dqkv, h1, p["qkv"], il=p["qkv"].il)
     want32 = need_dx_f32 or not lowp
@@ -296,17 +319,14 @@ class EsmStackFn(torch.autograd.Function):
         B, L = ids.shape                                    # packed batches come as [T, 1] with seq = (cu, max_len)
         d, H = module.hidden_size, module.num_heads
         D = d // H
-        rope = module.rope(L if seq is None else seq[1], ids.device)
-        meta = (B, L, H, D, mask_u8, rope, module.eps, seq)
+        attn = _Attn(B, L, H, D, mask_u8, seq, D ** -0.5, module.rope(L if seq is None else seq[1], ids.device), d)
         x = ops.embed_fwd(ids, table, row_scale=row_scale, mask=mask_u8.view(-1) if mask_u8 is not None else None,
                           mask_token_id=module.mask_token_id if module.token_dropout else -1)
         layers, saved = [], []
         need_bwd = any(ctx.needs_input_grad)        # frozen encoder (3_esm_integration.py:83-84): keep no activations
         if need_bwd:
             _bucket_begin(module)
-        # head dims the tiled RoPE epilogue cannot take (24: ESM-2-35M) get the pair-interleaved one (ROPE_INTERLEAVED)
-        use_il = (ROPE_INTERLEAVED and PREROTATE_QK and ROPE_IN_QKV_EPILOGUE and seq is None and D % 8 == 0
-                  and D not in (16, 32, 64) and d % 32 == 0)
+        use_il = attn.mode == _ROPE_INTERLEAVED
         il_idx = module.il_index(ids.device) if use_il else None
         for i in range(nl):
             t = flat[3 + 12 * i: 3 + 12 * (i + 1)]
@@ -320,7 +340,7 @@ class EsmStackFn(torch.autograd.Function):
                  "ln2_w": t[6], "ln2_b": t[7], "fc1": _Lin(t[8], t[9], caches[2]), "fc2": _Lin(t[10], t[11], caches[3])}
             if use_il:
                 p["qkv_b_il"] = t[3].detach().index_select(0, il_idx)   # the bias in the projection's column order
-            x, s = _esm_layer_fwd(x, p, meta, keep=need_bwd)
+            x, s = _esm_layer_fwd(x, p, attn, module.eps, keep=need_bwd)
             layers.append(p)
             saved.append(s if need_bwd else None)
         ctx.pool = None
@@ -330,7 +350,7 @@ class EsmStackFn(torch.autograd.Function):
             ctx.pool = (wrow, B, L)
         else:
             y, _, mf, rf = ops.layernorm_fwd(x, fin_w, fin_b, module.eps, want_f32=True)
-        ctx.module, ctx.meta, ctx.layers, ctx.saved = module, meta, layers, saved
+        ctx.module, ctx.attn, ctx.layers, ctx.saved = module, attn, layers, saved
         ctx.fin = (x, fin_w, fin_b, mf, rf)
         ctx.ids, ctx.row_scale = ids, row_scale
         ctx.table = table
@@ -341,7 +361,7 @@ class EsmStackFn(torch.autograd.Function):
         if ctx.saved is None:
             raise RuntimeError("EsmStackFn: second backward through the same forward: the stack frees each layer's "
                                "activations as its backward consumes them (retain_graph is not supported)")
-        module, meta = ctx.module, ctx.meta
+        module = ctx.module
         _bucket_backward_begin(module)
         x, fin_w, fin_b, mf, rf = ctx.fin
         nl = module.num_layers
@@ -351,13 +371,13 @@ class EsmStackFn(torch.autograd.Function):
                                               pool=ctx.pool)
         for i in reversed(range(nl)):
             # the last layer processed (i = 0) hands an f32 gradient to the embedding backward
-            dx, dxb, gr = _esm_layer_bwd(dx, dxb, ctx.layers[i], ctx.saved[i], meta, need_dx_bf16=i > 0,
+            dx, dxb, gr = _esm_layer_bwd(dx, dxb, ctx.layers[i], ctx.saved[i], ctx.attn, need_dx_bf16=i > 0,
                                          need_dx_f32=(i == 0) or not lowp)
             ctx.saved[i] = None                                     # free this layer's activations now
             for j, k in enumerate(_ESM_KEYS):
                 grads[3 + 12 * i + j] = gr[k]
         if ctx.needs_input_grad[6]:
-            mask_u8 = meta[4]
+            mask_u8 = ctx.attn.mask
             table = ctx.table
             direct = DIRECT_PARAM_GRADS and _direct_ok(table)       # the kernel accumulates: straight into table.grad
             dtable = table.grad if direct else torch.zeros(table.shape, dtype=torch.float32, device=dx.device)
@@ -582,13 +602,10 @@ def _post_layer_fwd(x, xb, p, meta, dr=None):
     """dr = None or (p_drop, seed_attn, seed_drop1, seed_ffn, seed_drop2): the four nn.Dropout sites of
     nn.TransformerEncoderLayer (attention probabilities; out_proj output; FFN activation; linear2 output), each a
     counter-based mask recomputed in the backward from the same seed."""
-    B, L, H, D, mask, act, eps, qs, seq, res16 = meta
+    attn, act, eps, res16 = meta
     da, d1, df, d2 = (None,) * 4 if dr is None else tuple((dr[0], sd) for sd in dr[1:])
     qkv = ops.gemm_nt(xb, p["in"].wb, bias=p["in"].b)
-    if seq is not None:
-        ctx, lse = ops.attn_varlen_fwd(qkv, seq[0], seq[1], H, D, rope=None, q_scale=qs, dropout=da)
-    else:
-        ctx, lse = ops.attn_fwd(qkv, B, L, H, D, key_mask=mask, rope=None, q_scale=qs, dropout=da)
+    ctx, lse = attn.fwd(qkv, dropout=da)
     s1 = ops.gemm_nt(ctx, p["out"].wb, bias=p["out"].b, residual=x, out_dtype=_SUM_DT, dropout=d1)
     if res16:
         _, x1b, m1, r1 = ops.layernorm_fwd(s1, p["n1_w"], p["n1_b"], eps, want_f32=False, want_bf16=True)
@@ -612,7 +629,7 @@ def _post_layer_fwd(x, xb, p, meta, dr=None):
 
 
 def _post_layer_bwd(dy, p, saved, meta, dr=None, need_dx=True):
-    B, L, H, D, mask, act, eps, qs, seq, res16 = meta
+    attn, act, eps, res16 = meta
     da, d1, df, d2 = (None,) * 4 if dr is None else tuple((dr[0], sd) for sd in dr[1:])
     xb, qkv, ctx, lse, s1, x1b, m1, r1, g, u, s2, m2, r2 = saved
     gr = {}
@@ -634,10 +651,7 @@ def _post_layer_bwd(dy, p, saved, meta, dr=None, need_dx=True):
                                                 dropout_bf16=d1)
     dctx = ops.gemm_nt(ds1b, p["out"].wtb)
     gr["out_w"], gr["out_b"] = _wgrad(ds1b, ctx, p["out"])
-    if seq is not None:
-        dqkv = ops.attn_varlen_bwd(qkv, ctx, dctx, lse, seq[0], seq[1], H, D, rope=None, q_scale=qs, dropout=da)
-    else:
-        dqkv = ops.attn_bwd(qkv, ctx, dctx, lse, B, L, H, D, key_mask=mask, rope=None, q_scale=qs, dropout=da)
+    dqkv = attn.bwd(qkv, ctx, dctx, lse, dropout=da)
     if not need_dx:                                   # first layer of a stack fed with features that need no gradient
         dx = None                                     # (the RNA tower of ProteinRNACLIP): its input dgrad is never used
     elif lowp:
@@ -660,7 +674,7 @@ class PostLNStackFn(torch.autograd.Function):
         nl = module.num_layers
         E, H = module.embed_dim, module.nhead
         D = module.head_dim_padded
-        meta = (B, L, H, D, mask_u8, module.activation, module.eps, float(E // H) ** -0.5, seq,
+        meta = (_Attn(B, L, H, D, mask_u8, seq, float(E // H) ** -0.5), module.activation, module.eps,
                 module.residual_dtype == "bf16" and POSTLN_BF16_RESIDUAL)
         x = x.contiguous()
         xb = ops.to_bf16(x)

@@ -1253,17 +1253,38 @@ def _drop(dropout):
     return (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF) if dropout else (0.0, 0)
 
 
+def _attn(entry, name, work, qkv, side, rope, B, L, H, D, tail, grads=None, packed=False):
+    """The body the six attention wrappers share: asserts, outputs, the timed call.  entry: the C entry point; name / work:
+    the kernel timer's; side: the key mask [B, L] (padded batch) or, packed, cu_seqlens int32 [B+1] with L the longest
+    sequence and B unused; tail: the entry point's arguments after the geometry; grads: None (forward -> (out, lse)) or
+    (out, dout, lse) (backward -> (dqkv, delta))."""
+    dev = qkv.device
+    if packed:
+        assert side.dtype == torch.int32 and side.is_contiguous()
+        rows = qkv.shape[0]
+        dims, stat = (side.numel() - 1, rows, int(L), H, D), (H, rows)
+    else:
+        rows = B * L
+        dims, stat = (B, L, H, D), (B, H, L)
+    if grads is None:                  # (result first, then the statistic: the allocator's block choice follows the order)
+        assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.shape == (rows, 3 * H * D)
+        res = torch.empty(rows, H * D, dtype=torch.bfloat16, device=dev)      # sizes unpacked: cheaper to parse
+        st = torch.empty(*stat, dtype=torch.float32, device=dev)
+        ptrs = (res.data_ptr(), st.data_ptr())
+    else:
+        res = torch.empty_like(qkv)
+        st = torch.empty(*stat, dtype=torch.float32, device=dev)
+        ptrs = (grads[0].data_ptr(), grads[1].data_ptr(), grads[2].data_ptr(), st.data_ptr(), res.data_ptr())
+    cos, sin = rope if rope is not None else (None, None)
+    fn, stream = getattr(_lib(), entry), _stream()
+    check(_timed(name, work, lambda: fn(qkv.data_ptr(), ptr(side), ptr(cos), ptr(sin), *ptrs, *dims, *tail, stream)), entry)
+    return res, st
+
+
 def attn_fwd(qkv, B, L, H, D, key_mask=None, rope=None, q_scale=1.0, dropout=None):
     _need_cuda(qkv, key_mask)
-    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.shape == (B * L, 3 * H * D)
-    out = torch.empty((B * L, H * D), dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
-    cos, sin = rope if rope is not None else (None, None)
-    check(_timed("attn_fwd", 4.0 * B * H * L * L * D,
-                 lambda: _lib().clipk_attn_fwd(qkv.data_ptr(), ptr(key_mask), ptr(cos), ptr(sin), out.data_ptr(),
-                                               lse.data_ptr(), B, L, H, D, float(q_scale), *_drop(dropout),
-                                               _stream())), "clipk_attn_fwd")
-    return out, lse
+    return _attn("clipk_attn_fwd", "attn_fwd", 4.0 * B * H * L * L * D, qkv, key_mask, rope, B, L, H, D,
+                 (float(q_scale), *_drop(dropout)))
 
 
 def rope_qk_(qkv, B, L, H, D, rope):
@@ -1279,28 +1300,14 @@ def attn_fwd_rot_(qkv, B, L, H, D, rope, key_mask=None, q_scale=1.0):
     """rope_qk_ + attn_fwd(rope=None) in one call (one kernel for short heads): rotates q / k of `qkv` in place and
     returns (out, lse) computed from the rotated values; backward: attn_bwd(rope=..., prerotated=True)."""
     _need_cuda(qkv, key_mask)
-    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.shape == (B * L, 3 * H * D)
-    out = torch.empty((B * L, H * D), dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
-    cos, sin = rope
-    check(_timed("attn_fwd", 4.0 * B * H * L * L * D,
-                 lambda: _lib().clipk_attn_fwd_rot(qkv.data_ptr(), ptr(key_mask), cos.data_ptr(), sin.data_ptr(),
-                                                   out.data_ptr(), lse.data_ptr(), B, L, H, D, float(q_scale),
-                                                   _stream())), "clipk_attn_fwd_rot")
-    return out, lse
+    return _attn("clipk_attn_fwd_rot", "attn_fwd", 4.0 * B * H * L * L * D, qkv, key_mask, rope, B, L, H, D,
+                 (float(q_scale),))
 
 
 def attn_bwd(qkv, out, dout, lse, B, L, H, D, key_mask=None, rope=None, q_scale=1.0, prerotated=False, dropout=None):
     _need_cuda(qkv, out, dout, lse)
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
-    cos, sin = rope if rope is not None else (None, None)
-    check(_timed("attn_bwd", 10.0 * B * H * L * L * D,
-                 lambda: _lib().clipk_attn_bwd(qkv.data_ptr(), ptr(key_mask), ptr(cos), ptr(sin), out.data_ptr(),
-                                               dout.data_ptr(), lse.data_ptr(), delta.data_ptr(), dqkv.data_ptr(), B, L,
-                                               H, D, float(q_scale), int(prerotated), *_drop(dropout),
-                                               _stream())), "clipk_attn_bwd")
-    return dqkv
+    return _attn("clipk_attn_bwd", "attn_bwd", 10.0 * B * H * L * L * D, qkv, key_mask, rope, B, L, H, D,
+                 (float(q_scale), int(prerotated), *_drop(dropout)), (out, dout, lse))[0]
 
 
 def attn_f32_fwd(qkv, B, L, H, D, key_mask=None, q_scale=1.0, dropout=None):
@@ -1342,38 +1349,16 @@ def dropout_f32(x, dropout, addend=None):
 def attn_varlen_fwd(qkv, cu_seqlens, max_len, H, D, rope=None, q_scale=1.0, dropout=None):
     """Packed variable-length self-attention: qkv bf16 [T, 3*H*D], cu_seqlens int32 [B+1] on the device."""
     _need_cuda(qkv, cu_seqlens)
-    T = qkv.shape[0]
-    B = cu_seqlens.numel() - 1
-    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.shape == (T, 3 * H * D)
-    assert cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
-    out = torch.empty((T, H * D), dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty((H, T), dtype=torch.float32, device=qkv.device)
-    cos, sin = rope if rope is not None else (None, None)
-    check(_timed("attn_fwd", 0.0,
-                 lambda: _lib().clipk_attn_varlen_fwd(qkv.data_ptr(), cu_seqlens.data_ptr(), ptr(cos), ptr(sin),
-                                                      out.data_ptr(), lse.data_ptr(), B, T, int(max_len), H, D,
-                                                      float(q_scale), *_drop(dropout), _stream())),
-          "clipk_attn_varlen_fwd")
-    return out, lse
+    return _attn("clipk_attn_varlen_fwd", "attn_fwd", 0.0, qkv, cu_seqlens, rope, None, max_len, H, D,
+                 (float(q_scale), *_drop(dropout)), packed=True)
 
 
 def attn_varlen_fwd_rot_(qkv, cu_seqlens, max_len, H, D, rope, q_scale=1.0):
     """attn_fwd_rot_ for a packed batch (whole-head kernel, D in {16, 24, 32}, 128 < max_len <= 256): q / k of `qkv`
     are rotated in place; backward: attn_varlen_bwd(..., prerotated=True)."""
     _need_cuda(qkv, cu_seqlens)
-    T = qkv.shape[0]
-    B = cu_seqlens.numel() - 1
-    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.shape == (T, 3 * H * D)
-    assert cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
-    out = torch.empty((T, H * D), dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty((H, T), dtype=torch.float32, device=qkv.device)
-    cos, sin = rope
-    check(_timed("attn_fwd", 0.0,
-                 lambda: _lib().clipk_attn_varlen_fwd_rot(qkv.data_ptr(), cu_seqlens.data_ptr(), cos.data_ptr(),
-                                                          sin.data_ptr(), out.data_ptr(), lse.data_ptr(), B, T,
-                                                          int(max_len), H, D, float(q_scale), _stream())),
-          "clipk_attn_varlen_fwd_rot")
-    return out, lse
+    return _attn("clipk_attn_varlen_fwd_rot", "attn_fwd", 0.0, qkv, cu_seqlens, rope, None, max_len, H, D,
+                 (float(q_scale),), packed=True)
 
 
 def varlen_whole_head_applies(max_len: int, D: int) -> bool:
@@ -1384,18 +1369,8 @@ def varlen_whole_head_applies(max_len: int, D: int) -> bool:
 def attn_varlen_bwd(qkv, out, dout, lse, cu_seqlens, max_len, H, D, rope=None, q_scale=1.0, dropout=None,
                     prerotated=False):
     _need_cuda(qkv, out, dout, lse, cu_seqlens)
-    T = qkv.shape[0]
-    B = cu_seqlens.numel() - 1
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty((H, T), dtype=torch.float32, device=qkv.device)
-    cos, sin = rope if rope is not None else (None, None)
-    check(_timed("attn_bwd", 0.0,
-                 lambda: _lib().clipk_attn_varlen_bwd(qkv.data_ptr(), cu_seqlens.data_ptr(), ptr(cos), ptr(sin),
-                                                      out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                                                      dqkv.data_ptr(), B, T, int(max_len), H, D, float(q_scale),
-                                                      int(bool(prerotated)), *_drop(dropout), _stream())),
-          "clipk_attn_varlen_bwd")
-    return dqkv
+    return _attn("clipk_attn_varlen_bwd", "attn_bwd", 0.0, qkv, cu_seqlens, rope, None, max_len, H, D,
+                 (float(q_scale), int(bool(prerotated)), *_drop(dropout)), (out, dout, lse), packed=True)[0]
 
 
 # --------------------------------------------------------------------------------------------------
