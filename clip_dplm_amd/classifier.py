@@ -3,7 +3,8 @@ constructor signatures, defaults and state_dict keys (a reference checkpoint loa
 
 Every head ends in nn.Linear(h, num_classes) under nn.CrossEntropyLoss (old/ablation.py:30).  Three entry points:
   forward(x)                          the logits - the reference's API (old/classifier.py:17,28,39,50)
-  loss(x, labels, x2=None, ...)       the fused Linear + cross-entropy (clipk_linear_ce_*): the logits never exist
+  loss(x, labels, x2=None, ...)       the fused Linear + cross-entropy (clipk_linear_ce_*; more than 64 classes: the
+                                      class-tiled clipk_linear_ce_tiled_*): the logits never exist
   predict(x, x2=None)                 the first-occurrence argmax of every row (torch.max(logits, 1) of ablation.py:46)
 x2: a second input whose columns follow x's - torch.cat([rna_embeds, protein_embeds], -1) of old/ablation.py:29,44.
 LinearClassifier, whose first layer is the fused one, reads the two sources in place; the other heads make the one
@@ -21,6 +22,22 @@ from . import ops
 def _seeds(n: int):
     """32-bit dropout seeds from torch's default CPU generator (torch.manual_seed() makes a run reproducible)."""
     return torch.randint(0, 2 ** 31 - 1, (n,), dtype=torch.int64).tolist()
+
+
+def _wide(last: nn.Linear) -> bool:
+    """More classes than clipk_linear_ce_* take: the class-tiled kernels (narrower heads keep the kernels they had)."""
+    return last.out_features > ops.LINEAR_CE_MAX_CLASSES
+
+
+def _fused_loss(x, last, labels, x2=None, return_pred=False):
+    fn = KF.linear_cross_entropy_tiled if _wide(last) else KF.linear_cross_entropy
+    return fn(x, last.weight, last.bias, labels, x2=x2, return_pred=return_pred)
+
+
+def _fused_pred(x, last, x2=None):
+    if _wide(last):
+        return ops.linear_ce_tiled_fwd(x, last.weight, last.bias, x2=x2)[2]
+    return ops.linear_ce_fwd(x, last.weight, last.bias, x2=x2)[2]
 
 
 def _rows(x, x2=None):
@@ -44,13 +61,11 @@ class _Head(nn.Module):
 
     def loss(self, x, labels, x2=None, return_pred=False):
         """Mean cross-entropy of the head's logits against integer `labels` [M] (and the detached predictions)."""
-        last = self._last()
-        return KF.linear_cross_entropy(self.features(_rows(x, x2)), last.weight, last.bias, labels, return_pred=return_pred)
+        return _fused_loss(self.features(_rows(x, x2)), self._last(), labels, return_pred=return_pred)
 
     @torch.no_grad()
     def predict(self, x, x2=None):
-        last = self._last()
-        return ops.linear_ce_fwd(self.features(_rows(x, x2)), last.weight, last.bias)[2]
+        return _fused_pred(self.features(_rows(x, x2)), self._last())
 
 
 class MLPClassifier(_Head):
@@ -143,13 +158,12 @@ class LinearClassifier(_Head):
 
     def loss(self, x, labels, x2=None, return_pred=False):
         x2 = None if x2 is None else x2.float().contiguous()
-        return KF.linear_cross_entropy(x.float().contiguous(), self.linear.weight, self.linear.bias, labels, x2=x2,
-                                       return_pred=return_pred)
+        return _fused_loss(x.float().contiguous(), self.linear, labels, x2=x2, return_pred=return_pred)
 
     @torch.no_grad()
     def predict(self, x, x2=None):
         x2 = None if x2 is None else x2.float().contiguous()
-        return ops.linear_ce_fwd(x.float().contiguous(), self.linear.weight, self.linear.bias, x2=x2)[2]
+        return _fused_pred(x.float().contiguous(), self.linear, x2=x2)
 
 
 class SimpleNonLinearClassifier(_Head):

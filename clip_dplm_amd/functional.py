@@ -346,6 +346,32 @@ def _grad_in_place(p) -> bool:
     return g is not None and g.dtype == torch.float32 and g.is_contiguous() and g.device == p.device and g.shape == p.shape
 
 
+def _linear_ce_backward(ctx, g, bwd):
+    """Backward of LinearCEFn / LinearCETiledFn; bwd: ops.linear_ce_bwd or its class-tiled sibling."""
+    x, weight, labels, lse = ctx.saved_tensors
+    bias, x2 = ctx.bias, ctx.x2
+    need = ctx.needs_input_grad
+    want_w, want_b = need[1], bias is not None and need[2]
+    want_dx, want_dx2 = need[0], x2 is not None and need[4]
+    g = g.reshape(1).contiguous().float()
+    w_here, b_here = want_w and _grad_in_place(weight), want_b and _grad_in_place(bias)
+    both_here = (w_here or not want_w) and (b_here or not want_b) and (w_here or b_here)
+    # straight into the parameters' .grad when every wanted parameter gradient goes there; otherwise one call into new
+    # tensors, and a gradient whose .grad exists is added to it here (what AccumulateGrad would do)
+    dw, db, dx, dx2 = bwd(x, weight, bias, labels, lse, g, x2=x2, dw=weight.grad if both_here and w_here else None,
+                          dbias=bias.grad if both_here and b_here else None, accumulate=both_here,
+                          want_w=want_w, want_bias=want_b, want_dx=want_dx, want_dx2=want_dx2)
+    if w_here:
+        if not both_here:
+            weight.grad.add_(dw)
+        dw = None
+    if b_here:
+        if not both_here:
+            bias.grad.add_(db)
+        db = None
+    return dx, dw, db, None, dx2
+
+
 class LinearCEFn(torch.autograd.Function):
     """mean_i CE([x | x2] W^T + b, labels) without the logits: nn.Linear(h, num_classes) + nn.CrossEntropyLoss() of
     old/classifier.py / old/ablation.py:30 on clipk_linear_ce_fwd / _bwd.  Returns (loss, pred); pred (int64, the
@@ -362,28 +388,23 @@ class LinearCEFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _gpred):
-        x, weight, labels, lse = ctx.saved_tensors
-        bias, x2 = ctx.bias, ctx.x2
-        need = ctx.needs_input_grad
-        want_w, want_b = need[1], bias is not None and need[2]
-        want_dx, want_dx2 = need[0], x2 is not None and need[4]
-        g = g.reshape(1).contiguous().float()
-        w_here, b_here = want_w and _grad_in_place(weight), want_b and _grad_in_place(bias)
-        both_here = (w_here or not want_w) and (b_here or not want_b) and (w_here or b_here)
-        # straight into the parameters' .grad when every wanted parameter gradient goes there; otherwise one call into new
-        # tensors, and a gradient whose .grad exists is added to it here (what AccumulateGrad would do)
-        dw, db, dx, dx2 = ops.linear_ce_bwd(x, weight, bias, labels, lse, g, x2=x2, dw=weight.grad if both_here and w_here else None,
-                                            dbias=bias.grad if both_here and b_here else None, accumulate=both_here,
-                                            want_w=want_w, want_bias=want_b, want_dx=want_dx, want_dx2=want_dx2)
-        if w_here:
-            if not both_here:
-                weight.grad.add_(dw)
-            dw = None
-        if b_here:
-            if not both_here:
-                bias.grad.add_(db)
-            db = None
-        return dx, dw, db, None, dx2
+        return _linear_ce_backward(ctx, g, ops.linear_ce_bwd)
+
+
+class LinearCETiledFn(torch.autograd.Function):
+    """LinearCEFn on the class-tiled kernels (clipk_linear_ce_tiled_fwd / _bwd): any class count up to 65536."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels, x2):
+        lse, tgt, pred = ops.linear_ce_tiled_fwd(x, weight, bias, labels, x2)
+        ctx.save_for_backward(x, weight, labels, lse)
+        ctx.bias, ctx.x2 = bias, x2
+        ctx.mark_non_differentiable(pred)
+        return ops.ce_combine(lse, tgt, None, None, 1.0, 0.0, float(x.shape[0])), pred
+
+    @staticmethod
+    def backward(ctx, g, _gpred):
+        return _linear_ce_backward(ctx, g, ops.linear_ce_tiled_bwd)
 
 
 def linear_cross_entropy(x, weight, bias, labels, x2=None, return_pred=False):
@@ -395,6 +416,16 @@ def linear_cross_entropy(x, weight, bias, labels, x2=None, return_pred=False):
     if labels is None:
         raise ValueError("linear_cross_entropy needs labels")
     loss, pred = LinearCEFn.apply(x, weight, bias, labels, x2)
+    return (loss, pred) if return_pred else loss
+
+
+def linear_cross_entropy_tiled(x, weight, bias, labels, x2=None, return_pred=False):
+    """linear_cross_entropy for wide heads: the class-tiled kernels take up to 65536 classes (the reference's 2,547 cell
+    types and 158 markers, run1/proposal.MD:3).  The same ValueErrors, with that class limit."""
+    ops._linear_ce_args(x, weight, bias, labels, x2, ops.LINEAR_CE_TILED_MAX_CLASSES)
+    if labels is None:
+        raise ValueError("linear_cross_entropy_tiled needs labels")
+    loss, pred = LinearCETiledFn.apply(x, weight, bias, labels, x2)
     return (loss, pred) if return_pred else loss
 
 

@@ -312,9 +312,14 @@ def ce_combine(lse_r, pos_r, lse_c, pos_c, w_row, w_col, bg):
     return out
 
 
-def _linear_ce_args(x, weight, bias, labels, x2):
-    """Checks shared by linear_ce_fwd / linear_ce_bwd (ValueError: the caller's mistake; nothing is launched).  Label VALUES
-    are not looked at - that would be a host sync; a label outside [0, C) makes the loss NaN (include/clipk.h).
+LINEAR_CE_MAX_CLASSES = 64           # clipk_linear_ce_*: a row's logits in at most four 16-class accumulator tiles
+LINEAR_CE_TILED_MAX_CLASSES = 65536  # clipk_linear_ce_tiled_*: the classes walked in 64-class tiles
+
+
+def _linear_ce_args(x, weight, bias, labels, x2, max_classes=LINEAR_CE_MAX_CLASSES):
+    """Checks shared by linear_ce_fwd / linear_ce_bwd and their class-tiled siblings (ValueError: the caller's mistake;
+    nothing is launched).  Label VALUES are not looked at - that would be a host sync; a label outside [0, C) makes the
+    loss NaN (include/clipk.h).  max_classes: the class limit of the kernels the caller is about to run.
     Returns (M, K1, K2, C)."""
     for name, t in (("x", x), ("weight", weight), ("bias", bias), ("x2", x2)):
         if t is not None and t.dtype != torch.float32:
@@ -334,15 +339,15 @@ def _linear_ce_args(x, weight, bias, labels, x2):
     devs = {t.device for t in (x, weight, bias, labels, x2) if t is not None}
     if len(devs) != 1:
         raise ValueError(f"linear_ce: tensors on different devices: {sorted(map(str, devs))}")
-    if C > 64:
-        raise ValueError(f"linear_ce: {C} classes; the fused kernel takes at most 64")
+    if C > max_classes:
+        raise ValueError(f"linear_ce: {C} classes; the fused kernel takes at most {max_classes}")
     if M < 1 or C < 1 or K1 < 1 or K1 % 4 or K2 % 4 or K1 + K2 > 4096:
         raise ValueError(f"linear_ce: K1 = {K1}, K2 = {K2} must be multiples of 4 with K1 + K2 <= 4096 (M = {M}, C = {C})")
     return M, K1, K2, C
 
 
-def _linear_ce_prep(x, weight, bias, labels, x2):
-    M, K1, K2, C = _linear_ce_args(x, weight, bias, labels, x2)
+def _linear_ce_prep(x, weight, bias, labels, x2, max_classes=LINEAR_CE_MAX_CLASSES):
+    M, K1, K2, C = _linear_ce_args(x, weight, bias, labels, x2, max_classes)
     _need_cuda(x, weight, bias, labels, x2)
     x, weight = x.contiguous(), weight.contiguous()
     x2 = None if x2 is None or K2 == 0 else x2.contiguous()
@@ -368,12 +373,11 @@ def linear_ce_fwd(x, weight, bias=None, labels=None, x2=None, want_logits=False,
     return lse, tgt, pred, logits
 
 
-def linear_ce_bwd(x, weight, bias, labels, lse, g, x2=None, dw=None, dbias=None, accumulate=False, want_w=True,
-                  want_bias=True, want_dx=False, want_dx2=False):
-    """Gradients of mean(lse - tgt) times the device scalar g (clipk_linear_ce_bwd).  dw / dbias: write (accumulate: add)
-    into these tensors, e.g. the parameters' .grad; otherwise new tensors where want_w / want_bias.  Returns
-    (dw, dbias, dx, dx2), None where not asked for."""
-    (M, K1, K2, C), x, weight, bias, labels, x2 = _linear_ce_prep(x, weight, bias, labels, x2)
+def _linear_ce_bwd(tiled, x, weight, bias, labels, lse, g, x2, dw, dbias, accumulate, want_w, want_bias, want_dx, want_dx2):
+    """One body for linear_ce_bwd / linear_ce_tiled_bwd: the two C entries take the same arguments."""
+    name = "linear_ce_tiled" if tiled else "linear_ce"
+    (M, K1, K2, C), x, weight, bias, labels, x2 = _linear_ce_prep(
+        x, weight, bias, labels, x2, LINEAR_CE_TILED_MAX_CLASSES if tiled else LINEAR_CE_MAX_CLASSES)
     _need_cuda(x, lse, g, dw, dbias)
     dev = x.device
     assert lse.dtype == torch.float32 and lse.shape == (M,) and lse.is_contiguous()
@@ -391,14 +395,49 @@ def linear_ce_bwd(x, weight, bias, labels, lse, g, x2=None, dw=None, dbias=None,
     if dw is None and dbias is None and dx is None and dx2 is None:
         return None, None, None, None
     lib = _lib()
-    ws = workspace(lib.clipk_linear_ce_workspace(M, K1, K2, C), dev, "linear_ce")
-    check(_timed("linear_ce_bwd", 4.0 * M * C * (K1 + K2),
-                 lambda: lib.clipk_linear_ce_bwd(x.data_ptr(), K1, ptr(x2), K2, weight.data_ptr(), ptr(bias),
-                                                 labels.data_ptr(), M, C, lse.data_ptr(), g.data_ptr(), int(bool(accumulate)),
-                                                 ptr(dw), ptr(dbias), ptr(dx), ptr(dx2), ws.data_ptr(), ws.numel(),
-                                                 _stream()),
-                 8.0 * M * (K1 + K2)), "clipk_linear_ce_bwd")
+    entry = lib.clipk_linear_ce_tiled_bwd if tiled else lib.clipk_linear_ce_bwd
+    nws = (lib.clipk_linear_ce_tiled_workspace if tiled else lib.clipk_linear_ce_workspace)(M, K1, K2, C)
+    ws = workspace(nws, dev, name)
+    check(_timed(name + "_bwd", 4.0 * M * C * (K1 + K2),
+                 lambda: entry(x.data_ptr(), K1, ptr(x2), K2, weight.data_ptr(), ptr(bias), labels.data_ptr(), M, C,
+                               lse.data_ptr(), g.data_ptr(), int(bool(accumulate)), ptr(dw), ptr(dbias), ptr(dx), ptr(dx2),
+                               ws.data_ptr(), ws.numel(), _stream()),
+                 8.0 * M * (K1 + K2)), f"clipk_{name}_bwd")
     return dw, dbias, dx, dx2
+
+
+def linear_ce_bwd(x, weight, bias, labels, lse, g, x2=None, dw=None, dbias=None, accumulate=False, want_w=True,
+                  want_bias=True, want_dx=False, want_dx2=False):
+    """Gradients of mean(lse - tgt) times the device scalar g (clipk_linear_ce_bwd).  dw / dbias: write (accumulate: add)
+    into these tensors, e.g. the parameters' .grad; otherwise new tensors where want_w / want_bias.  Returns
+    (dw, dbias, dx, dx2), None where not asked for."""
+    return _linear_ce_bwd(False, x, weight, bias, labels, lse, g, x2, dw, dbias, accumulate, want_w, want_bias, want_dx,
+                          want_dx2)
+
+
+def linear_ce_tiled_fwd(x, weight, bias=None, labels=None, x2=None):
+    """linear_ce_fwd for any class count up to 65536 (include/clipk.h: clipk_linear_ce_tiled_fwd): (lse [M], tgt [M] or None
+    without labels, pred int64 [M]).  No logits output: head(x) serves them."""
+    (M, K1, K2, C), x, weight, bias, labels, x2 = _linear_ce_prep(x, weight, bias, labels, x2, LINEAR_CE_TILED_MAX_CLASSES)
+    dev = x.device
+    lse = torch.empty(M, dtype=torch.float32, device=dev)
+    tgt = torch.empty(M, dtype=torch.float32, device=dev) if labels is not None else None
+    pred = torch.empty(M, dtype=torch.int64, device=dev)
+    lib = _lib()
+    ws = workspace(lib.clipk_linear_ce_tiled_workspace(M, K1, K2, C), dev, "linear_ce_tiled")
+    check(_timed("linear_ce_tiled_fwd", 2.0 * M * C * (K1 + K2),
+                 lambda: lib.clipk_linear_ce_tiled_fwd(x.data_ptr(), K1, ptr(x2), K2, weight.data_ptr(), ptr(bias), ptr(labels),
+                                                       M, C, lse.data_ptr(), ptr(tgt), pred.data_ptr(), ws.data_ptr(),
+                                                       ws.numel(), _stream()),
+                 4.0 * (M * (K1 + K2) + C * (K1 + K2))), "clipk_linear_ce_tiled_fwd")
+    return lse, tgt, pred
+
+
+def linear_ce_tiled_bwd(x, weight, bias, labels, lse, g, x2=None, dw=None, dbias=None, accumulate=False, want_w=True,
+                        want_bias=True, want_dx=False, want_dx2=False):
+    """linear_ce_bwd for any class count up to 65536 (clipk_linear_ce_tiled_bwd): the same arguments and returns."""
+    return _linear_ce_bwd(True, x, weight, bias, labels, lse, g, x2, dw, dbias, accumulate, want_w, want_bias, want_dx,
+                          want_dx2)
 
 
 def _grad_outs(x):

@@ -505,6 +505,38 @@ int clipk_linear_ce_bwd(const float* X1, int K1, const float* X2, int K2, const 
                         float* dW /*[C,K1+K2]*/, float* dbias /*[C]*/, float* dX1 /*[M,K1]*/, float* dX2 /*[M,K2]*/,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same Linear + cross-entropy for ANY class count: 1 <= C <= 65536.  The reference's own probe task is far past 64
+ * classes - run1/proposal.MD:3 pairs 2,547 immune cell types with 158 unique markers, and every head takes num_classes as
+ * a free argument (old/classifier.py:14,31,40,52; old/ablation.py:30,45).  Definitions of Z, lse, tgt, pred, G, dW, dbias,
+ * dX1, dX2, the out-of-range-label rule and the accumulate flag: exactly those of clipk_linear_ce_* above.  No logits
+ * output (clipk_gemm_f32 serves logits); each of lse / tgt / pred may be NULL (not all).
+ * fwd: a workgroup owns 64 rows of [X1|X2] and walks 64-class tiles of W on v_mfma_f32_32x32x2_f32 (classes on the MFMA
+ *   rows, X rows on the lanes; the second source continues the first one's accumulator), keeping per row the running
+ *   (max, sum), the best (value, class) and the target logit.  Equal logits resolve to the lower class also across class
+ *   tiles and splits: the merge rule "larger value, then lower class" is associative.  The class range is split across
+ *   workgroups when M alone does not fill the chip; the partials [split][M][5] go to the workspace and a second kernel
+ *   merges them in split order.
+ * bwd: the forward's kernel recomputes Z with the forward's bits and writes G to the workspace (pitch C rounded up to 4,
+ *   zeros in the padding); dW and dbias are summed over row splits and 64-class groups by a kernel of clipk_linear_ce_bwd's
+ *   layout and the splits are added in split order (clipk_gemm_f32 does not split its contraction, here the M rows: at
+ *   C = 158 it ran 24 workgroups); dX comes from clipk_gemm_f32 on G, one call per source.  The rows are processed in
+ *   slabs whose G stays at 128 MiB or less (half of the Infinity Cache); dW / dbias accumulate over the slabs in slab
+ *   order (record of the slab A/B: profiles/probe/README.md).
+ * Supported: M >= 1, 1 <= C <= 65536, K1 % 4 == 0, K2 % 4 == 0, K1 >= 4, K1 + K2 <= 4096, X1 / X2 / W / dW / dX / workspace
+ * 16-byte aligned; anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED and the workspace helper returns 0.
+ * Never allocates, never synchronises, capturable, no float atomics: results depend on the shapes alone.  workspace (fwd
+ * and bwd): clipk_linear_ce_tiled_workspace(M, K1, K2, C) bytes.
+ * Accuracy: the bounds of clipk_linear_ce_* hold (a logit is a chain of K fused multiply-adds, k ascending per source,
+ * and the bias addition); bits differ from clipk_linear_ce_* at C <= 64, which keeps its own kernels. */
+size_t clipk_linear_ce_tiled_workspace(int M, int K1, int K2, int C);
+int clipk_linear_ce_tiled_fwd(const float* X1, int K1, const float* X2, int K2, const float* W, const float* bias,
+                              const int64_t* labels, int M, int C, float* lse /*[M]*/, float* tgt /*[M]*/,
+                              int64_t* pred /*[M]*/, void* workspace, size_t workspace_bytes, void* stream);
+int clipk_linear_ce_tiled_bwd(const float* X1, int K1, const float* X2, int K2, const float* W, const float* bias,
+                              const int64_t* labels, int M, int C, const float* lse, const float* g, int accumulate,
+                              float* dW /*[C,K1+K2]*/, float* dbias /*[C]*/, float* dX1 /*[M,K1]*/, float* dX2 /*[M,K2]*/,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* out[cols, rows] = scale_dev[0] * in[rows, cols]^T (f32; scale_dev NULL = 1).  Operand preparation of the exact-f32
  * products that differentiate the materialised logits (d/dA = scale * dS · B, d/dB = scale * dS^T · A of
  * old/clip.py:67) and of the ICNN's transposed weights (triple_flow/2_icnn_core.py:181-211). */
