@@ -26,6 +26,8 @@ from .diagnostics import SimilarityStats, evaluate_embeddings, similarity_stats
 from . import diagnostics
 from .classifier import LinearClassifier, MLPClassifier, SimpleNonLinearClassifier, TransformerClassifier
 from . import classifier, probe
+from .ot import SinkhornResult, sinkhorn, sinkhorn_divergence
+from . import ot
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -40,4 +42,5 @@ __all__ = [
     "retrieval", "EmbeddingIndex", "evaluate_retrieval", "retrieval_metrics", "metrics_from_ranks",
     "diagnostics", "SimilarityStats", "similarity_stats", "evaluate_embeddings",
     "classifier", "probe", "MLPClassifier", "TransformerClassifier", "LinearClassifier", "SimpleNonLinearClassifier",
+    "ot", "sinkhorn", "sinkhorn_divergence", "SinkhornResult",
 ]

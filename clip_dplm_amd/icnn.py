@@ -457,6 +457,18 @@ class GraphedTransport:
         return self.static_out
 
 
+@torch.no_grad()
+def compute_transport_error(transport: SingleCellTransport, source: torch.Tensor, target: torch.Tensor,
+                            batch_size: int = 128) -> float:
+    """4_transport_maps.py:284-301: the mean over batches of the paired MSE between transport(source) and target (a
+    short last batch weighs as much as a full one, as there)."""
+    errors = []
+    for i in range(0, len(source), batch_size):
+        transported = transport(source[i:i + batch_size])
+        errors.append(F.mse_loss(transported, target[i:i + batch_size]).item())
+    return sum(errors) / len(errors)
+
+
 def create_transport_system(cell_dim: int, pert_dim: int, protein_dim: int, hidden_dims: Optional[List[int]] = None,
                             **kwargs) -> TripleTransportMaps:
     """4_transport_maps.py:248-281."""

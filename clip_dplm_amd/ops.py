@@ -886,6 +886,86 @@ def sim_stats(x, y, *, scale: float = 1.0, labels=None, label_offset: int = 0, c
     return out
 
 
+SIM_LSE_BIAS_MAX_P = 768        # clipk_sim_lse_bias
+SINKHORN_APPLY_MAX_P = 512      # clipk_sinkhorn_apply
+
+
+def _sinkhorn_args(x, y, scale, max_p, vectors=()):
+    """Operand checks of the two Sinkhorn entries, before any launch.  vectors: (name, tensor or None, length)."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    if P > max_p:
+        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {max_p})")
+    if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or scale.numel() != 1:
+        raise TypeError("scale must be a one-element float32 device tensor")
+    for name, t, n in vectors:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.shape != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous tensor of shape ({n},), got {tuple(t.shape)}")
+    for t in (x, y, scale, *(v[1] for v in vectors)):
+        if t is not None and not t.is_cuda:
+            raise ValueError("the Sinkhorn kernels need device tensors (there is no CPU fallback)")
+    _need_cuda(x, y, scale, *(v[1] for v in vectors))
+    return Mx, Ny, P
+
+
+def sim_lse_bias_plan(Mx: int, Ny: int):
+    """(64-query blocks, key-range splits) of the grid clipk_sim_lse_bias launches for these sizes."""
+    nqb, ks = C.c_int(0), C.c_int(0)
+    check(_lib().clipk_sim_lse_bias_plan(int(Mx), int(Ny), C.byref(nqb), C.byref(ks)), "clipk_sim_lse_bias_plan")
+    return nqb.value, ks.value
+
+
+def sim_lse_bias(x, y, scale, bias=None, logw=None, prev=None, average=False, out=None, err=None):
+    """One Sinkhorn half-iteration (include/clipk.h: clipk_sim_lse_bias): nv[i] = logw[i] - logsumexp_j(scale * <x_i, y_j>
+    + bias[j]); returns out = nv, or (prev + nv) / 2 with average=True.  scale: device scalar; bias [Ny], logw [Mx], prev
+    [Mx]: f32 device vectors or None.  err: device scalar that receives += sum_i exp(logw_i) |exp(prev_i - nv_i) - 1|
+    (needs prev).  out may be given, and may be prev."""
+    Mx, Ny, P = _sinkhorn_args(x, y, scale, SIM_LSE_BIAS_MAX_P,
+                               (("bias", bias, y.shape[0]), ("logw", logw, x.shape[0]), ("prev", prev, x.shape[0]),
+                                ("out", out, x.shape[0]), ("err", None if err is None else err.reshape(-1), 1)))
+    if (average or err is not None) and prev is None:
+        raise ValueError("average=True and err need prev")
+    if out is None:
+        out = torch.empty(Mx, dtype=torch.float32, device=x.device)
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_sim_lse_bias_workspace(Mx, Ny, P), x.device, "sinkhorn", stream)
+    check(_timed("sim_lse_bias", 2.0 * Mx * Ny * P,
+                 lambda: lib.clipk_sim_lse_bias(x.data_ptr(), Mx, y.data_ptr(), Ny, P, scale.data_ptr(), ptr(bias), ptr(logw),
+                                                ptr(prev), int(bool(average)), out.data_ptr(), ptr(err), ws.data_ptr(),
+                                                ws.numel(), stream)), "clipk_sim_lse_bias")
+    return out
+
+
+def sinkhorn_apply(x, y, scale, u, v, nx=None, ny=None, want_mass=True, want_bary=True, want_cost=True):
+    """Row sums over the plan P_ij = exp(scale * <x_i, y_j> + u_i + v_j) (include/clipk.h: clipk_sinkhorn_apply):
+    (mass [Mx] = sum_j P_ij, bary [Mx, P] = sum_j P_ij y_j, cost [Mx] = sum_j P_ij |x_i - y_j|^2), None for an output not
+    wanted.  cost needs the squared norms nx [Mx], ny [Ny]."""
+    Mx, Ny, P = _sinkhorn_args(x, y, scale, SINKHORN_APPLY_MAX_P,
+                               (("u", u, x.shape[0]), ("v", v, y.shape[0]), ("nx", nx, x.shape[0]), ("ny", ny, y.shape[0])))
+    if u is None or v is None:
+        raise ValueError("u and v are needed")
+    if not (want_mass or want_bary or want_cost):
+        raise ValueError("no output wanted")
+    if want_cost and (nx is None or ny is None):
+        raise ValueError("cost needs the squared norms nx and ny")
+    dev = x.device
+    mass = torch.empty(Mx, dtype=torch.float32, device=dev) if want_mass else None
+    bary = torch.empty((Mx, P), dtype=torch.float32, device=dev) if want_bary else None
+    cost = torch.empty(Mx, dtype=torch.float32, device=dev) if want_cost else None
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_sinkhorn_apply_workspace(Mx, Ny, P), dev, "sinkhorn", stream)
+    check(_timed("sinkhorn_apply", 2.0 * Mx * Ny * P * (2 if want_bary else 1),
+                 lambda: lib.clipk_sinkhorn_apply(x.data_ptr(), Mx, y.data_ptr(), Ny, P, scale.data_ptr(), u.data_ptr(),
+                                                  v.data_ptr(), ptr(nx), ptr(ny), ptr(mass), ptr(bary), ptr(cost),
+                                                  ws.data_ptr(), ws.numel(), stream)), "clipk_sinkhorn_apply")
+    return mass, bary, cost
+
+
 def ce_logits_lse(S, S2=None, columns=False, label_offset=0):
     """LSE over the rows (optionally of [S | S2]) or the columns of materialised f32 logits + the diagonal logit."""
     _need_cuda(S, S2)

@@ -1,0 +1,283 @@
+"""Entropic optimal transport (Sinkhorn) between embedding clouds on the fused kernels of csrc/sinkhorn.hip.
+
+The transport maps of icnn.py are judged by the reference with paired distances only (TransportCost's "Wasserstein-2" is
+the mean of ||T(x_i) - y_i||, compute_transport_error a paired MSE); whether T pushes the source DISTRIBUTION onto the
+target one is what this module measures.  The reference's second generation (tong/models/flows/ot_flow.py,
+SchrodingerBridgeFlow) takes an entropic plan with reg = 2 sigma^2 from a library on the materialised squared-distance
+matrix; here the M x N matrix is never written (include/clipk.h: clipk_sim_lse_bias, clipk_sinkhorn_apply).
+
+Clouds x [M, P], y [N, P] (f32, device), weights a [M], b [N] (> 0, sum 1; uniform by default), cost C_ij = |x_i - y_j|^2:
+
+    OT_eps = min_P <P, C> + eps KL(P | a (x) b)
+
+With S = (2 / eps) x y^T and scaled log-potentials u, v (the squared norms are absorbed into them):
+
+    u_i = log a_i - LSE_j(S_ij + v_j),  v_j = log b_j - LSE_i(S_ij + u_i)       start v = log b; one iteration = u, then v
+    P_ij = exp(S_ij + u_i + v_j);  f_i = eps (u_i - log a_i) + |x_i|^2,  g_j = eps (v_j - log b_j) + |y_j|^2
+    OT_eps = <a, f> + <b, g>;   dOT_eps / dx_i = 2 (r_i x_i - sum_j P_ij y_j),  r_i = sum_j P_ij        (envelope theorem)
+    symmetric problem (y is x, a = b):  u <- (u + log a - LSE(S + u)) / 2, one potential
+    S_eps(x, y) = OT_eps(x, y) - OT_eps(x, x) / 2 - OT_eps(y, y) / 2                                   (debiased divergence)
+
+Every half-iteration is one ops.sim_lse_bias call; every plan-weighted sum one ops.sinkhorn_apply call.  What is left to
+ATen is O((M + N) P) glue: squared norms, the closed-form mean cost, the duals from the potentials.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, field
+from typing import Optional, Union
+
+import torch
+
+from . import ops
+
+__all__ = ["SinkhornResult", "sinkhorn", "sinkhorn_loss", "sinkhorn_divergence", "mean_cost", "evaluate_transport"]
+
+
+def mean_cost(x, y, a=None, b=None):
+    """sum_ij a_i b_j |x_i - y_j|^2 in closed form, sum_i a_i |x_i|^2 + sum_j b_j |y_j|^2 - 2 <sum_i a_i x_i, sum_j b_j y_j>:
+    no pass over pairs.  0-d tensor on the inputs' device."""
+    nx, ny = (x * x).sum(1), (y * y).sum(1)
+    mx = x.mean(0) if a is None else a @ x
+    my = y.mean(0) if b is None else b @ y
+    sx = nx.mean() if a is None else (a * nx).sum()
+    sy = ny.mean() if b is None else (b * ny).sum()
+    return sx + sy - 2.0 * (mx * my).sum()
+
+
+def _check_args(x, y, eps, eps_rel, a, b, n_iters, tol, check_every, symmetric):
+    """Every argument error of sinkhorn(), raised before anything is launched."""
+    for name, t in (("x", x), ("y", y)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.dim() != 2 or t.shape[0] == 0:
+            raise ValueError(f"{name} must be a non-empty 2-D tensor, got shape {tuple(t.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"x has {x.shape[1]} columns, y {y.shape[1]}")
+    P = x.shape[1]
+    if P == 0 or P % 4 or P > ops.SIM_LSE_BIAS_MAX_P:
+        raise ValueError(f"the width must be a multiple of 4 and at most {ops.SIM_LSE_BIAS_MAX_P}, got {P}")
+    for name, w, t in (("a", a, x), ("b", b, y)):
+        if w is None:
+            continue
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 tensor")
+        if w.shape != (t.shape[0],):
+            raise ValueError(f"{name} must have shape ({t.shape[0]},), got {tuple(w.shape)}")
+        if w.device != t.device:
+            raise ValueError(f"{name} is on {w.device}, its cloud on {t.device}")
+        # (a host read: skipped while a graph is being captured, where the weights were checked by the warm-up call)
+        if not (w.is_cuda and torch.cuda.is_current_stream_capturing()) and not bool((w > 0).all()):
+            raise ValueError(f"{name} must be positive")
+    if eps is not None and not isinstance(eps, torch.Tensor) and not (float(eps) > 0 and math.isfinite(float(eps))):
+        raise ValueError(f"eps must be positive and finite, got {eps}")
+    if eps is None and not (float(eps_rel) > 0 and math.isfinite(float(eps_rel))):
+        raise ValueError(f"eps_rel must be positive and finite, got {eps_rel}")
+    if int(n_iters) < 1 or int(check_every) < 1:
+        raise ValueError("n_iters and check_every must be at least 1")
+    if tol is not None and not float(tol) > 0:
+        raise ValueError(f"tol must be positive or None, got {tol}")
+    if symmetric and (y is not x or (b is not None and b is not a)):
+        raise ValueError("symmetric=True is the problem of a cloud with itself: pass y = x (the same tensor) and b = a or None")
+    if not x.is_cuda or not y.is_cuda:
+        raise ValueError("sinkhorn needs device tensors (there is no CPU fallback)")
+
+
+@dataclass
+class SinkhornResult:
+    """Potentials and value of one solve.  f, g: the dual potentials; u, v: the scaled log-potentials of the plan
+    P_ij = exp((2 / eps) <x_i, y_j> + u_i + v_j); eps, value (= <a, f> + <b, g>) and marginal_error (the L1 distance of the
+    plan's row marginal from a; the column marginal is exact after a v update) are 0-d device tensors, so that a solve
+    with tol=None does not wait for the device once its arguments are checked; n_iters: iterations run."""
+    f: torch.Tensor
+    g: torch.Tensor
+    u: torch.Tensor
+    v: torch.Tensor
+    eps: torch.Tensor
+    value: torch.Tensor
+    n_iters: int
+    marginal_error: torch.Tensor
+    _x: torch.Tensor = field(repr=False, default=None)
+    _y: torch.Tensor = field(repr=False, default=None)
+    _scale: torch.Tensor = field(repr=False, default=None)
+    _nx: torch.Tensor = field(repr=False, default=None)
+    _ny: torch.Tensor = field(repr=False, default=None)
+
+    def marginals(self):
+        """(row sums [M], column sums [N]) of the plan."""
+        rows, _, _ = ops.sinkhorn_apply(self._x, self._y, self._scale, self.u, self.v, want_bary=False, want_cost=False)
+        cols, _, _ = ops.sinkhorn_apply(self._y, self._x, self._scale, self.v, self.u, want_bary=False, want_cost=False)
+        return rows, cols
+
+    def cost(self):
+        """<P, C>, the transport cost of the plan without the entropy term (0-d tensor)."""
+        _, _, c = ops.sinkhorn_apply(self._x, self._y, self._scale, self.u, self.v, self._nx, self._ny, want_mass=False,
+                                     want_bary=False)
+        return c.sum()
+
+    def barycentric_map(self):
+        """[M, P]: sum_j P_ij y_j / sum_j P_ij, where the plan sends x_i on average."""
+        mass, bary, _ = ops.sinkhorn_apply(self._x, self._y, self._scale, self.u, self.v, want_cost=False)
+        return bary / mass[:, None]
+
+
+@torch.no_grad()
+def sinkhorn(x, y, eps: Union[None, float, torch.Tensor] = None, eps_rel: float = 0.05, a=None, b=None, n_iters: int = 100,
+             tol: Optional[float] = 1e-5, check_every: int = 10, symmetric: bool = False) -> SinkhornResult:
+    """Solve OT_eps between the clouds x [M, P] and y [N, P] (f32, device; P % 4 == 0, P <= 768).
+
+    eps: the regularisation in units of the squared distance (a number or a 0-d device tensor); None takes eps_rel x the
+    mean cost, from mean_cost's closed form, on the device.  a, b: weights (> 0, summing to 1), None = uniform.
+    tol=None runs exactly n_iters iterations without waiting for the device, so the call can be captured in a graph (with
+    uniform weights nothing is read back at all; given weights are checked for positivity by one host read before the
+    first launch, which is left out while a graph is being captured);
+    with a tol the L1 marginal error (a device scalar the update kernel leaves behind) is read every check_every
+    iterations and the solve stops once it is below tol.  symmetric=True (y is x, b is a or None): the averaged update with one
+    potential; the alternating one leaves the two potentials of a self problem apart for hundreds of iterations."""
+    _check_args(x, y, eps, eps_rel, a, b, n_iters, tol, check_every, symmetric)
+    x = x.detach().contiguous()
+    y = x if symmetric else y.detach().contiguous()
+    if symmetric:
+        b = a
+    dev = x.device
+    M, N = x.shape[0], y.shape[0]
+    nx = (x * x).sum(1)
+    ny = nx if symmetric else (y * y).sum(1)
+    loga = torch.full((M,), -math.log(M), dtype=torch.float32, device=dev) if a is None else a.log()
+    logb = loga if symmetric else (torch.full((N,), -math.log(N), dtype=torch.float32, device=dev) if b is None else b.log())
+    if eps is None:
+        eps_t = float(eps_rel) * mean_cost(x, y, a, b)
+    elif isinstance(eps, torch.Tensor):
+        eps_t = eps.detach().to(device=dev, dtype=torch.float32).reshape(())
+    else:
+        eps_t = torch.full((), float(eps), dtype=torch.float32, device=dev)
+    scale = (2.0 / eps_t).reshape(1)
+    err = torch.zeros(1, dtype=torch.float32, device=dev)
+    n_iters, check_every = int(n_iters), int(check_every)
+    done = n_iters
+    if symmetric:
+        u = loga.clone()
+        for it in range(n_iters):
+            look = tol is not None and (it + 1) % check_every == 0
+            if look:
+                err.zero_()
+            ops.sim_lse_bias(x, x, scale, bias=u, logw=loga, prev=u, average=True, out=u, err=err if look else None)
+            if look and err.item() < tol:           # the error of the potential this update replaced
+                done = it + 1
+                break
+        v = u
+    else:
+        u, v = torch.empty_like(loga), logb.clone()
+        for it in range(n_iters):
+            look = tol is not None and it > 0 and (it + 1) % check_every == 0
+            if look:
+                err.zero_()
+            ops.sim_lse_bias(x, y, scale, bias=v, logw=loga, prev=u if look else None, out=u, err=err if look else None)
+            ops.sim_lse_bias(y, x, scale, bias=u, logw=logb, out=v)
+            if look and err.item() < tol:           # the row error of the plan before this iteration
+                done = it + 1
+                break
+    # the returned plan's own row error: one more half-iteration's worth of work, its update discarded
+    err.zero_()
+    ops.sim_lse_bias(x, y, scale, bias=v, logw=loga, prev=u, out=torch.empty_like(u), err=err)
+    f = eps_t * (u - loga) + nx
+    g = f if symmetric else eps_t * (v - logb) + ny
+    va = f.mean() if a is None else (a * f).sum()
+    vb = va if symmetric else (g.mean() if b is None else (b * g).sum())
+    return SinkhornResult(f=f, g=g, u=u, v=v, eps=eps_t, value=va + vb, n_iters=done, marginal_error=err.reshape(()),
+                          _x=x, _y=y, _scale=scale, _nx=nx, _ny=ny)
+
+
+def _row_gradient(x, y, scale, u, v):
+    """dOT_eps / dx = 2 (r_i x_i - sum_j P_ij y_j) from the potentials."""
+    mass, bary, _ = ops.sinkhorn_apply(x, y, scale, u, v, want_cost=False)
+    return 2.0 * (mass[:, None] * x - bary)
+
+
+def _check_apply_width(x):
+    if x.shape[1] > ops.SINKHORN_APPLY_MAX_P:
+        raise ValueError(f"gradients and plan sums need a width of at most {ops.SINKHORN_APPLY_MAX_P}, got {x.shape[1]}")
+
+
+class _SinkhornLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, a, b, kw):
+        if x.requires_grad or y.requires_grad:
+            _check_apply_width(x)
+        r = sinkhorn(x, y, a=a, b=b, **kw)
+        ctx.save_for_backward(r._x, r._y, r._scale, r.u, r.v)
+        return r.value.clone()
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, grad):
+        x, y, scale, u, v = ctx.saved_tensors
+        gx = _row_gradient(x, y, scale, u, v) * grad if ctx.needs_input_grad[0] else None
+        gy = _row_gradient(y, x, scale, v, u) * grad if ctx.needs_input_grad[1] else None
+        return gx, gy, None, None, None
+
+
+class _SinkhornDivergenceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, a, b, same, kw):
+        if x.requires_grad or y.requires_grad:
+            _check_apply_width(x)
+        if same:                                     # a cloud with itself: the three terms are one problem, S_eps = 0
+            xy = xx = yy = sinkhorn(x, x, a=a, b=a, symmetric=True, **kw)
+        else:
+            xy = sinkhorn(x, y, a=a, b=b, **kw)
+            kw = dict(kw, eps=xy.eps)                # the three terms share the cross problem's eps
+            xx = sinkhorn(xy._x, xy._x, a=a, b=a, symmetric=True, **kw)
+            yy = sinkhorn(xy._y, xy._y, a=b, b=b, symmetric=True, **kw)
+        ctx.save_for_backward(xy._x, xy._y, xy._scale, xy.u, xy.v, xx.u, yy.u)
+        return xy.value - 0.5 * xx.value - 0.5 * yy.value
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, grad):
+        # the self terms enter with factor 1/2 and depend on their cloud through both arguments: the two halves add up to
+        # one row gradient
+        x, y, scale, u, v, uxx, uyy = ctx.saved_tensors
+        gx = gy = None
+        if ctx.needs_input_grad[0]:
+            gx = (_row_gradient(x, y, scale, u, v) - _row_gradient(x, x, scale, uxx, uxx)) * grad
+        if ctx.needs_input_grad[1]:
+            gy = (_row_gradient(y, x, scale, v, u) - _row_gradient(y, y, scale, uyy, uyy)) * grad
+        return gx, gy, None, None, None, None
+
+
+def _solver_kw(eps, eps_rel, n_iters, tol, check_every):
+    return dict(eps=eps, eps_rel=eps_rel, n_iters=n_iters, tol=tol, check_every=check_every)
+
+
+def sinkhorn_loss(x, y, eps=None, eps_rel: float = 0.05, a=None, b=None, n_iters: int = 100, tol: Optional[float] = 1e-5,
+                  check_every: int = 10):
+    """OT_eps(x, y) as a differentiable 0-d tensor.  Gradients flow to x and y only (not to the weights, and eps - also
+    when it is derived from the clouds - is a constant); they are the envelope-theorem gradients, exact at convergence:
+    nothing is unrolled, so a solve stopped early gives the gradient of its current plan.  Gradients need P <= 512."""
+    return _SinkhornLossFn.apply(x, y, a, b, _solver_kw(eps, eps_rel, n_iters, tol, check_every))
+
+
+def sinkhorn_divergence(x, y, eps=None, eps_rel: float = 0.05, a=None, b=None, n_iters: int = 100,
+                        tol: Optional[float] = 1e-5, check_every: int = 10):
+    """The debiased divergence S_eps(x, y) = OT_eps(x, y) - OT_eps(x, x) / 2 - OT_eps(y, y) / 2 as a differentiable 0-d
+    tensor: zero for equal clouds, positive otherwise.  The self terms use the symmetric update and the cross term's eps.
+    Gradients as in sinkhorn_loss."""
+    return _SinkhornDivergenceFn.apply(x, y, a, b, y is x and b is a, _solver_kw(eps, eps_rel, n_iters, tol, check_every))
+
+
+@torch.no_grad()
+def evaluate_transport(transport, source, target, batch_size: int = 128, **sinkhorn_kwargs) -> dict:
+    """Judge a transport map on held-out clouds: `mse`, the reference's paired compute_transport_error
+    (triple_flow/4_transport_maps.py:284-301); `sinkhorn_divergence` between transport(source) and target, which needs no
+    pairing; `identity_divergence` between source and target when their widths match - what the map has to beat."""
+    from .icnn import compute_transport_error
+    out = {"mse": compute_transport_error(transport, source, target, batch_size)}
+    moved = torch.cat([transport(source[i:i + batch_size]) for i in range(0, len(source), batch_size)]).float().contiguous()
+    tgt = target.float().contiguous()
+    out["sinkhorn_divergence"] = float(sinkhorn_divergence(moved, tgt, **sinkhorn_kwargs))
+    if source.shape[1] == target.shape[1]:
+        out["identity_divergence"] = float(sinkhorn_divergence(source.float().contiguous(), tgt, **sinkhorn_kwargs))
+    return out

@@ -793,6 +793,50 @@ int clipk_adamw_step(float* w, const float* g, float* m, float* v, void* w_bf16 
                      int step, const float* grad_norm_sq /* device scalar or NULL */, float max_norm,
                      float grad_scale, const float* hyper_dev /* or NULL */, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Entropic optimal transport (Sinkhorn) between two f32 clouds X [Mx,P], Y [Ny,P] with weights a [Mx], b [Ny] (> 0, sum 1)
+ * and cost C_ij = |x_i - y_j|^2:   OT_eps = min_P <P,C> + eps KL(P | a (x) b).   The reference's second generation
+ * (tong/models/flows/ot_flow.py, SchrodingerBridgeFlow) takes the plan from a library on the materialised matrix; here
+ * the M x N matrix is never written.  With S = (2/eps) X Y^T and scaled log-potentials u, v (the squared norms are
+ * absorbed into them):
+ *     u_i = log a_i - LSE_j(S_ij + v_j),   v_j = log b_j - LSE_i(S_ij + u_i),   start v = log b, one iteration = u then v
+ *     plan P_ij = exp(S_ij + u_i + v_j);  duals f_i = eps (u_i - log a_i) + |x_i|^2, g_j = eps (v_j - log b_j) + |y_j|^2
+ *     OT_eps = <a,f> + <b,g>;  dOT_eps/dx_i = 2 (r_i x_i - sum_j P_ij y_j), r_i = sum_j P_ij  (envelope theorem)
+ *     symmetric problem (X = Y, a = b): u <- (u + log a - LSE(S + u)) / 2, one potential.
+ *
+ * clipk_sim_lse_bias - one half-iteration:  nv_i = logw[i] - LSE_j(scale[0] <X_i, Y_j> + bias[j])
+ *   bias [Ny] or NULL (zeros), logw [Mx] or NULL (zeros), scale: device scalar.  prev [Mx] or NULL: the potential being
+ *   replaced; average != 0 (needs prev): out_i = (prev_i + nv_i) / 2, else out_i = nv_i.  err (device scalar or NULL,
+ *   needs prev): err[0] += sum_i exp(logw_i) |exp(prev_i - nv_i) - 1|, the L1 distance between the marginal of the plan
+ *   with `prev` on this side and its weights.  prev == out is allowed.
+ *   Kernel: the tiling of the fused cross-entropy's LSE pass (64 queries per workgroup, 64-key tiles on
+ *   v_mfma_f32_32x32x2_f32, a running (max, sum) per lane, keys beyond Ny masked with -inf); key-range splits are merged
+ *   in split order by a finalize kernel which also forms the update; the error terms are summed by one workgroup in a
+ *   fixed order (a third, tiny launch, only when err is given).  clipk_sim_lse_bias_plan reports the grid: nqb 64-query
+ *   blocks x ksplit key splits.
+ *   Supported: Mx, Ny >= 1, P % 4 == 0, P <= 768, X / Y / workspace 16-byte aligned.
+ * clipk_sinkhorn_apply - plan-weighted sums per row, each output optional (not all NULL):
+ *     mass[i] = sum_j P_ij,   bary[i,:] = sum_j P_ij y_j (unnormalised),   cost[i] = sum_j P_ij C_ij
+ *   u [Mx], v [Ny]; nx [Mx] = |x_i|^2 and ny [Ny] = |y_j|^2 are read for cost only (C_ij = nx_i + ny_j - 2 <x_i, y_j>).
+ *   Kernel: the structure of the fused cross-entropy's gradient pass: S tile, the plan tile into LDS, a second MFMA
+ *   product with the staged key rows; key-split slabs are summed in split order.  Without bary the second product and
+ *   the slabs are skipped.
+ *   Supported: Mx, Ny >= 1, P % 4 == 0, P <= 512, X / Y / bary / workspace 16-byte aligned.
+ * Anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED and the workspace helpers return 0.  Never allocates,
+ * never synchronises, capturable, no float atomics: results depend on the shapes alone. */
+int clipk_sim_lse_bias_plan(int Mx, int Ny, int* nqb, int* ksplit);
+size_t clipk_sim_lse_bias_workspace(int Mx, int Ny, int P);
+int clipk_sim_lse_bias(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale /* device scalar */,
+                       const float* bias /*[Ny] or NULL*/, const float* logw /*[Mx] or NULL*/,
+                       const float* prev /*[Mx] or NULL*/, int average, float* out /*[Mx]*/,
+                       float* err /* device scalar, accumulated, or NULL */, void* workspace, size_t workspace_bytes,
+                       void* stream);
+size_t clipk_sinkhorn_apply_workspace(int Mx, int Ny, int P);
+int clipk_sinkhorn_apply(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale /* device scalar */,
+                         const float* u /*[Mx]*/, const float* v /*[Ny]*/, const float* nx /*[Mx]*/,
+                         const float* ny /*[Ny]*/, float* mass /*[Mx] or NULL*/, float* bary /*[Mx,P] or NULL*/,
+                         float* cost /*[Mx] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
