@@ -28,6 +28,8 @@ from .classifier import LinearClassifier, MLPClassifier, SimpleNonLinearClassifi
 from . import classifier, probe
 from .ot import SinkhornResult, sinkhorn, sinkhorn_divergence
 from . import ot
+from .flow import SchrodingerBridgeConditionalFlowMatcher, conditional_flow, flow_matching_loss
+from . import flow
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -43,4 +45,5 @@ __all__ = [
     "diagnostics", "SimilarityStats", "similarity_stats", "evaluate_embeddings",
     "classifier", "probe", "MLPClassifier", "TransformerClassifier", "LinearClassifier", "SimpleNonLinearClassifier",
     "ot", "sinkhorn", "sinkhorn_divergence", "SinkhornResult",
+    "flow", "SchrodingerBridgeConditionalFlowMatcher", "conditional_flow", "flow_matching_loss",
 ]

@@ -966,6 +966,49 @@ def sinkhorn_apply(x, y, scale, u, v, nx=None, ny=None, want_mass=True, want_bar
     return mass, bary, cost
 
 
+def _seed_offset(seed, stream_offset, device=None):
+    """{seed, stream_offset} as the kernel reads them: `seed` may be the int64 device tensor of two elements itself
+    (stream_offset is then left at 0), or both are Python ints, taken modulo 2^64.  device=None: checks only."""
+    if isinstance(seed, torch.Tensor):
+        if seed.dtype != torch.int64 or seed.shape != (2,) or not seed.is_contiguous():
+            raise TypeError("a seed tensor must be a contiguous int64 tensor of two elements, {seed, stream_offset}")
+        if isinstance(stream_offset, torch.Tensor) or int(stream_offset) != 0:
+            raise ValueError("a seed tensor carries the stream offset as its second element: leave stream_offset at 0")
+        return seed
+    vals = []
+    for name, v in (("seed", seed), ("stream_offset", stream_offset)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"{name} must be an int (or seed an int64 device tensor of two elements), got {type(v).__name__}")
+        v &= (1 << 64) - 1
+        vals.append(v - (1 << 64) if v >= 1 << 63 else v)
+    return None if device is None else torch.tensor(vals, dtype=torch.int64, device=device)
+
+
+def sim_sample(x, y, scale, bias=None, seed=0, stream_offset=0, want_score=False):
+    """One Gumbel-max draw per row (include/clipk.h: clipk_sim_sample has the noise contract): idx[i] = argmax_j
+    scale * <x_i, y_j> + bias[j] + G(seed, stream_offset + i, j), int64 [Mx], distributed as softmax_j(scale * <x_i, y_j>
+    + bias[j]); with want_score also the winning value, f32 [Mx].  scale: device scalar; bias [Ny] f32 or None.  seed,
+    stream_offset: Python ints, or `seed` one int64 device tensor {seed, stream_offset} that the kernel reads (a captured
+    graph draws fresh noise once the caller changes it).  The result depends on (inputs, seed, stream) alone."""
+    _seed_offset(seed, stream_offset)
+    Mx, Ny, P = _sinkhorn_args(x, y, scale, SIM_LSE_BIAS_MAX_P, (("bias", bias, y.shape[0]),))
+    if isinstance(seed, torch.Tensor):
+        if not seed.is_cuda:
+            raise ValueError("the Sinkhorn kernels need device tensors (there is no CPU fallback)")
+        _need_cuda(x, seed)
+    so = _seed_offset(seed, stream_offset, x.device)
+    idx = torch.empty(Mx, dtype=torch.int64, device=x.device)
+    score = torch.empty(Mx, dtype=torch.float32, device=x.device) if want_score else None
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_sim_sample_workspace(Mx, Ny, P), x.device, "sinkhorn", stream)
+    check(_timed("sim_sample", 2.0 * Mx * Ny * P,
+                 lambda: lib.clipk_sim_sample(x.data_ptr(), Mx, y.data_ptr(), Ny, P, scale.data_ptr(), ptr(bias),
+                                              so.data_ptr(), idx.data_ptr(), ptr(score), ws.data_ptr(), ws.numel(),
+                                              stream)), "clipk_sim_sample")
+    return (idx, score) if want_score else idx
+
+
 def ce_logits_lse(S, S2=None, columns=False, label_offset=0):
     """LSE over the rows (optionally of [S | S2]) or the columns of materialised f32 logits + the diagonal logit."""
     _need_cuda(S, S2)

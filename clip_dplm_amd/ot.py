@@ -18,8 +18,10 @@ With S = (2 / eps) x y^T and scaled log-potentials u, v (the squared norms are a
     symmetric problem (y is x, a = b):  u <- (u + log a - LSE(S + u)) / 2, one potential
     S_eps(x, y) = OT_eps(x, y) - OT_eps(x, x) / 2 - OT_eps(y, y) / 2                                   (debiased divergence)
 
-Every half-iteration is one ops.sim_lse_bias call; every plan-weighted sum one ops.sinkhorn_apply call.  What is left to
-ATen is O((M + N) P) glue: squared norms, the closed-form mean cost, the duals from the potentials.
+Every half-iteration is one ops.sim_lse_bias call; every plan-weighted sum one ops.sinkhorn_apply call; every batch of
+draws from the plan (SinkhornResult.sample_targets / sample_pairs, what flow.py's matcher re-pairs its batches with) one
+ops.sim_sample call.  What is left to ATen is O((M + N) P) glue: squared norms, the closed-form mean cost, the duals
+from the potentials, the row gather of a draw.
 """
 from __future__ import annotations
 
@@ -104,6 +106,7 @@ class SinkhornResult:
     _scale: torch.Tensor = field(repr=False, default=None)
     _nx: torch.Tensor = field(repr=False, default=None)
     _ny: torch.Tensor = field(repr=False, default=None)
+    _a: Optional[torch.Tensor] = field(repr=False, default=None)     # the row weights (None = uniform), for sample_pairs
 
     def marginals(self):
         """(row sums [M], column sums [N]) of the plan."""
@@ -121,6 +124,42 @@ class SinkhornResult:
         """[M, P]: sum_j P_ij y_j / sum_j P_ij, where the plan sends x_i on average."""
         mass, bary, _ = ops.sinkhorn_apply(self._x, self._y, self._scale, self.u, self.v, want_cost=False)
         return bary / mass[:, None]
+
+    def sample_targets(self, rows=None, seed=0):
+        """int64 [n]: for each entry of `rows` one j ~ P(. | row) = softmax_j(S_row,j + v_j), by one ops.sim_sample call
+        (Gumbel arg max; include/clipk.h: clipk_sim_sample has the noise).  rows: int64 index tensor on the clouds' device,
+        entries in [0, M), repeats allowed; None = arange(M), which reads x in place - otherwise one row gather, O(n P)
+        glue.  Draw k uses stream k of `seed`, so equal (rows, seed) give equal draws and repeated rows independent ones.
+        seed: a Python int, or an int64 device tensor {seed, stream_offset} read by the kernel (no host read, capturable)."""
+        ops._seed_offset(seed, 0)
+        x = self._x
+        if rows is not None:
+            if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.dim() != 1 or rows.numel() == 0:
+                raise TypeError("rows must be a non-empty 1-D int64 index tensor")
+            if rows.device != x.device:
+                raise ValueError(f"rows is on {rows.device}, the clouds on {x.device}")
+            # (a host read: skipped while a graph is being captured, where the rows were checked by the warm-up call)
+            if not (rows.is_cuda and torch.cuda.is_current_stream_capturing()) and not bool(((rows >= 0) & (rows < x.shape[0])).all()):
+                raise IndexError(f"rows must lie in [0, {x.shape[0]})")
+        return self._draw(rows, seed)
+
+    def _draw(self, rows, seed):
+        x = self._x if rows is None else self._x.index_select(0, rows)
+        return ops.sim_sample(x, self._y, self._scale, bias=self.v, seed=seed)
+
+    def sample_pairs(self, n=None, seed=0, generator=None):
+        """(i, j), int64 [n] each (n defaults to M): i from torch.multinomial over the row weights `a` (uniform if none
+        were given) with replacement, under `generator`; j = sample_targets(i, seed).  The row marginal of the drawn
+        coupling is therefore exactly `a`, and the conditionals are the plan's: this is the joint plan up to the
+        result's `marginal_error`, the L1 distance between the plan's own row marginal and `a`."""
+        M = self._x.shape[0]
+        n = M if n is None else int(n)
+        if n < 1:
+            raise ValueError(f"n must be at least 1, got {n}")
+        ops._seed_offset(seed, 0)
+        w = self._a if self._a is not None else torch.ones(M, dtype=torch.float32, device=self._x.device)
+        i = torch.multinomial(w, n, replacement=True, generator=generator)
+        return i, self._draw(i, seed)                  # (in range by construction: no host read)
 
 
 @torch.no_grad()
@@ -187,7 +226,7 @@ def sinkhorn(x, y, eps: Union[None, float, torch.Tensor] = None, eps_rel: float 
     va = f.mean() if a is None else (a * f).sum()
     vb = va if symmetric else (g.mean() if b is None else (b * g).sum())
     return SinkhornResult(f=f, g=g, u=u, v=v, eps=eps_t, value=va + vb, n_iters=done, marginal_error=err.reshape(()),
-                          _x=x, _y=y, _scale=scale, _nx=nx, _ny=ny)
+                          _x=x, _y=y, _scale=scale, _nx=nx, _ny=ny, _a=a)
 
 
 def _row_gradient(x, y, scale, u, v):

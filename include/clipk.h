@@ -837,6 +837,32 @@ int clipk_sinkhorn_apply(const float* X, int Mx, const float* Y, int Ny, int P, 
                          const float* ny /*[Ny]*/, float* mass /*[Mx] or NULL*/, float* bary /*[Mx,P] or NULL*/,
                          float* cost /*[Mx] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Draws from the entropic plan without the matrix.  The conditional of P_ij = exp(S_ij + u_i + v_j) along row i is
+ * softmax_j(S_ij + v_j) (u_i is constant along the row), and the arg max of Gumbel-perturbed logits is a draw from it:
+ *
+ * clipk_sim_sample - idx[i] = argmax_j z_ij,  z_ij = scale[0] <X_i, Y_j> + bias[j] + G(seed, stream_i, j),  score[i] = max_j z_ij
+ *   bias [Ny] or NULL (zeros); score [Mx] or NULL.  seed_offset: two 64-bit integers in device memory, {seed,
+ *   stream_offset}; row i of the launch is stream stream_offset + i (64-bit).  They are read by the kernel, so a captured
+ *   graph draws fresh noise on every replay once the caller bumps them.
+ *   The noise is part of the contract (tests/sinkhorn_sample_ref.py restates it on the CPU):
+ *     Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), key = (low, high 32 bits
+ *     of seed), counter = (j >> 2, low 32 bits of the stream, high 32 bits of the stream, 0); key j takes output word
+ *     j & 3 = w;  U = ((w >> 9) + 0.5) 2^-23, exact in f32 and in [2^-24, 1 - 2^-24];  G = -log(-log U).
+ *   A higher z wins and equal z goes to the lower key index, at every level of the merge: the result depends on (inputs,
+ *   seed, stream) only, never on the grid - rows [r0, r1) of a launch equal a launch of those rows with stream_offset + r0.
+ *   Kernel: the tiling and the key-range split plan of clipk_sim_lse_bias (clipk_sim_lse_bias_plan reports the grid),
+ *   a running (best value, best key) per lane in place of (max, sum), keys beyond Ny masked with -inf, one Philox call
+ *   per four consecutive keys per query; the key splits are merged in split order by a finalize launch.
+ *   Supported: Mx, Ny >= 1, P % 4 == 0, P <= 768, X / Y / workspace 16-byte aligned.
+ * Anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED and the workspace helper returns 0.  Never allocates,
+ * never synchronises, capturable, no float atomics. */
+size_t clipk_sim_sample_workspace(int Mx, int Ny, int P);
+int clipk_sim_sample(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale /* device scalar */,
+                     const float* bias /*[Ny] or NULL*/, const long long* seed_offset /* device: {seed, stream_offset} */,
+                     long long* idx /*[Mx]*/, float* score /*[Mx] or NULL: the winning z*/, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
