@@ -30,6 +30,8 @@ from .ot import SinkhornResult, sinkhorn, sinkhorn_divergence
 from . import ot
 from .flow import SchrodingerBridgeConditionalFlowMatcher, conditional_flow, flow_matching_loss
 from . import flow
+from .distribution import evaluate_distributions, frechet_distance, mmd2
+from . import distribution
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -46,4 +48,5 @@ __all__ = [
     "classifier", "probe", "MLPClassifier", "TransformerClassifier", "LinearClassifier", "SimpleNonLinearClassifier",
     "ot", "sinkhorn", "sinkhorn_divergence", "SinkhornResult",
     "flow", "SchrodingerBridgeConditionalFlowMatcher", "conditional_flow", "flow_matching_loss",
+    "distribution", "mmd2", "frechet_distance", "evaluate_distributions",
 ]

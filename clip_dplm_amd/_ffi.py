@@ -147,6 +147,8 @@ SIGNATURES = {
     "clipk_sinkhorn_apply": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_sim_sample_workspace": (_sz, [_i, _i, _i]),
     "clipk_sim_sample": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_kernel_sums_workspace": (_sz, [_i, _i, _i, _i]),
+    "clipk_kernel_sums": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "clipk_embed_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "clipk_embed_bwd_workspace": (_sz, [_i, _i, _i, _i]),
     "clipk_embed_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -1009,6 +1009,66 @@ def sim_sample(x, y, scale, bias=None, seed=0, stream_offset=0, want_score=False
     return (idx, score) if want_score else idx
 
 
+KERNEL_SUMS_MAX_P = 512         # clipk_kernel_sums
+KERNEL_SUMS_MAX_B = 8
+
+
+def kernel_sums_plan(Mx: int, Ny: int):
+    """(64-query blocks, key-range splits) of the grid clipk_kernel_sums launches: that of clipk_sim_lse_bias."""
+    return sim_lse_bias_plan(Mx, Ny)
+
+
+def kernel_sums(x, y, gammas, weights, nx=None, ny=None, diag_offset=-1, want_sum=True, want_bary=False):
+    """Row sums over the Gaussian mixture K_ij = sum_b weights[b] exp(-gammas[b] d2_ij), d2_ij = max(nx_i + ny_j -
+    2 <x_i, y_j>, 0) (include/clipk.h: clipk_kernel_sums): (ksum [Mx] = sum_j K_ij, kbary [Mx, P] = sum_j K_ij y_j), None
+    for an output not wanted.  gammas, weights: f32 device vectors of B <= 8 entries, read by the kernel.  nx, ny: the
+    squared norms, computed here when not given.  diag_offset >= 0: row i skips key i + diag_offset (0 for a cloud with
+    itself); -1: nothing is skipped."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    if P > KERNEL_SUMS_MAX_P:
+        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {KERNEL_SUMS_MAX_P})")
+    for name, t in (("gammas", gammas), ("weights", weights)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 device tensor")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-D tensor, got shape {tuple(t.shape)}")
+    B = gammas.shape[0]
+    if not 1 <= B <= KERNEL_SUMS_MAX_B or weights.shape[0] != B:
+        raise ValueError(f"gammas and weights must have the same 1..{KERNEL_SUMS_MAX_B} entries, got {B} and "
+                         f"{weights.shape[0]}")
+    for name, t, n in (("nx", nx, Mx), ("ny", ny, Ny)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.shape != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous tensor of shape ({n},), got {tuple(t.shape)}")
+    diag_offset = int(diag_offset)
+    if diag_offset < -1:
+        raise ValueError(f"diag_offset must be -1 (nothing skipped) or >= 0, got {diag_offset}")
+    if not (want_sum or want_bary):
+        raise ValueError("no output wanted")
+    for t in (x, y, gammas, weights, nx, ny):
+        if t is not None and not t.is_cuda:
+            raise ValueError("the kernel-sum kernel needs device tensors (there is no CPU fallback)")
+    _need_cuda(x, y, gammas, weights, nx, ny)
+    if nx is None:
+        nx = (x * x).sum(1)
+    if ny is None:
+        ny = nx if y is x else (y * y).sum(1)
+    dev = x.device
+    ksum = torch.empty(Mx, dtype=torch.float32, device=dev) if want_sum else None
+    kbary = torch.empty((Mx, P), dtype=torch.float32, device=dev) if want_bary else None
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_kernel_sums_workspace(Mx, Ny, P, B), dev, "kernel_sums", stream)
+    check(_timed("kernel_sums", 2.0 * Mx * Ny * P * (2 if want_bary else 1),
+                 lambda: lib.clipk_kernel_sums(x.data_ptr(), Mx, y.data_ptr(), Ny, P, gammas.data_ptr(), weights.data_ptr(),
+                                               B, nx.data_ptr(), ny.data_ptr(), diag_offset, ptr(ksum), ptr(kbary),
+                                               ws.data_ptr(), ws.numel(), stream)), "clipk_kernel_sums")
+    return ksum, kbary
+
+
 def ce_logits_lse(S, S2=None, columns=False, label_offset=0):
     """LSE over the rows (optionally of [S | S2]) or the columns of materialised f32 logits + the diagonal logit."""
     _need_cuda(S, S2)

@@ -863,6 +863,36 @@ int clipk_sim_sample(const float* X, int Mx, const float* Y, int Ny, int P, cons
                      long long* idx /*[Mx]*/, float* score /*[Mx] or NULL: the winning z*/, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Row sums over a mixture of Gaussian kernels between two f32 clouds X [Mx,P], Y [Ny,P] without the Mx x Ny matrix: what
+ * a multi-bandwidth MMD (clip_dplm_amd.distribution.mmd2; the 'mmd' of the reference's tong/configs/default.yaml:74)
+ * and its gradient are made of.
+ *
+ * clipk_kernel_sums - each output optional (not both NULL):
+ *     d2_ij = max(nx[i] + ny[j] - 2 <X_i, Y_j>, 0),   K_ij = sum_b weights[b] exp(-gammas[b] d2_ij)
+ *     ksum[i] = sum_j K_ij,   kbary[i,:] = sum_j K_ij Y_j
+ *   gammas [B] (> 0) and weights [B] (any sign) are device vectors the kernel reads: a bandwidth derived from the data
+ *   costs no host read.  nx [Mx] = |x_i|^2, ny [Ny] = |y_j|^2.
+ *   Diagonal rule: diag_offset = -1 skips nothing; diag_offset >= 0: row i skips key j = i + diag_offset - the term
+ *   enters neither output (it is dropped, never formed and subtracted, so no trace of the computed d2 of a point with
+ *   itself is left); a row whose skipped key lies at or beyond Ny skips nothing.  A cloud with itself: diag_offset = 0.
+ *   Gradient: with weights[b] gammas[b] in place of weights[b] (K'), d/dx_i sum_j K_ij = -2 (ksum'[i] x_i - kbary'[i,:]).
+ *   Kernel: the structure of clipk_sinkhorn_apply (64 queries per workgroup, 64-key tiles on v_mfma_f32_32x32x2_f32, the
+ *   weight tile into LDS, a second MFMA product with the staged key rows); d2 is formed once per element and the B
+ *   exponentials applied to it - one tile walk for every bandwidth; the values lie in (0, 1], so there is no running
+ *   maximum; keys beyond Ny contribute 0.  Key-split slabs are summed in split order by a finalize launch; without kbary
+ *   the second product and the slabs are skipped.  The grid is that of clipk_sim_lse_bias (clipk_sim_lse_bias_plan).
+ *   Supported: Mx, Ny >= 1, P % 4 == 0, P <= 512, 1 <= B <= 8, X / Y / kbary / workspace 16-byte aligned.
+ * Anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED and the workspace helper returns 0.  Never allocates,
+ * never synchronises, capturable, no float atomics: results depend on the shapes and inputs alone. */
+size_t clipk_kernel_sums_workspace(int Mx, int Ny, int P, int B);
+int clipk_kernel_sums(const float* X, int Mx, const float* Y, int Ny, int P,
+                      const float* gammas /* device [B], > 0 */, const float* weights /* device [B] */, int B,
+                      const float* nx /*[Mx] = |x_i|^2*/, const float* ny /*[Ny] = |y_j|^2*/,
+                      long long diag_offset /* -1: none; else row i skips key j == i + diag_offset */,
+                      float* ksum /*[Mx] or NULL*/, float* kbary /*[Mx,P] or NULL*/,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
