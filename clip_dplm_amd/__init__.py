@@ -27,8 +27,10 @@ from . import diagnostics
 from .classifier import LinearClassifier, MLPClassifier, SimpleNonLinearClassifier, TransformerClassifier
 from . import classifier, probe
 from .ot import SinkhornResult, sinkhorn, sinkhorn_divergence
+from .ot import AssignmentResult, exact_assignment, wasserstein2_exact
 from . import ot
 from .flow import SchrodingerBridgeConditionalFlowMatcher, conditional_flow, flow_matching_loss
+from .flow import ExactOptimalTransportConditionalFlowMatcher, linear_conditional_flow
 from . import flow
 from .distribution import evaluate_distributions, frechet_distance, mmd2
 from . import distribution
@@ -48,5 +50,7 @@ __all__ = [
     "classifier", "probe", "MLPClassifier", "TransformerClassifier", "LinearClassifier", "SimpleNonLinearClassifier",
     "ot", "sinkhorn", "sinkhorn_divergence", "SinkhornResult",
     "flow", "SchrodingerBridgeConditionalFlowMatcher", "conditional_flow", "flow_matching_loss",
+    "AssignmentResult", "exact_assignment", "wasserstein2_exact",
+    "ExactOptimalTransportConditionalFlowMatcher", "linear_conditional_flow",
     "distribution", "mmd2", "frechet_distance", "evaluate_distributions",
 ]

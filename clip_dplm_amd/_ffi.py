@@ -149,6 +149,11 @@ SIGNATURES = {
     "clipk_sim_sample": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_kernel_sums_workspace": (_sz, [_i, _i, _i, _i]),
     "clipk_kernel_sums": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_sim_top2_bias_plan": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "clipk_sim_top2_bias_workspace": (_sz, [_i, _i, _i]),
+    "clipk_sim_top2_bias": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_auction_rounds_workspace": (_sz, [_i, _i]),
+    "clipk_auction_rounds": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "clipk_embed_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "clipk_embed_bwd_workspace": (_sz, [_i, _i, _i, _i]),
     "clipk_embed_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),

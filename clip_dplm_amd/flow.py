@@ -11,6 +11,14 @@ never written), re-pair the rows and build the bridge's location and conditional
 flow_matching_loss (tong/utils/losses.py:30-32) trains a field against ut.  The arithmetic on [n, P] is plain torch on
 any device - it is not a hot path; the solve and the draw need the device.  The reference's OTFlow network, which feeds
 ut into its own input, is not part of this module.
+
+The reference's other coupling, flow_type == 'exact_ot' (ExactOTFlow, ot_flow.py:58-68, on the library's
+ExactOptimalTransportConditionalFlowMatcher), re-pairs the batches with the optimal permutation and moves along straight
+lines: ExactOptimalTransportConditionalFlowMatcher below, on ot.exact_assignment, with
+
+    xt = t x1 + (1 - t) x0 + sigma noise,   ut = x1 - x0                                      (linear_conditional_flow)
+
+The library is not a dependency: these formulae are what this module commits to.
 """
 from __future__ import annotations
 
@@ -21,12 +29,11 @@ import torch
 
 from . import ops, ot
 
-__all__ = ["conditional_flow", "SchrodingerBridgeConditionalFlowMatcher", "flow_matching_loss"]
+__all__ = ["conditional_flow", "SchrodingerBridgeConditionalFlowMatcher", "flow_matching_loss", "linear_conditional_flow",
+           "ExactOptimalTransportConditionalFlowMatcher"]
 
 
-def conditional_flow(x0, x1, t, noise, sigma):
-    """(xt, ut) of the bridge between the paired rows x0, x1 [n, P] at times t [n] (or a 0-d tensor / number) under the
-    standard-normal `noise` [n, P]; the formulae are in the module's docstring."""
+def _flow_args(x0, x1, t, noise):
     for name, v in (("x0", x0), ("x1", x1), ("noise", noise)):
         if not isinstance(v, torch.Tensor):
             raise TypeError(f"{name} must be a tensor")
@@ -35,12 +42,24 @@ def conditional_flow(x0, x1, t, noise, sigma):
     t = torch.as_tensor(t, dtype=x0.dtype, device=x0.device)
     if t.dim() > 1 or (t.dim() == 1 and t.shape[0] != x0.shape[0]):
         raise ValueError(f"t must be a scalar or have one entry per row, got shape {tuple(t.shape)}")
-    if t.dim() == 1:
-        t = t.reshape(-1, *([1] * (x0.dim() - 1)))
+    return t.reshape(-1, *([1] * (x0.dim() - 1))) if t.dim() == 1 else t
+
+
+def conditional_flow(x0, x1, t, noise, sigma):
+    """(xt, ut) of the bridge between the paired rows x0, x1 [n, P] at times t [n] (or a 0-d tensor / number) under the
+    standard-normal `noise` [n, P]; the formulae are in the module's docstring."""
+    t = _flow_args(x0, x1, t, noise)
     mu = t * x1 + (1.0 - t) * x0
     xt = mu + sigma * torch.sqrt(t * (1.0 - t)) * noise
     ut = (1.0 - 2.0 * t) / (2.0 * t * (1.0 - t) + 1e-8) * (xt - mu) + x1 - x0
     return xt, ut
+
+
+def linear_conditional_flow(x0, x1, t, noise, sigma):
+    """(xt, ut) of the straight path between the paired rows x0, x1 [n, P] at times t [n] (or a 0-d tensor / number):
+    xt = t x1 + (1 - t) x0 + sigma noise, ut = x1 - x0."""
+    t = _flow_args(x0, x1, t, noise)
+    return t * x1 + (1.0 - t) * x0 + sigma * noise, x1 - x0
 
 
 def flow_matching_loss(v, target_v):
@@ -84,6 +103,51 @@ class SchrodingerBridgeConditionalFlowMatcher:
             t = torch.rand(n, dtype=a.dtype, device=a.device, generator=generator)
         noise = torch.randn(a.shape, dtype=a.dtype, device=a.device, generator=generator)
         xt, ut = conditional_flow(a, b, t, noise, self.sigma)
+        out = [t, xt, ut]
+        if return_noise:
+            out.append(noise)
+        if return_indices:
+            out.append((i, j))
+        return tuple(out)
+
+
+class ExactOptimalTransportConditionalFlowMatcher:
+    """The reference's 'exact_ot' coupling: batches re-paired by the optimal permutation between them
+    (ot.exact_assignment; solver_kw are its keyword arguments), straight conditional paths with noise scale sigma
+    (0 by default).  replace=True draws the n = N rows i uniformly with replacement under `generator`, as a draw from the
+    plan does; replace=False takes every row once, in order."""
+
+    def __init__(self, sigma: float = 0.0, replace: bool = True, **solver_kw):
+        sigma = float(sigma)
+        if not (sigma >= 0 and math.isfinite(sigma)):
+            raise ValueError(f"sigma must be non-negative and finite, got {sigma}")
+        unknown = set(solver_kw) - {"eps", "eps_rel", "eps_start_rel", "theta", "check_every", "max_rounds"}
+        if unknown:
+            raise TypeError(f"unknown solver arguments: {sorted(unknown)}")
+        self.sigma, self.replace, self.solver_kw = sigma, bool(replace), dict(solver_kw)
+
+    @torch.no_grad()
+    def sample_location_and_conditional_flow(self, x0, x1, t=None, return_noise=False, return_indices=False, generator=None):
+        """(t, xt, ut[, noise][, (i, j)]) for the batches x0, x1 [N, P] (f32, device): j = perm[i] under the optimal
+        matching, xt and ut = linear_conditional_flow(x0[i], x1[j], t, noise, sigma).  t [N]: given, or uniform on [0, 1)
+        under `generator`, which also drives the noise and (replace=True) the choice of i.  Raises RuntimeError when the
+        solve left rows unassigned."""
+        if isinstance(x0, torch.Tensor) and isinstance(t, torch.Tensor) and t.shape != (x0.shape[0],):
+            raise ValueError(f"t must have shape ({x0.shape[0]},), got {tuple(t.shape)}")
+        r = ot.exact_assignment(x0, x1, **self.solver_kw)
+        if bool((r.perm < 0).any()):
+            raise RuntimeError(f"exact_assignment did not converge ({r.reason}): no matching to pair the batches with")
+        n, dev = x0.shape[0], r.perm.device
+        if self.replace:
+            i = torch.randint(n, (n,), dtype=torch.int64, device=dev, generator=generator)
+        else:
+            i = torch.arange(n, dtype=torch.int64, device=dev)
+        j = r.perm.index_select(0, i)
+        a, b = r._x.index_select(0, i), r._y.index_select(0, j)
+        if t is None:
+            t = torch.rand(n, dtype=a.dtype, device=dev, generator=generator)
+        noise = torch.randn(a.shape, dtype=a.dtype, device=dev, generator=generator)
+        xt, ut = linear_conditional_flow(a, b, t, noise, self.sigma)
         out = [t, xt, ut]
         if return_noise:
             out.append(noise)

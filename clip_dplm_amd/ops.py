@@ -1009,7 +1009,97 @@ def sim_sample(x, y, scale, bias=None, seed=0, stream_offset=0, want_score=False
     return (idx, score) if want_score else idx
 
 
-KERNEL_SUMS_MAX_P = 512         # clipk_kernel_sums
+AUCTION_MAX_N = 65536           # clipk_auction_rounds: one workgroup compacts the unassigned rows
+
+
+def _int32_vector(name, t, n, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise TypeError(f"{name} must be an int32 tensor")
+    if t.shape != (n,) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor of shape ({n},), got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the clouds on {device}")
+
+
+def sim_top2_bias_plan(Mr: int, Ny: int):
+    """(64-query blocks, key-range splits) of the grid clipk_sim_top2_bias launches for Mr listed rows and Ny keys."""
+    nqb, ks = C.c_int(0), C.c_int(0)
+    check(_lib().clipk_sim_top2_bias_plan(int(Mr), int(Ny), C.byref(nqb), C.byref(ks)), "clipk_sim_top2_bias_plan")
+    return nqb.value, ks.value
+
+
+def sim_top2_bias(x, y, scale, bias=None, rows=None, n_active=None, want_best=True, want_gap=True, out=None):
+    """The two best keys of every listed row (include/clipk.h: clipk_sim_top2_bias): z_rj = scale * <x[row(r)], y_j> +
+    bias[j]; returns (idx int32 [Mr] = argmax_j, best f32 [Mr] = max_j, gap f32 [Mr] = best - runner-up, +inf with one
+    key), None for an output not wanted.  A higher z is best, equal z goes to the lower key, an exact tie gives gap 0.
+    scale: device scalar; bias [Ny] f32 or None.  rows: int32 [Mr] device indices into x's rows (repeats allowed; the
+    caller answers for their range, nothing is read back), None = every row.  n_active: one-element int32 device tensor,
+    only the list positions below it are computed, the others keep what `out` held.  out: (idx, best, gap) to write into
+    (best / gap may be None when not wanted)."""
+    Mr = _retrieval_args(x, y)[0]
+    if rows is not None:
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.numel() == 0:
+            raise TypeError("rows must be a non-empty 1-D int32 index tensor")
+        Mr = rows.shape[0]
+        _int32_vector("rows", rows, Mr, x.device)
+    if n_active is not None:
+        _int32_vector("n_active", n_active, 1, x.device)
+    dev = x.device
+    if out is not None:
+        idx, best, gap = out
+        _int32_vector("out[0]", idx, Mr, dev)
+        if (want_best and best is None) or (want_gap and gap is None):
+            raise ValueError("out lacks an output that is wanted")
+    else:
+        best = gap = None
+    Mx, Ny, P = _sinkhorn_args(x, y, scale, SIM_LSE_BIAS_MAX_P,
+                               (("bias", bias, y.shape[0]), ("out[1]", best, Mr), ("out[2]", gap, Mr)))
+    if out is None:
+        idx = torch.empty(Mr, dtype=torch.int32, device=dev)
+        best = torch.empty(Mr, dtype=torch.float32, device=dev) if want_best else None
+        gap = torch.empty(Mr, dtype=torch.float32, device=dev) if want_gap else None
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_sim_top2_bias_workspace(Mr, Ny, P), dev, "sinkhorn", stream)
+    check(_timed("sim_top2_bias", 2.0 * Mr * Ny * P,
+                 lambda: lib.clipk_sim_top2_bias(x.data_ptr(), Mx, ptr(rows), Mr, ptr(n_active), y.data_ptr(), Ny, P,
+                                                 scale.data_ptr(), ptr(bias), idx.data_ptr(),
+                                                 ptr(best) if want_best else None, ptr(gap) if want_gap else None,
+                                                 ws.data_ptr(), ws.numel(), stream)), "clipk_sim_top2_bias")
+    return idx, (best if want_best else None), (gap if want_gap else None)
+
+
+def auction_rounds(x, y, bias, eps, assigned, owner, n_unassigned, stalled, n_rounds: int):
+    """n_rounds bidding rounds of the auction on device state, enqueued without a host read (include/clipk.h:
+    clipk_auction_rounds): x, y [N, P] f32; bias [N] f32 = -|y_j|^2 - price_j, assigned [N] int32 (row -> key or -1) and
+    owner [N] int32 (key -> row or -1) are updated in place; eps: one-element f32 device tensor; n_unassigned, stalled:
+    one-element int32 device tensors - the count after the last round, and a flag set (never cleared) when an offer left
+    a price unchanged.  n_rounds = 0 only counts.  Returns None."""
+    if isinstance(n_rounds, bool) or not isinstance(n_rounds, int) or n_rounds < 0:
+        raise ValueError(f"n_rounds must be a non-negative int, got {n_rounds!r}")
+    if not isinstance(eps, torch.Tensor) or eps.dtype != torch.float32 or eps.numel() != 1:
+        raise TypeError("eps must be a one-element float32 device tensor")
+    N, Ny, P = _retrieval_args(x, y)
+    if bias is None:
+        raise ValueError("bias is needed")
+    if N != Ny:
+        raise ValueError(f"the auction needs clouds of one size, got {N} and {Ny}")
+    if N > AUCTION_MAX_N:
+        raise ValueError(f"the auction handles at most {AUCTION_MAX_N} rows, got {N}")
+    for name, t, n in (("assigned", assigned, N), ("owner", owner, N), ("n_unassigned", n_unassigned, 1), ("stalled", stalled, 1)):
+        _int32_vector(name, t, n, x.device)
+    _sinkhorn_args(x, y, eps, SIM_LSE_BIAS_MAX_P, (("bias", bias, N),))
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_auction_rounds_workspace(N, P), x.device, "sinkhorn", stream)
+    check(_timed("auction_rounds", 2.0 * N * N * P,
+                 lambda: lib.clipk_auction_rounds(x.data_ptr(), y.data_ptr(), N, P, bias.data_ptr(), eps.data_ptr(),
+                                                  assigned.data_ptr(), owner.data_ptr(), n_unassigned.data_ptr(),
+                                                  stalled.data_ptr(), n_rounds, ws.data_ptr(), ws.numel(), stream)),
+          "clipk_auction_rounds")
+
+
+KERNEL_SUMS_MAX_P = 512        # clipk_kernel_sums
 KERNEL_SUMS_MAX_B = 8
 
 

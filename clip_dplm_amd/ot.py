@@ -22,6 +22,9 @@ Every half-iteration is one ops.sim_lse_bias call; every plan-weighted sum one o
 draws from the plan (SinkhornResult.sample_targets / sample_pairs, what flow.py's matcher re-pairs its batches with) one
 ops.sim_sample call.  What is left to ATen is O((M + N) P) glue: squared norms, the closed-form mean cost, the duals
 from the potentials, the row gather of a draw.
+
+The exact (non-entropic) coupling of two clouds of one size - the reference's flow_type == 'exact_ot' - is the second half
+of this module: exact_assignment / wasserstein2_exact on the auction kernels of csrc/auction.hip.
 """
 from __future__ import annotations
 
@@ -33,7 +36,8 @@ import torch
 
 from . import ops
 
-__all__ = ["SinkhornResult", "sinkhorn", "sinkhorn_loss", "sinkhorn_divergence", "mean_cost", "evaluate_transport"]
+__all__ = ["SinkhornResult", "sinkhorn", "sinkhorn_loss", "sinkhorn_divergence", "mean_cost", "evaluate_transport",
+           "AssignmentResult", "exact_assignment", "wasserstein2_exact", "eps_schedule"]
 
 
 def mean_cost(x, y, a=None, b=None):
@@ -320,3 +324,172 @@ def evaluate_transport(transport, source, target, batch_size: int = 128, **sinkh
     if source.shape[1] == target.shape[1]:
         out["identity_divergence"] = float(sinkhorn_divergence(source.float().contiguous(), tgt, **sinkhorn_kwargs))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the exact coupling
+# For two clouds of one size N with uniform weights the optimal plan of min_P <P, C> is a permutation.  The reference
+# selects it with flow_type == 'exact_ot' (tong/models/flows/triple_flow.py:12-17, ot_flow.py:58-68) and takes it from a
+# library that copies the squared-distance matrix to the host and runs a network-simplex solver there, once per batch.
+# Here it is the auction algorithm (Bertsekas) on the device, the matrix never written: rows bid for keys on the values
+#     z_ij = 2 <x_i, y_j> - |y_j|^2 - p_j = 2 <x_i, y_j> + bias_j            (-C_ij - p_j up to the row constant |x_i|^2)
+# An unassigned row offers its best key the price rise gap + eps (gap = best - second-best value); the key goes to the
+# largest offer.  When every row holds a key, z_{i,perm(i)} >= max_j z_ij - eps on every row (eps-complementary
+# slackness), so the matching's mean cost is within eps of the optimum.  eps-scaling runs phases from a coarse eps down
+# to the wanted one, keeping the prices and resetting the assignment.  One round is ops.auction_rounds' three launches;
+# the host reads the unassigned count every check_every rounds.
+def _check_assignment_args(x, y, eps, eps_rel, eps_start_rel, theta, check_every, max_rounds):
+    """Every argument error of exact_assignment(), raised before anything is launched."""
+    for name, t in (("x", x), ("y", y)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.dim() != 2 or t.shape[0] == 0:
+            raise ValueError(f"{name} must be a non-empty 2-D tensor, got shape {tuple(t.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"x has {x.shape[1]} columns, y {y.shape[1]}")
+    if x.shape[0] != y.shape[0]:
+        raise ValueError(f"x has {x.shape[0]} rows, y {y.shape[0]}: clouds of unequal sizes have no permutation plan "
+                         "(use ot.sinkhorn for the entropic plan between them)")
+    P = x.shape[1]
+    if P == 0 or P % 4 or P > ops.SIM_LSE_BIAS_MAX_P:
+        raise ValueError(f"the width must be a multiple of 4 and at most {ops.SIM_LSE_BIAS_MAX_P}, got {P}")
+    if x.shape[0] > ops.AUCTION_MAX_N:
+        raise ValueError(f"at most {ops.AUCTION_MAX_N} rows, got {x.shape[0]}")
+    for name, v in (("eps", eps), ("eps_rel", eps_rel), ("eps_start_rel", eps_start_rel)):
+        if name == "eps" and v is None:
+            continue
+        if isinstance(v, (bool, torch.Tensor)) or not (float(v) > 0 and math.isfinite(float(v))):
+            raise ValueError(f"{name} must be a positive finite number, got {v!r}")
+    if not (float(theta) > 1 and math.isfinite(float(theta))):
+        raise ValueError(f"theta must be greater than 1, got {theta}")
+    if int(check_every) < 1:
+        raise ValueError("check_every must be at least 1")
+    if int(max_rounds) < 1:
+        raise ValueError("max_rounds must be at least 1")
+    if not x.is_cuda or not y.is_cuda:
+        raise ValueError("exact_assignment needs device tensors (there is no CPU fallback)")
+
+
+def eps_schedule(eps_start: float, eps: float, theta: float):
+    """The eps of every phase: eps_start, eps_start / theta, ... while above eps, then eps itself."""
+    out, e = [], float(eps_start)
+    while e > eps:
+        out.append(e)
+        e /= theta
+    out.append(float(eps))
+    return out
+
+
+@dataclass
+class AssignmentResult:
+    """One exact_assignment() solve.  perm [N] int64 (device): row i of x is matched to row perm[i] of y (-1 on a row left
+    unassigned when converged is False); cost: the mean squared distance of the matching; lower_bound, gap = cost -
+    lower_bound: the dual certificate in f64 - the optimum lies in [lower_bound, cost] and the auction guarantees gap <=
+    eps up to rounding (cost and gap are nan while rows are unassigned); eps: the last phase's, in units of the squared
+    distance; n_rounds: rounds enqueued (each phase's count rounded up to check_every), phase_rounds: the same per phase;
+    reason: 'converged', 'stalled' (an offer left an f32 price unchanged: eps is below the resolution of the prices) or
+    'max_rounds'.  bias [N] f32 = -|y_j|^2 - price_j, assigned / owner [N] int32: the device state the solve ended in."""
+    perm: torch.Tensor
+    cost: float
+    lower_bound: float
+    gap: float
+    eps: float
+    n_rounds: int
+    n_phases: int
+    converged: bool
+    reason: str
+    phase_rounds: tuple
+    bias: torch.Tensor
+    assigned: torch.Tensor
+    owner: torch.Tensor
+    _best: torch.Tensor = field(repr=False, default=None)
+    _x: torch.Tensor = field(repr=False, default=None)
+    _y: torch.Tensor = field(repr=False, default=None)
+
+    def duals(self):
+        """(f [N], g [N]) in f64: f_i = |x_i|^2 - max_j z_ij, g_j = -price_j = |y_j|^2 + bias_j.  f_i + g_j <= |x_i - y_j|^2
+        for every pair (up to the f32 rounding of the kernel's maxima) and mean f + mean g is lower_bound."""
+        x, y = self._x.double(), self._y.double()
+        return (x * x).sum(1) - self._best.double(), (y * y).sum(1) + self.bias.double()
+
+
+def _certificate(x, y, bias, best, perm, all_assigned):
+    """(cost, lower bound) in f64 from the device vectors."""
+    xd, yd = x.double(), y.double()
+    N = x.shape[0]
+    lower = float(((xd * xd).sum() + (yd * yd).sum() + bias.double().sum() - best.double().sum()) / N)
+    cost = float(((xd - yd.index_select(0, perm)) ** 2).sum(1).mean()) if all_assigned else float("nan")
+    return cost, lower
+
+
+@torch.no_grad()
+def exact_assignment(x, y, eps: Optional[float] = None, eps_rel: float = 1e-4, eps_start_rel: float = 0.03,
+                     theta: float = 8.0, check_every: int = 32, max_rounds: int = 100000) -> AssignmentResult:
+    """The optimal matching between the clouds x, y [N, P] (f32, device; P % 4 == 0, P <= 768, N <= 65536) under the cost
+    |x_i - y_j|^2, within eps of the optimum in mean cost, by eps-scaled auction rounds on the device.
+
+    eps: in units of the squared distance; None takes eps_rel x mean_cost(x, y).  Phases run eps_start_rel x the mean cost,
+    divided by theta from phase to phase while above eps, then eps itself.  check_every: rounds enqueued per host read of
+    the unassigned count (a round without bidders changes nothing, so the result does not depend on it).  The solve ends
+    without raising when a price stops moving or after max_rounds rounds: `converged` is then False and `reason` says
+    which.  N == 1 is answered on the host."""
+    _check_assignment_args(x, y, eps, eps_rel, eps_start_rel, theta, check_every, max_rounds)
+    x, y = x.detach().contiguous(), y.detach().contiguous()
+    dev, N = x.device, x.shape[0]
+    check_every, max_rounds = int(check_every), int(max_rounds)
+    bias = -(y * y).sum(1)
+    mc = float(mean_cost(x, y))
+    eps_f = float(eps) if eps is not None else float(eps_rel) * mc
+    if N == 1:
+        perm = torch.zeros(1, dtype=torch.int64, device=dev)
+        best = 2.0 * (x * y).sum(1) + bias
+        cost, lower = _certificate(x, y, bias, best, perm, True)
+        z = torch.zeros(1, dtype=torch.int32, device=dev)
+        return AssignmentResult(perm=perm, cost=cost, lower_bound=lower, gap=cost - lower, eps=eps_f, n_rounds=0, n_phases=0,
+                                converged=True, reason="converged", phase_rounds=(), bias=bias, assigned=z, owner=z.clone(),
+                                _best=best, _x=x, _y=y)
+    if not eps_f > 0:
+        raise ValueError("the mean cost of the clouds is zero (every point coincides): pass eps")
+    assigned = torch.empty(N, dtype=torch.int32, device=dev)
+    owner = torch.empty(N, dtype=torch.int32, device=dev)
+    state = torch.zeros(2, dtype=torch.int32, device=dev)          # {unassigned rows, stalled}
+    eps_t = torch.empty(1, dtype=torch.float32, device=dev)
+    total, phases, reason = 0, [], "converged"
+    for e in eps_schedule(float(eps_start_rel) * mc, eps_f, float(theta)):
+        eps_t.fill_(e)
+        assigned.fill_(-1)
+        owner.fill_(-1)
+        done = 0
+        while True:
+            k = min(check_every, max_rounds - total)
+            ops.auction_rounds(x, y, bias, eps_t, assigned, owner, state[0:1], state[1:2], k)
+            total, done = total + k, done + k
+            left, stalled = state.tolist()
+            if stalled:
+                reason = "stalled"
+            elif left and total >= max_rounds:
+                reason = "max_rounds"
+            if left == 0 or reason != "converged":
+                break
+        phases.append(done)
+        if reason != "converged":
+            break
+    perm = assigned.long()
+    all_assigned = bool(left == 0)
+    _, best, _ = ops.sim_top2_bias(x, y, torch.full((1,), 2.0, dtype=torch.float32, device=dev), bias=bias, want_gap=False)
+    cost, lower = _certificate(x, y, bias, best, perm, all_assigned)
+    return AssignmentResult(perm=perm, cost=cost, lower_bound=lower, gap=cost - lower, eps=eps_f, n_rounds=total,
+                            n_phases=len(phases), converged=reason == "converged", reason=reason,
+                            phase_rounds=tuple(phases), bias=bias, assigned=assigned, owner=owner, _best=best, _x=x, _y=y)
+
+
+def wasserstein2_exact(x, y, **solver_kw):
+    """mean_i |x_i - y_perm(i)|^2 under the optimal matching of exact_assignment(x, y, **solver_kw), a differentiable 0-d
+    tensor: the gradients flow through the gathered rows in plain torch, dW/dx_i = 2 (x_i - y_perm(i)) / N and its mirror
+    image - by the envelope theorem the permutation is a constant.  Raises RuntimeError when the solve left rows
+    unassigned."""
+    r = exact_assignment(x, y, **solver_kw)
+    if bool((r.perm < 0).any()):
+        raise RuntimeError(f"exact_assignment did not converge ({r.reason}): no matching to take the distance of")
+    return ((x - y.index_select(0, r.perm)) ** 2).sum(1).mean()

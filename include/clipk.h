@@ -893,6 +893,57 @@ int clipk_kernel_sums(const float* X, int Mx, const float* Y, int Ny, int P,
                       float* ksum /*[Mx] or NULL*/, float* kbary /*[Mx,P] or NULL*/,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The exact (non-entropic) coupling of two equal-size f32 clouds X, Y [N,P] under the cost |x_i - y_j|^2 by the auction
+ * algorithm (Bertsekas) without the N x N matrix: with uniform weights the optimal plan is a permutation.  The reference
+ * selects it with flow_type == 'exact_ot' (tong/models/flows/triple_flow.py:12-17, ot_flow.py:58-68) and takes it from a
+ * library that solves the materialised matrix on the host.
+ *
+ * clipk_sim_top2_bias - the two best keys of every listed query row:
+ *     z_rj   = scale[0] <X[row(r)], Y_j> + bias[j]                 row(r) = rows ? rows[r] : r,   r in [0, Mr)
+ *     idx[r] = argmax_j z_rj,   best[r] = max_j z_rj,   gap[r] = best[r] - max_{j != idx[r]} z_rj   (+inf when Ny == 1)
+ *   bias [Ny] or NULL (zeros).  rows [Mr] int32 or NULL: indices into X's Mx rows, repeats allowed (without rows,
+ *   Mr <= Mx).  n_active: a device int32 or NULL (= Mr): only the list positions below min(n_active[0], Mr) are
+ *   computed; a query block at or beyond it returns before its first barrier and outputs beyond it are untouched.
+ *   idx int32 [Mr]; best, gap f32 [Mr], each may be NULL.
+ *   Rule at every merge level (within a lane, lane halves, the two key-waves, key splits in the finalize launch): the
+ *   higher z is best, equal z goes to the lower key, the runner-up is the maximum of what is left - an exact tie gives
+ *   gap 0.  The merge of (z1, k1, z2) triples is associative and commutative: the result depends on the inputs alone,
+ *   never on the grid or on n_active - rows [r0, r1) of a launch equal a launch of those rows.
+ *   Kernel: the tiling of clipk_sim_sample (64 queries per workgroup, 64-key tiles on v_mfma_f32_32x32x2_f32, keys beyond
+ *   Ny masked; the query row pointers are a gather) with a running (best, arg best, runner-up) per lane.  The key split
+ *   is this entry's own, a fixed number of tiles per split whatever the row count (clipk_sim_top2_bias_plan reports the
+ *   grid: nqb 64-query blocks x ksplit key splits): one active query block still fills the device.
+ *   Supported: Mx, Mr, Ny >= 1, P % 4 == 0, P <= 768, X / Y / workspace 16-byte aligned.
+ *
+ * clipk_auction_rounds - n_rounds Jacobi bidding rounds on device state, no host read between them:
+ *     assigned [N] int32 row -> key or -1;  owner [N] int32 key -> row or -1 (mutually inverse);
+ *     bias [N] f32 = -|y_j|^2 - price_j;  eps: device f32 scalar (> 0), in units of the squared distance.
+ *   One round: (1) the unassigned rows are compacted into a list in rising row order; (2) clipk_sim_top2_bias over that
+ *   list with scale 2 and the device count; (3) each bidder r offers inc = gap + eps to key idx[r]; a key keeps the
+ *   largest offer, an equal offer goes to the lower row (a 64-bit integer atomicMax on (bits of inc, complement of the
+ *   row): inc >= 0, so its bit pattern is ordered, and integer max does not depend on the order of arrival); (4) every
+ *   key with an offer frees its previous owner, takes the winner and sets bias[j] -= inc; if that leaves bias[j]
+ *   unchanged (eps below the f32 resolution of the prices) stalled[0] is set to 1 (it is never cleared here).
+ *   On return (in stream order) the state is consistent and n_unassigned[0] is the number of unassigned rows after the
+ *   last round.  A round with no bidders changes nothing, so trailing rounds are harmless and the state after k rounds
+ *   does not depend on how the calls were chunked (n_rounds = 0 only counts).  N <= 65536 (one workgroup compacts).
+ *   Supported: 1 <= N <= 65536, P % 4 == 0, P <= 768, X / Y / workspace 16-byte aligned.
+ * Anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED before any launch and the workspace helpers return 0.
+ * Never allocates, never synchronises, capturable, no float atomics. */
+int clipk_sim_top2_bias_plan(int Mr, int Ny, int* nqb, int* ksplit);
+size_t clipk_sim_top2_bias_workspace(int Mr, int Ny, int P);
+int clipk_sim_top2_bias(const float* X, int Mx, const int* rows /*[Mr] or NULL*/, int Mr,
+                        const int* n_active /* device int32 or NULL */, const float* Y, int Ny, int P,
+                        const float* scale /* device scalar */, const float* bias /*[Ny] or NULL*/, int* idx /*[Mr]*/,
+                        float* best /*[Mr] or NULL*/, float* gap /*[Mr] or NULL*/, void* workspace,
+                        size_t workspace_bytes, void* stream);
+size_t clipk_auction_rounds_workspace(int N, int P);
+int clipk_auction_rounds(const float* X, const float* Y, int N, int P, float* bias /*[N]*/,
+                         const float* eps /* device scalar */, int* assigned /*[N]*/, int* owner /*[N]*/,
+                         int* n_unassigned /* device int32 */, int* stalled /* device int32 */, int n_rounds,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
