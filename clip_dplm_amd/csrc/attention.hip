@@ -73,6 +73,12 @@ __device__ __forceinline__ long stat_at(const AP& p, int b, int h, int H, int L,
 
 constexpr float LOG2E = 1.4426950408889634f;
 
+// A row's lse as the backward kernels subtract it, in base 2: p = 2^(s c2 - lse2).  A row with no valid key has lse = -inf
+// and every score s = -inf: -inf + inf would be NaN, so the row's -inf is held at the most negative finite float -
+// s c2 - lse2 stays -inf, p = 2^-inf = 0 and the row's gradients are zero (one v_max per query row, nothing in the sweeps).
+// (Not a compare + select to +inf, the form used for rows past the end: with it hipcc spilled in attn_bwd_fused96_kernel.)
+__device__ __forceinline__ float live_lse2(float lse) { return fmaxf(lse * LOG2E, -3.0e38f); }
+
 // v_exp_f32 directly: every argument here is <= 0 (or -inf), so the denormal-range fix-up of exp2f() is dead weight
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -687,7 +693,7 @@ __global__ __launch_bounds__(256, Geo<DP>::WG_BWD) void attn_bwd_dq_kernel(const
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     int q = q0 + wid * 32 + qt * 16 + li; q = q < L ? q : L - 1;
-    lse2[qt] = p.lse[stat_at(p, b, h, H, L, row0, q)] * LOG2E;
+    lse2[qt] = live_lse2(p.lse[stat_at(p, b, h, H, L, row0, q)]);
     dl[qt] = delta_l[wid * 32 + qt * 16 + li];
   }
   __syncthreads();
@@ -872,7 +878,7 @@ __global__ __launch_bounds__(256, Geo<DP>::WG_BWD) void attn_bwd_dkv_kernel(cons
       const int q = qb * QB + tid;
       const bool ok = q < L;
       // queries past the end: lse = +inf makes p = exp2(-inf) = 0
-      lse_l[tid] = ok ? p.lse[stat_at(p, b, h, H, L, row0, q)] * LOG2E : INFINITY;
+      lse_l[tid] = ok ? live_lse2(p.lse[stat_at(p, b, h, H, L, row0, q)]) : INFINITY;
       dl_l[tid] = ok ? -p.delta[stat_at(p, b, h, H, L, row0, q)] : 0.f;      // NEGATED: the dP accumulators start from it
     }
     __syncthreads();
@@ -1108,7 +1114,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
     const int tq = tid + opaque_zero();
     const int ci = tq & 3, r0 = tq >> 2;
     // ---- K / V rows to LDS, lse and delta = rowsum(dO * O) to their arrays, dQ image to zero
-    if (tid < LQ) lse_l[tid] = tid < L ? R.lse * LOG2E : INFINITY;       // +inf: p = 2^-inf = 0 past the end
+    if (tid < LQ) lse_l[tid] = tid < L ? live_lse2(R.lse) : INFINITY;       // +inf: p = 2^-inf = 0 past the end
     if (cpr < 4 && ci >= cpr) {                            // the pad chunk: zeros in LDS
       const u32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -1480,7 +1486,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
         }
       }
     }
-    lse_l[tid] = tid < L ? lse_r * LOG2E : INFINITY;       // p = 2^-inf = 0 past the end
+    lse_l[tid] = tid < L ? live_lse2(lse_r) : INFINITY;    // p = 2^-inf = 0 past the end
     store_block(0);
     __syncthreads();
     finish_delta(0);
@@ -1787,7 +1793,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused96w8_kernel(const AP p) 
         *reinterpret_cast<u32x4*>(ktile + r * RS + ch * 16) = kr[ps];
       }
     }
-    if (tid < LQ) lse_l[tid] = tid < L ? lse_r * LOG2E : INFINITY;       // p = 2^-inf = 0 past the end
+    if (tid < LQ) lse_l[tid] = tid < L ? live_lse2(lse_r) : INFINITY;    // p = 2^-inf = 0 past the end
     store_block(0);
     __syncthreads();
     finish_delta(0);

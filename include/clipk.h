@@ -682,7 +682,10 @@ int clipk_attn_fwd(const void* qkv, const uint8_t* key_mask, const float* rope_c
                    void* out, float* lse, int B, int L, int H, int D, float q_scale, float dropout_p,
                    uint32_t dropout_seed, void* stream);
 /* Backward: dqkv bf16 [B*L, 3*H*D] from dout bf16 [B*L, H*D]; recomputes P from qkv + lse.
- * delta: f32 [B,H,L] scratch (rowsum(dout*out)) provided by the caller.
+ * delta: f32 [B,H,L] provided by the caller; the backward writes delta = rowsum(dout * out) of the stored bf16 `out` there.
+ * A sequence with no valid key (key_mask all zero): clipk_attn_fwd gives zero `out` rows and lse = -inf, and the backward
+ * gives zero dqkv rows (and delta = 0) for it - no NaN - whatever kernel the shape and the options select; `dout` is not
+ * read as zero at masked positions: a key mask hides keys, not queries.
  * prerotated: 0 = q / k in qkv are un-rotated (the kernels rotate at staging when given tables); 1 = already rotated
  * (clipk_rope_qk / clipk_attn_fwd_rot / clipk_gemm_nt's RoPE epilogue), rotate-half column order; 2 = already rotated, heads in
  * PAIR-INTERLEAVED column order (clipk_gemm_nt rope_interleaved): the gradients leave through the matching RoPE^T. */
@@ -760,6 +763,7 @@ int clipk_pool_varlen_bwd(const float* dy, const int* cu_seqlens, float* dx, int
  * attention row.  Here sequence b is rows [cu_seqlens[b], cu_seqlens[b+1]) of the packed tensors:
  *   qkv bf16 [T, 3*H*D], out / dout bf16 [T, H*D], dqkv bf16 [T, 3*H*D], lse / delta f32 [H, T];
  *   cu_seqlens: DEVICE int32 [B+1] (cu[0] = 0, cu[B] = T); max_len = longest sequence (grid sizing only);
+ *   every sequence must have at least one row, cu[b+1] - cu[b] >= 1: a length of 0 is not supported (nor tested);
  *   rope tables (optional, ESM head dims): f32 [>= max_len, D/2], indexed by the position inside the sequence.
  * Arithmetic is that of clipk_attn_fwd / clipk_attn_bwd on each sequence alone. */
 int clipk_attn_varlen_fwd(const void* qkv, const int* cu_seqlens, const float* rope_cos, const float* rope_sin,
