@@ -143,6 +143,9 @@ SIGNATURES = {
     "clipk_sim_lse_bias_plan": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "clipk_sim_lse_bias_workspace": (_sz, [_i, _i, _i]),
     "clipk_sim_lse_bias": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_sim_lse_bias_x3_plan": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "clipk_sim_lse_bias_x3_workspace": (_sz, [_i, _i, _i]),
+    "clipk_sim_lse_bias_x3": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipk_sinkhorn_apply_workspace": (_sz, [_i, _i, _i]),
     "clipk_sinkhorn_apply": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_sim_sample_workspace": (_sz, [_i, _i, _i]),

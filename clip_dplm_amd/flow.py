@@ -70,9 +70,10 @@ def flow_matching_loss(v, target_v):
 class SchrodingerBridgeConditionalFlowMatcher:
     """sigma: the bridge's noise scale.  reg: the entropic regularisation handed to ot.sinkhorn as eps, None = 2 sigma^2
     (the reference's setting).  n_iters, tol: the solver's; tol=None runs exactly n_iters iterations and reads nothing
-    back from the device."""
+    back from the device.  precision: ot.sinkhorn's ("f32" or "bf16x3"; the draws always use the exact f32 kernel)."""
 
-    def __init__(self, sigma: float, reg: Optional[float] = None, n_iters: int = 50, tol: Optional[float] = None):
+    def __init__(self, sigma: float, reg: Optional[float] = None, n_iters: int = 50, tol: Optional[float] = None,
+                 precision: str = "f32"):
         sigma = float(sigma)
         if not (sigma > 0 and math.isfinite(sigma)):
             raise ValueError(f"sigma must be positive and finite, got {sigma}")
@@ -83,7 +84,9 @@ class SchrodingerBridgeConditionalFlowMatcher:
             raise ValueError("n_iters must be at least 1")
         if tol is not None and not float(tol) > 0:
             raise ValueError(f"tol must be positive or None, got {tol}")
-        self.sigma, self.reg, self.n_iters, self.tol = sigma, reg, int(n_iters), tol
+        if precision not in ot.PRECISIONS:
+            raise ValueError(f"precision must be one of {ot.PRECISIONS}, got {precision!r}")
+        self.sigma, self.reg, self.n_iters, self.tol, self.precision = sigma, reg, int(n_iters), tol, precision
 
     @torch.no_grad()
     def sample_location_and_conditional_flow(self, x0, x1, t=None, return_noise=False, return_indices=False, seed=0,
@@ -95,7 +98,7 @@ class SchrodingerBridgeConditionalFlowMatcher:
         if isinstance(x0, torch.Tensor) and isinstance(t, torch.Tensor) and t.shape != (x0.shape[0],):
             raise ValueError(f"t must have shape ({x0.shape[0]},), got {tuple(t.shape)}")
         ops._seed_offset(seed, 0)
-        r = ot.sinkhorn(x0, x1, eps=self.reg, n_iters=self.n_iters, tol=self.tol)
+        r = ot.sinkhorn(x0, x1, eps=self.reg, n_iters=self.n_iters, tol=self.tol, precision=self.precision)
         n = x0.shape[0]
         i, j = r.sample_pairs(n, seed=seed, generator=generator)
         a, b = r._x.index_select(0, i), r._y.index_select(0, j)

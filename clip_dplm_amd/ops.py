@@ -940,6 +940,61 @@ def sim_lse_bias(x, y, scale, bias=None, logw=None, prev=None, average=False, ou
     return out
 
 
+def sim_lse_bias_x3_plan(Mx: int, Ny: int):
+    """(128-query blocks, key-range splits) of the grid clipk_sim_lse_bias_x3 launches for these sizes."""
+    nqb, ks = C.c_int(0), C.c_int(0)
+    check(_lib().clipk_sim_lse_bias_x3_plan(int(Mx), int(Ny), C.byref(nqb), C.byref(ks)), "clipk_sim_lse_bias_x3_plan")
+    return nqb.value, ks.value
+
+
+def sim_lse_bias_x3(xhi, xlo, yhi, ylo, P: int, scale, bias=None, logw=None, prev=None, average=False, out=None, err=None):
+    """sim_lse_bias with the product as a bf16x3 split on the bf16 matrix pipe (include/clipk.h: clipk_sim_lse_bias_x3):
+    nv[i] = logw[i] - logsumexp_j(scale * A_ij + bias[j]), A = hi.hi + hi.lo + lo.hi.  xhi / xlo [Mx, plane_pitch(P)] and
+    yhi / ylo [Ny, plane_pitch(P)]: the planes split_bf16 writes for the two clouds of width P.  Everything else as in
+    sim_lse_bias; |nv - sim_lse_bias's| <= |scale| max|x| max|y| retrieval.prefilter_eps_rel(P, "bf16x3") + eps_abs."""
+    P = int(P)
+    if P <= 0 or P % 4 or P > SIM_LSE_BIAS_MAX_P:
+        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {SIM_LSE_BIAS_MAX_P})")
+    for name, t in (("xhi", xhi), ("xlo", xlo), ("yhi", yhi), ("ylo", ylo)):
+        if not isinstance(t, torch.Tensor) or t.element_size() != 2:
+            raise TypeError(f"{name} must be a 2-byte (bf16) plane tensor")
+        if t.dim() != 2 or t.shape[0] == 0 or t.shape[1] != plane_pitch(P) or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError(f"{name} must be a contiguous, 16-byte aligned [rows, {plane_pitch(P)}] plane, got "
+                             f"{tuple(t.shape)}")
+    if xlo.shape != xhi.shape or ylo.shape != yhi.shape:
+        raise ValueError("the hi and lo planes of a cloud must have one shape")
+    Mx, Ny = xhi.shape[0], yhi.shape[0]
+    if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or scale.numel() != 1:
+        raise TypeError("scale must be a one-element float32 device tensor")
+    vectors = (("bias", bias, Ny), ("logw", logw, Mx), ("prev", prev, Mx), ("out", out, Mx),
+               ("err", None if err is None else err.reshape(-1), 1))
+    for name, t, n in vectors:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.shape != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous tensor of shape ({n},), got {tuple(t.shape)}")
+    if (average or err is not None) and prev is None:
+        raise ValueError("average=True and err need prev")
+    tensors = (xhi, xlo, yhi, ylo, scale, *(v[1] for v in vectors))
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise ValueError("the Sinkhorn kernels need device tensors (there is no CPU fallback)")
+    _need_cuda(*tensors)
+    if out is None:
+        out = torch.empty(Mx, dtype=torch.float32, device=xhi.device)
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_sim_lse_bias_x3_workspace(Mx, Ny, P), xhi.device, "sinkhorn", stream)
+    check(_timed("sim_lse_bias_x3", 6.0 * Mx * Ny * plane_pitch(P),
+                 lambda: lib.clipk_sim_lse_bias_x3(xhi.data_ptr(), xlo.data_ptr(), Mx, yhi.data_ptr(), ylo.data_ptr(), Ny, P,
+                                                   scale.data_ptr(), ptr(bias), ptr(logw), ptr(prev), int(bool(average)),
+                                                   out.data_ptr(), ptr(err), ws.data_ptr(), ws.numel(), stream)),
+          "clipk_sim_lse_bias_x3")
+    return out
+
+
 def sinkhorn_apply(x, y, scale, u, v, nx=None, ny=None, want_mass=True, want_bary=True, want_cost=True):
     """Row sums over the plan P_ij = exp(scale * <x_i, y_j> + u_i + v_j) (include/clipk.h: clipk_sinkhorn_apply):
     (mass [Mx] = sum_j P_ij, bary [Mx, P] = sum_j P_ij y_j, cost [Mx] = sum_j P_ij |x_i - y_j|^2), None for an output not

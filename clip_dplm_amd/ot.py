@@ -18,8 +18,9 @@ With S = (2 / eps) x y^T and scaled log-potentials u, v (the squared norms are a
     symmetric problem (y is x, a = b):  u <- (u + log a - LSE(S + u)) / 2, one potential
     S_eps(x, y) = OT_eps(x, y) - OT_eps(x, x) / 2 - OT_eps(y, y) / 2                                   (debiased divergence)
 
-Every half-iteration is one ops.sim_lse_bias call; every plan-weighted sum one ops.sinkhorn_apply call; every batch of
-draws from the plan (SinkhornResult.sample_targets / sample_pairs, what flow.py's matcher re-pairs its batches with) one
+Every half-iteration is one ops.sim_lse_bias call (ops.sim_lse_bias_x3, the product as a bf16x3 split on the bf16 matrix
+pipe, for all but the last iteration of a precision="bf16x3" solve); every plan-weighted sum one ops.sinkhorn_apply
+call; every batch of draws from the plan (SinkhornResult.sample_targets / sample_pairs, what flow.py's matcher re-pairs its batches with) one
 ops.sim_sample call.  What is left to ATen is O((M + N) P) glue: squared norms, the closed-form mean cost, the duals
 from the potentials, the row gather of a draw.
 
@@ -37,7 +38,7 @@ import torch
 from . import ops
 
 __all__ = ["SinkhornResult", "sinkhorn", "sinkhorn_loss", "sinkhorn_divergence", "mean_cost", "evaluate_transport",
-           "AssignmentResult", "exact_assignment", "wasserstein2_exact", "eps_schedule"]
+           "AssignmentResult", "exact_assignment", "wasserstein2_exact", "eps_schedule", "PRECISIONS"]
 
 
 def mean_cost(x, y, a=None, b=None):
@@ -96,7 +97,9 @@ class SinkhornResult:
     """Potentials and value of one solve.  f, g: the dual potentials; u, v: the scaled log-potentials of the plan
     P_ij = exp((2 / eps) <x_i, y_j> + u_i + v_j); eps, value (= <a, f> + <b, g>) and marginal_error (the L1 distance of the
     plan's row marginal from a; the column marginal is exact after a v update) are 0-d device tensors, so that a solve
-    with tol=None does not wait for the device once its arguments are checked; n_iters: iterations run."""
+    with tol=None does not wait for the device once its arguments are checked; n_iters: iterations run.  precision: the
+    solve's ("f32" or "bf16x3"); logit_error_bound: 0-d device tensor, the eta no logit of the split iterations was further
+    from the exact one than (0 for f32) - DESIGN.md has what it bounds in the result."""
     f: torch.Tensor
     g: torch.Tensor
     u: torch.Tensor
@@ -105,6 +108,8 @@ class SinkhornResult:
     value: torch.Tensor
     n_iters: int
     marginal_error: torch.Tensor
+    precision: str = "f32"
+    logit_error_bound: Optional[torch.Tensor] = None
     _x: torch.Tensor = field(repr=False, default=None)
     _y: torch.Tensor = field(repr=False, default=None)
     _scale: torch.Tensor = field(repr=False, default=None)
@@ -166,9 +171,32 @@ class SinkhornResult:
         return i, self._draw(i, seed)                  # (in range by construction: no host read)
 
 
+PRECISIONS = ("f32", "bf16x3")
+
+
+def _split_planes(t):
+    """(hi, lo, max row norm [1]) of a cloud: the bf16 planes ops.split_bf16 writes, once per solve."""
+    pitch = ops.plane_pitch(t.shape[1])
+    hi = torch.empty((t.shape[0], pitch), dtype=torch.bfloat16, device=t.device)
+    lo = torch.empty_like(hi)
+    norm = torch.zeros(1, dtype=torch.float32, device=t.device)
+    ops.split_bf16(t, hi, lo, norm)
+    return hi, lo, norm
+
+
+def _logit_error_bound(P, scale, xnorm, ynorm):
+    """eta of include/clipk.h (clipk_sim_lse_bias_x3) as a 0-d device tensor: no split logit scale * A_ij is further from
+    scale * <x_i, y_j> than |scale| max|x| max|y| eps_rel + eps_abs, in either direction of the half-iteration."""
+    from .retrieval import prefilter_eps_rel
+    s = scale.abs()
+    eta = s * xnorm * ynorm * prefilter_eps_rel(P, "bf16x3") + (s * P * (xnorm + ynorm + 1.0) + 1.0) * 2.0 ** -120
+    return eta.reshape(())
+
+
 @torch.no_grad()
 def sinkhorn(x, y, eps: Union[None, float, torch.Tensor] = None, eps_rel: float = 0.05, a=None, b=None, n_iters: int = 100,
-             tol: Optional[float] = 1e-5, check_every: int = 10, symmetric: bool = False) -> SinkhornResult:
+             tol: Optional[float] = 1e-5, check_every: int = 10, symmetric: bool = False,
+             precision: str = "f32") -> SinkhornResult:
     """Solve OT_eps between the clouds x [M, P] and y [N, P] (f32, device; P % 4 == 0, P <= 768).
 
     eps: the regularisation in units of the squared distance (a number or a 0-d device tensor); None takes eps_rel x the
@@ -178,7 +206,16 @@ def sinkhorn(x, y, eps: Union[None, float, torch.Tensor] = None, eps_rel: float 
     first launch, which is left out while a graph is being captured);
     with a tol the L1 marginal error (a device scalar the update kernel leaves behind) is read every check_every
     iterations and the solve stops once it is below tol.  symmetric=True (y is x, b is a or None): the averaged update with one
-    potential; the alternating one leaves the two potentials of a self problem apart for hundreds of iterations."""
+    potential; the alternating one leaves the two potentials of a self problem apart for hundreds of iterations.
+
+    precision="bf16x3": the clouds are split once into bf16 hi / lo planes and the iterations run on the bf16 matrix pipe
+    (ops.sim_lse_bias_x3), whose logits are within the result's `logit_error_bound` of the exact ones; the LAST
+    iteration and the final error pass run on the exact f32 kernel, so the column marginal is exact and marginal_error is
+    the exact plan's.  tol=None: n_iters - 1 split iterations and one exact one, no host read.  With a tol: split
+    iterations (looked at every check_every) until their error is below tol or n_iters - 1 have run, then exact
+    iterations, each looked at, until the exact error is below tol or n_iters is used up; n_iters counts both phases."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
     _check_args(x, y, eps, eps_rel, a, b, n_iters, tol, check_every, symmetric)
     x = x.detach().contiguous()
     y = x if symmetric else y.detach().contiguous()
@@ -199,29 +236,50 @@ def sinkhorn(x, y, eps: Union[None, float, torch.Tensor] = None, eps_rel: float 
     scale = (2.0 / eps_t).reshape(1)
     err = torch.zeros(1, dtype=torch.float32, device=dev)
     n_iters, check_every = int(n_iters), int(check_every)
-    done = n_iters
-    if symmetric:
-        u = loga.clone()
-        for it in range(n_iters):
-            look = tol is not None and (it + 1) % check_every == 0
-            if look:
-                err.zero_()
-            ops.sim_lse_bias(x, x, scale, bias=u, logw=loga, prev=u, average=True, out=u, err=err if look else None)
-            if look and err.item() < tol:           # the error of the potential this update replaced
-                done = it + 1
-                break
-        v = u
+    split = precision == "bf16x3"
+    if split:
+        xh, xl, xnorm = _split_planes(x)
+        yh, yl, ynorm = (xh, xl, xnorm) if symmetric else _split_planes(y)
+        bound = _logit_error_bound(x.shape[1], scale, xnorm, ynorm)
     else:
-        u, v = torch.empty_like(loga), logb.clone()
-        for it in range(n_iters):
-            look = tol is not None and it > 0 and (it + 1) % check_every == 0
-            if look:
-                err.zero_()
-            ops.sim_lse_bias(x, y, scale, bias=v, logw=loga, prev=u if look else None, out=u, err=err if look else None)
-            ops.sim_lse_bias(y, x, scale, bias=u, logw=logb, out=v)
-            if look and err.item() < tol:           # the row error of the plan before this iteration
-                done = it + 1
-                break
+        bound = torch.zeros((), dtype=torch.float32, device=dev)
+
+    def update_u(exact, **kw):                      # the half-iteration with x as the queries
+        if exact:
+            return ops.sim_lse_bias(x, y, scale, **kw)
+        return ops.sim_lse_bias_x3(xh, xl, yh, yl, x.shape[1], scale, **kw)
+
+    def update_v(exact, **kw):                      # ... with y as the queries
+        if exact:
+            return ops.sim_lse_bias(y, x, scale, **kw)
+        return ops.sim_lse_bias_x3(yh, yl, xh, xl, x.shape[1], scale, **kw)
+
+    u = loga.clone() if symmetric else torch.empty_like(loga)
+    v = u if symmetric else logb.clone()
+
+    def iteration(it, exact, look):
+        """Iteration `it` (0-based); with look, whether the error of the plan it replaced is below tol (a host read)."""
+        look = look and (symmetric or it > 0)       # the alternating update's first iteration has no u to compare with
+        if look:
+            err.zero_()
+        if symmetric:
+            update_u(exact, bias=u, logw=loga, prev=u, average=True, out=u, err=err if look else None)
+        else:
+            update_u(exact, bias=v, logw=loga, prev=u if look else None, out=u, err=err if look else None)
+            update_v(exact, bias=u, logw=logb, out=v)
+        return look and err.item() < tol
+
+    done = 0
+    n_split = n_iters - 1 if split else 0           # the split phase leaves at least one iteration to the exact kernel
+    while done < n_split:
+        done += 1
+        if iteration(done - 1, False, tol is not None and done % check_every == 0):
+            break
+    while done < n_iters:
+        done += 1
+        # exact iterations of a split solve are each looked at; those of an f32 solve every check_every
+        if iteration(done - 1, True, tol is not None and (split or done % check_every == 0)):
+            break
     # the returned plan's own row error: one more half-iteration's worth of work, its update discarded
     err.zero_()
     ops.sim_lse_bias(x, y, scale, bias=v, logw=loga, prev=u, out=torch.empty_like(u), err=err)
@@ -230,6 +288,7 @@ def sinkhorn(x, y, eps: Union[None, float, torch.Tensor] = None, eps_rel: float 
     va = f.mean() if a is None else (a * f).sum()
     vb = va if symmetric else (g.mean() if b is None else (b * g).sum())
     return SinkhornResult(f=f, g=g, u=u, v=v, eps=eps_t, value=va + vb, n_iters=done, marginal_error=err.reshape(()),
+                          precision=precision, logit_error_bound=bound,
                           _x=x, _y=y, _scale=scale, _nx=nx, _ny=ny, _a=a)
 
 
@@ -291,24 +350,28 @@ class _SinkhornDivergenceFn(torch.autograd.Function):
         return gx, gy, None, None, None, None
 
 
-def _solver_kw(eps, eps_rel, n_iters, tol, check_every):
-    return dict(eps=eps, eps_rel=eps_rel, n_iters=n_iters, tol=tol, check_every=check_every)
+def _solver_kw(eps, eps_rel, n_iters, tol, check_every, precision):
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    return dict(eps=eps, eps_rel=eps_rel, n_iters=n_iters, tol=tol, check_every=check_every, precision=precision)
 
 
 def sinkhorn_loss(x, y, eps=None, eps_rel: float = 0.05, a=None, b=None, n_iters: int = 100, tol: Optional[float] = 1e-5,
-                  check_every: int = 10):
+                  check_every: int = 10, precision: str = "f32"):
     """OT_eps(x, y) as a differentiable 0-d tensor.  Gradients flow to x and y only (not to the weights, and eps - also
     when it is derived from the clouds - is a constant); they are the envelope-theorem gradients, exact at convergence:
-    nothing is unrolled, so a solve stopped early gives the gradient of its current plan.  Gradients need P <= 512."""
-    return _SinkhornLossFn.apply(x, y, a, b, _solver_kw(eps, eps_rel, n_iters, tol, check_every))
+    nothing is unrolled, so a solve stopped early gives the gradient of its current plan.  Gradients need P <= 512.
+    precision: sinkhorn()'s; the plan sums of the gradient are always exact f32."""
+    return _SinkhornLossFn.apply(x, y, a, b, _solver_kw(eps, eps_rel, n_iters, tol, check_every, precision))
 
 
 def sinkhorn_divergence(x, y, eps=None, eps_rel: float = 0.05, a=None, b=None, n_iters: int = 100,
-                        tol: Optional[float] = 1e-5, check_every: int = 10):
+                        tol: Optional[float] = 1e-5, check_every: int = 10, precision: str = "f32"):
     """The debiased divergence S_eps(x, y) = OT_eps(x, y) - OT_eps(x, x) / 2 - OT_eps(y, y) / 2 as a differentiable 0-d
     tensor: zero for equal clouds, positive otherwise.  The self terms use the symmetric update and the cross term's eps.
-    Gradients as in sinkhorn_loss."""
-    return _SinkhornDivergenceFn.apply(x, y, a, b, y is x and b is a, _solver_kw(eps, eps_rel, n_iters, tol, check_every))
+    Gradients and precision as in sinkhorn_loss."""
+    return _SinkhornDivergenceFn.apply(x, y, a, b, y is x and b is a,
+                                       _solver_kw(eps, eps_rel, n_iters, tol, check_every, precision))
 
 
 @torch.no_grad()

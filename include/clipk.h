@@ -835,6 +835,30 @@ int clipk_sim_lse_bias(const float* X, int Mx, const float* Y, int Ny, int P, co
                        const float* prev /*[Mx] or NULL*/, int average, float* out /*[Mx]*/,
                        float* err /* device scalar, accumulated, or NULL */, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* clipk_sim_lse_bias_x3 - the half-iteration of clipk_sim_lse_bias with the product on the bf16 matrix pipe (bf16x3):
+ *     nv_i = logw[i] - LSE_j(scale[0] A_ij + bias[j]),   A_ij = sum_p hi(x)hi(y) + hi(x)lo(y) + lo(x)hi(y)   (f32 sums)
+ *   Xhi / Xlo [Mx, PP] and Yhi / Ylo [Ny, PP]: the planes clipk_split_bf16 writes (row pitch PP = P rounded up to 32, pads
+ *   zero).  Both clouds are queries in one half-iteration and keys in the other: split each once per solve.  bias, logw,
+ *   prev, average, out and err (accumulated, fixed-order reduce) as in clipk_sim_lse_bias; prev == out is allowed; scale
+ *   is a device scalar; keys beyond Ny are masked with -inf.
+ *   Error bound (the "Certificate" of the prefiltered top-k above, same eps_rel and eps_abs): for every pair
+ *     |scale A_ij - scale <x_i, y_j>| <= eta_i = |scale| |x_i| max_j|y_j| eps_rel + eps_abs,
+ *   eps_rel = the bf16x3 value (retrieval.prefilter_eps_rel(P, "bf16x3")).  LSE is non-expansive in the sup norm, so
+ *   |nv_x3 - nv_exact| <= eta = max_i eta_i.  A_ij with x as the query need not equal A_ji with y as the query bit for
+ *   bit (the MFMA's summation order is not documented): only the bound is promised, not symmetry.
+ *   Kernel: the 128-query x 64-key tile of the prefilter's candidate pass (three v_mfma_f32_32x32x16_bf16 per fragment
+ *   pair), the running (max, sum) of clipk_sim_lse_bias as its epilogue, the same finalize and error kernels.
+ *   clipk_sim_lse_bias_x3_plan reports the grid: nqb 128-query blocks x ksplit key splits.
+ *   Supported: Mx, Ny >= 1, P % 4 == 0, P <= 768, planes / workspace 16-byte aligned; anything else returns
+ *   CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED and the workspace helper returns 0.  Never allocates, never synchronises,
+ *   capturable, no float atomics: two runs give identical bits.  Non-finite inputs are as undefined as in the f32 entry. */
+int clipk_sim_lse_bias_x3_plan(int Mx, int Ny, int* nqb, int* ksplit);
+size_t clipk_sim_lse_bias_x3_workspace(int Mx, int Ny, int P);
+int clipk_sim_lse_bias_x3(const void* Xhi, const void* Xlo, int Mx, const void* Yhi, const void* Ylo, int Ny, int P,
+                          const float* scale /* device scalar */, const float* bias /*[Ny] or NULL*/,
+                          const float* logw /*[Mx] or NULL*/, const float* prev /*[Mx] or NULL*/, int average,
+                          float* out /*[Mx]*/, float* err /* device scalar, accumulated, or NULL */, void* workspace,
+                          size_t workspace_bytes, void* stream);
 size_t clipk_sinkhorn_apply_workspace(int Mx, int Ny, int P);
 int clipk_sinkhorn_apply(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale /* device scalar */,
                          const float* u /*[Mx]*/, const float* v /*[Ny]*/, const float* nx /*[Mx]*/,
