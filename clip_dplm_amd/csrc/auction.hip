@@ -3,9 +3,10 @@
 //
 // A bidding round needs, for every still-unassigned row i, the best and the second-best value of
 //   z_ij = 2 <x_i, y_j> - |y_j|^2 - price_j = 2 <x_i, y_j> + bias_j
-// over all keys j: the tile walk of sinkhorn_sample.hip's sinkhorn_sample_kernel (copied here without the Philox part:
-// 64 queries per workgroup, 64-key tiles on sim_tile.h's exact-f32 block, keys on the MFMA rows, queries on the lanes)
-// with a running (best, arg best, runner-up) per lane, over a LIST of query rows whose length is read from device memory.
+// over all keys j: the tile walk of sinkhorn_sample.hip's sinkhorn_sample_kernel without the Philox part (cloud_tile.h's
+// KeyWalk: 64 queries per workgroup, 64-key tiles on sim_tile.h's exact-f32 block, keys on the MFMA rows, queries on the
+// lanes) with a running (best, arg best, runner-up) per lane, over a LIST of query rows whose length is read from device
+// memory.
 // Merge rule of (z1, k1, z2) triples, the same at every level (within a lane, lane halves, the two key-waves, key splits
 // in the finalize launch): the higher z1 wins, equal z1 goes to the lower key, the runner-up is the maximum of what is
 // left (the loser's z1, the winner's z2).  A triple stands for (the first element under the order (z down, key up), the
@@ -30,7 +31,7 @@
 //                            on the order of arrival
 // and a call ends with one more auction_resolve_compact, which leaves the state consistent and the count current.
 #include "common.h"
-#include "sim_tile.h"
+#include "cloud_tile.h"
 #include <math.h>
 
 #ifndef TOP2_TPS
@@ -39,7 +40,6 @@
 
 namespace {
 
-constexpr int TQ = 64, TK = 64;                   // queries per workgroup, keys per tile
 constexpr int TOP2_PMAX = 768;                    // contraction limit (that of the LSE pass)
 constexpr int NO_KEY = 0x7fffffff;                // loses every tie: a lane that saw no key below Ny
 constexpr int AUCTION_NMAX = 65536;               // one workgroup compacts the rows
@@ -80,51 +80,26 @@ __global__ __launch_bounds__(256, 2) void top2_kernel(const T2P p) {
   const int q0 = blockIdx.x * TQ;
   const int na = active_count(p.n_active, p.Mr);
   if (q0 >= na) return;                                                   // the whole workgroup, before any barrier
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid >> 1, wn = wid & 1;                                  // key half, query half
-  const int li = lane & 31, h = lane >> 5;
-  const int ks = blockIdx.y;
-  const int P = p.P, Ny = p.Ny;
   const float scale = p.scale[0];
-  const int qg = q0 + wn * 32 + li;                                       // this lane's list position
+  const KeyWalk<BKL> w(p.X, p.Mx, p.rows, na, p.Y, p.Ny, p.P, p.tiles_per_split, p.ntiles, smem);
+  const int wm = w.wm, wn = w.wn, li = w.li, h = w.h, ks = w.ks, qg = w.qg;   // qg: this lane's list position
   float z1 = -INFINITY, z2 = -INFINITY;
   int k1 = NO_KEY;
-  const float* xrows[BKL / 16];
-#pragma unroll
-  for (int i = 0; i < BKL / 16; ++i) {
-    int q = q0 + (tid + i * 256) / (BKL / 4); q = q < na ? q : na - 1;
-    int row = p.rows ? p.rows[q] : q;
-    row = row < 0 ? 0 : (row < p.Mx ? row : p.Mx - 1);                    // a bad list entry reads a valid row
-    xrows[i] = p.X + (long)row * P;
-  }
-  const int t_beg = ks * p.tiles_per_split;
-  int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
 
-  for (int kt = t_beg; kt < t_end; ++kt) {
+  for (int kt = w.t_beg; kt < w.t_end; ++kt) {
     const int j0 = kt * TK;
-    const float* yrows[BKL / 16];
-#pragma unroll
-    for (int i = 0; i < BKL / 16; ++i) {
-      int j = j0 + (tid + i * 256) / (BKL / 4); j = j < Ny ? j : Ny - 1;  // clamped: masked in the epilogue
-      yrows[i] = p.Y + (long)j * P;
-    }
     float bk[16];                                                         // bias of this lane's 16 key rows
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = j0 + wm * 32 + keyrow32(r, h);
-      bk[r] = (p.bias && key < Ny) ? p.bias[key] : 0.f;
-    }
+    for (int r = 0; r < 16; ++r) bk[r] = w.key_bias(p.bias, j0, r);
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    s_tile<BKL>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
+    w.product(j0, acc);
     // keys in rising order within the lane (tiles rise, keyrow32 rises with r): `>` keeps the lower key of a tie, and
     // the tied value becomes the runner-up
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int key = j0 + wm * 32 + keyrow32(r, h);
+      const int key = w.key(j0, r);
       const float z = scale * acc[r] + bk[r];
-      if (key < Ny) {
+      if (key < p.Ny) {
         if (z > z1) { z2 = z1; z1 = z; k1 = key; }
         else z2 = fmaxf(z2, z);
       }

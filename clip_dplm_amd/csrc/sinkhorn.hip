@@ -2,27 +2,25 @@
 // (include/clipk.h: clipk_sim_lse_bias / clipk_sinkhorn_apply have the formulae).
 //
 // A Sinkhorn half-iteration is a row log-sum-exp of S_ij + bias_j with S = scale <x_i, y_j>, and everything one wants
-// from the plan P_ij = exp(S_ij + u_i + v_j) is a P-weighted sum over the keys.  Both are the tile walks of
-// simce_tiled.hip on sim_tile.h's exact-f32 64 x 64 block (keys on the MFMA rows, queries on the lanes), copied here
-// with the key-side bias and the potentials in place of the cross-entropy's labels:
+// from the plan P_ij = exp(S_ij + u_i + v_j) is a P-weighted sum over the keys.  Both walk the key tiles as
+// cloud_tile.h's KeyWalk does on sim_tile.h's exact-f32 64 x 64 block (keys on the MFMA rows, queries on the lanes), with
+// the key-side bias and the potentials where simce_tiled.hip has the cross-entropy's labels:
 //   * sinkhorn_lse_kernel: 64 queries per workgroup, 64-key tiles, a running (max, sum) per lane, key-range splits as
 //     (m, l) partials; sinkhorn_lse_finalize merges them in a fixed order, forms logw - LSE, applies the averaged update
 //     of the symmetric problem and leaves each row's marginal-error term for sinkhorn_err_reduce (one workgroup, fixed
 //     order: the error scalar is as deterministic as the potentials);
 //   * sinkhorn_lse_x3_kernel: the same pass with the product as a bf16x3 split on v_mfma_f32_32x32x16_bf16 (128-query
 //     blocks, its own plan), feeding the same finalize and error kernels (clipk_sim_lse_bias_x3);
-//   * sinkhorn_apply_kernel: S tile -> P tile into LDS -> second MFMA product with the staged key rows (bary^T = Y^T P^T),
-//     mass and cost from the same P values; key-split slabs are summed in split order by sinkhorn_apply_finalize.
+//   * sinkhorn_apply_kernel: S tile -> P tile into LDS -> cloud_keysum.h's weighted key sum (bary^T = Y^T P^T), mass and
+//     cost from the same P values; key-split slabs are summed in split order by split_sum_finalize.
 // No float atomics, no cooperative launch: results depend on the shapes alone.
 #include "common.h"
-#include "sim_tile.h"
+#include "cloud_tile.h"
 #include <math.h>
 
 namespace {
 
-constexpr int TQ = 64, TK = 64;                   // queries per workgroup, keys per tile
 constexpr int LSE_PMAX = 768;                     // contraction limit of the LSE pass
-constexpr int APMAX = 512;                        // contraction / output width limit of the apply pass
 
 struct SLP {
   const float* X; int Mx;
@@ -38,46 +36,22 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_lse_kernel(const SLP p) {
   constexpr int BKL = 32;                                                 // 16 MFMAs per wave between barriers
   __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (BKL + 4)];   // 2 buffers x (keys | queries)
   __shared__ float mrg[2][TQ];                                            // key-wave 1's [m | l][query]
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid >> 1, wn = wid & 1;                                  // key half, query half
-  const int li = lane & 31, h = lane >> 5;
-  const int q0 = blockIdx.x * TQ, ks = blockIdx.y;
-  const int P = p.P, Ny = p.Ny;
   const float scale = p.scale[0];
-  const int qg = q0 + wn * 32 + li;                                       // this lane's query
+  const KeyWalk<BKL> w(p.X, p.Mx, nullptr, p.Mx, p.Y, p.Ny, p.P, p.tiles_per_split, p.ntiles, smem);
+  const int wm = w.wm, wn = w.wn, li = w.li, h = w.h, ks = w.ks, qg = w.qg;
   float m_run = -INFINITY, l_run = 0.f;
-  const float* xrows[BKL / 16];
-#pragma unroll
-  for (int i = 0; i < BKL / 16; ++i) {
-    int q = q0 + (tid + i * 256) / (BKL / 4); q = q < p.Mx ? q : p.Mx - 1;
-    xrows[i] = p.X + (long)q * P;
-  }
-  const int t_beg = ks * p.tiles_per_split;
-  int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
 
-  for (int kt = t_beg; kt < t_end; ++kt) {
+  for (int kt = w.t_beg; kt < w.t_end; ++kt) {
     const int j0 = kt * TK;
-    const float* yrows[BKL / 16];
-#pragma unroll
-    for (int i = 0; i < BKL / 16; ++i) {
-      int j = j0 + (tid + i * 256) / (BKL / 4); j = j < Ny ? j : Ny - 1;  // clamped: masked in the epilogue
-      yrows[i] = p.Y + (long)j * P;
-    }
     float bk[16];                                                         // bias of this lane's 16 key rows
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = j0 + wm * 32 + keyrow32(r, h);
-      bk[r] = (p.bias && key < Ny) ? p.bias[key] : 0.f;
-    }
+    for (int r = 0; r < 16; ++r) bk[r] = w.key_bias(p.bias, j0, r);
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    s_tile<BKL>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
+    w.product(j0, acc);
     float sv[16], tmax = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int key = j0 + wm * 32 + keyrow32(r, h);
-      sv[r] = key < Ny ? scale * acc[r] + bk[r] : -INFINITY;
+      sv[r] = w.key(j0, r) < p.Ny ? scale * acc[r] + bk[r] : -INFINITY;
       tmax = fmaxf(tmax, sv[r]);
     }
     if (tmax > -INFINITY) {
@@ -122,6 +96,7 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_lse_kernel(const SLP p) {
 // The exponentials are __expf (v_exp_f32 of the argument times log2 e): the argument is <= 0, its rounding moves a term
 // by |arg| 2^-24 relative, and 32 of them per tile and lane sit on the VALU, which does not overlap this SIMD's MFMAs.
 constexpr int XQ = 128, XK = 64;                  // queries per workgroup, keys per tile
+static_assert(XK == TK, "key_split_plan counts tiles of TK keys");
 constexpr int XBK = 32, XLD = XBK + 8;            // K-step in bf16 elements (two MFMA k-steps), LDS row pitch (80 B)
 
 struct SLPX {
@@ -300,12 +275,21 @@ __global__ __launch_bounds__(1024) void sinkhorn_err_reduce(const float* err_row
   if (threadIdx.x == 0) err[0] += red[0];
 }
 
+}  // namespace
+
 // ------------------------------------------------------------------------------------------------ apply pass
+// (cloud_keysum.h here and not at the top: kernels lie in the code object in the order of their definitions, and its
+// split_sum_finalize stays where sinkhorn_apply_finalize was, behind the LSE kernels)
+#include "cloud_keysum.h"
+
+namespace {
+
+constexpr int APMAX = KEYSUM_PMAX;                // contraction / output width limit of the apply pass
+
 // Same 64 x 64 tiles as simce_grad_tiled_kernel: (1) S^T tile by the K-loop over P; (2) the plan's entries in the
 // accumulator layout (keys on rows, queries on lanes), mass and cost summed per lane, the tile written once to a 16 KiB
-// LDS tile; (3) bary^T[p, q] += Y^T[p, key] P^T[key, q] as a second MFMA product whose M dimension is p: wave w owns p in
-// [w P/4, (w+1) P/4) for all 64 queries, the key tile comes back in four 16-key blocks staged in LDS.  70 KiB of LDS:
-// two workgroups per CU.  Without bary the kernel stops after (2).
+// LDS tile; (3) bary^T[p, q] += Y^T[p, key] P^T[key, q] by cloud_keysum.h's weighted key sum.  70 KiB of LDS: two
+// workgroups per CU.  Without bary the kernel stops after (2).
 struct SAP {
   const float* X; int Mx;
   const float* Y; int Ny;
@@ -319,20 +303,21 @@ struct SAP {
   int tiles_per_split, ntiles;
 };
 
-constexpr int YH_LD = APMAX + 4;                   // floats per staged key row
-constexpr int KSB = 16;                            // keys per staged block of the second product
-constexpr int BKG = 16;                            // K-step of the S tile (LDS budget: 2 workgroups per CU)
-constexpr int APPLY_LDS_ROWS = 2 * 2 * 64 * (BKG + 4) + 2 * TQ;          // K-loop buffers + mass / cost merge slots
-constexpr int APPLY_LDS_FLOATS = APPLY_LDS_ROWS + TK * TQ + KSB * YH_LD;   // + plan tile + staged key block (BARY)
+constexpr int APPLY_LDS_ROWS = KLOOP_LDS_FLOATS + 2 * TQ;                 // K-loop buffers + mass / cost merge slots
+constexpr int APPLY_LDS_FLOATS = APPLY_LDS_ROWS + KEYSUM_LDS_FLOATS;      // + plan tile + staged key block (BARY)
 
 // BARY = false: mass and cost only - no accumulators of the second product, 21 KiB of LDS
 template <bool BARY>
 __global__ __launch_bounds__(256, 2) void sinkhorn_apply_kernel(const SAP p) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* smem = reinterpret_cast<float*>(smem_raw);                      // K-loop buffers
-  float* mcl = smem + 2 * 2 * 64 * (BKG + 4);                             // [mass | cost][64 queries] of key-wave 1
+  float* mcl = smem + KLOOP_LDS_FLOATS;                                   // [mass | cost][64 queries] of key-wave 1
   float* gl = mcl + 2 * TQ;                                               // BARY: plan tile [64 keys][64 queries]
   float* yh = gl + TK * TQ;                                               // BARY: key block [16][YH_LD] / output transposes
+  // This kernel keeps its own walk (KeyWalk<BKG>'s statements): on KeyWalk the <false> instantiation came out 4
+  // instructions shorter with its K-loop 4 bytes further on, and the mass / cost pass measured 0.7 - 0.8 % slower at
+  // 8192 x 8192 x 512 in each of three comparisons (profiles/cloud_tile/README.md).  As written here it is the
+  // instruction stream it was before the fold.
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   const int li = lane & 31, h = lane >> 5;
@@ -342,18 +327,10 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_apply_kernel(const SAP p) {
   const int qg = q0 + wn * 32 + li;
   const int qc = qg < p.Mx ? qg : p.Mx - 1;
   const float u_i = p.u[qc];
-  constexpr bool want_bary = BARY;
   const bool want_cost = p.cost_part != nullptr;
   const float nx_i = want_cost ? p.nx[qc] : 0.f;
-  const int npt = (P + 127) / 128;                                        // 32-row p tiles per wave: P/4 / 32
-  const int pw = npt * 32;                                                // p rows per wave
-  f32x16 dx[BARY ? 4 : 1][2];
-#pragma unroll
-  for (int a = 0; a < (BARY ? 4 : 1); ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dx[a][b][r] = 0.f;
+  f32x16 dx[4][2];                                                        // (BARY only)
+  if constexpr (BARY) key_sum_zero(dx);
   float mass = 0.f, cst = 0.f;
 
   const float* xrows[1];
@@ -385,69 +362,11 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_apply_kernel(const SAP p) {
       mass += pv;
       if constexpr (BARY) gl[kl * TQ + wn * 32 + li] = pv;
     }
-    if constexpr (BARY) {
-    // ---- bary^T += Y^T P^T, the key tile in blocks of KSB keys
-    for (int kb = 0; kb < TK / KSB; ++kb) {
-      __syncthreads();                                                    // gl complete (kb = 0) / yh free again
-      {
-        // stage Y[16 keys][P]: thread -> (key = tid / 16, 16-B chunks c = tid % 16 + 16 i), loads first, then stores
-        const float* yr = key_row(j0 + kb * KSB + (tid >> 4));
-        float* dst = yh + (tid >> 4) * YH_LD;
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {                                     // two groups of four: 16 staging registers
-          f32x4 tmp[APMAX / 128];
-#pragma unroll
-          for (int i = 0; i < APMAX / 128; ++i) {
-            const int c = (tid & 15) + 16 * (g * (APMAX / 128) + i);
-            tmp[i] = (c * 4 < P) ? ld4(yr, c * 4, P) : f32x4{0.f, 0.f, 0.f, 0.f};
-          }
-#pragma unroll
-          for (int i = 0; i < APMAX / 128; ++i) {
-            const int c = (tid & 15) + 16 * (g * (APMAX / 128) + i);
-            if (c * 4 < P) *reinterpret_cast<f32x4*>(dst + c * 4) = tmp[i];
-          }
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < KSB / 2; ++u) {                                 // MFMA u contracts keys 2u (h = 0) and 2u + 1
-        const int kl = 2 * u + h;
-        const float b0 = gl[(kb * KSB + kl) * TQ + li], b1 = gl[(kb * KSB + kl) * TQ + 32 + li];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-          if (a < npt) {
-            const int prow = wid * pw + a * 32 + li;
-            const float av = prow < P ? yh[kl * YH_LD + prow] : 0.f;
-            dx[a][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, dx[a][0], 0, 0, 0);
-            dx[a][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b1, dx[a][1], 0, 0, 0);
-          }
-      }
-    }
-    }
+    if constexpr (BARY) key_sum_tile(dx, p.Y, Ny, P, j0, gl, yh, tid, wid, li, h);   // bary^T += Y^T P^T
   }
 
   __syncthreads();
-  if constexpr (BARY) {
-    // ---- bary^T accumulators -> [q][p] rows through LDS (one 32 x 32 block per wave at a time)
-    float* tb = yh + wid * (32 * 33);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {                           // (fully unrolled: the accumulators are register arrays)
-      if (a < npt) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) tb[li * 33 + keyrow32(r, h)] = dx[a][b][r];  // [query][p]
-          // wave-private region: the wave's own writes are visible to its reads in program order
-#pragma unroll
-          for (int it = 0; it < 16; ++it) {
-            const int ql = it * 2 + h;                                    // 2 query rows per pass, 32 consecutive p each
-            const int q = q0 + b * 32 + ql, pp = wid * pw + a * 32 + li;
-            if (q < p.Mx && pp < P) p.slab[((long)ks * p.Mx + q) * P + pp] = tb[ql * 33 + li];
-          }
-        }
-      }
-    }
-  }
+  if constexpr (BARY) key_sum_store(dx, yh, p.slab, p.Mx, P, q0, ks, wid, li, h);
   // ---- mass / cost partials: lane halves, then the two key-waves
   mass += __shfl_xor(mass, 32, 64);
   cst += __shfl_xor(cst, 32, 64);
@@ -459,72 +378,38 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_apply_kernel(const SAP p) {
   }
 }
 
-// slabs and row partials summed in split order (a fixed order: deterministic)
-__global__ __launch_bounds__(256) void sinkhorn_apply_finalize(const float* slab, const float* mass_part,
-                                                               const float* cost_part, int ksplit, int Mx, int P,
-                                                               float* bary, float* mass, float* cost) {
-  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-  if (bary) {
-    const long n4 = (long)Mx * P / 4, slab_n = (long)Mx * P;
-    for (long i = tid; i < n4; i += nth) {
-      f32x4 a = reinterpret_cast<const f32x4*>(slab)[i];
-      for (int s = 1; s < ksplit; ++s) a += reinterpret_cast<const f32x4*>(slab + (long)s * slab_n)[i];
-      reinterpret_cast<f32x4*>(bary)[i] = a;
-    }
-  }
-  for (long i = tid; i < Mx; i += nth) {
-    if (mass) {
-      float a = 0.f;
-      for (int s = 0; s < ksplit; ++s) a += mass_part[(long)s * Mx + i];
-      mass[i] = a;
-    }
-    if (cost) {
-      float a = 0.f;
-      for (int s = 0; s < ksplit; ++s) a += cost_part[(long)s * Mx + i];
-      cost[i] = a;
-    }
-  }
-}
-
 bool shape_ok(int Mx, int Ny, int P, int pmax) { return Mx > 0 && Ny > 0 && P > 0 && !(P & 3) && P <= pmax; }
 
-// one workgroup per (64-query block, key split); splits so that the grid holds >= 2 workgroups per CU
-void plan(int Mx, int Ny, int* nqb, int* ksplit, int* tps, int* ntiles) {
-  *nqb = (Mx + TQ - 1) / TQ;
-  *ntiles = (Ny + TK - 1) / TK;
-  int ks = (512 + *nqb - 1) / *nqb;
-  if (ks > *ntiles) ks = *ntiles;
-  if (ks < 1) ks = 1;
-  *tps = (*ntiles + ks - 1) / ks;
-  *ksplit = (*ntiles + *tps - 1) / *tps;
+size_t lse_workspace_bytes(const KeySplitPlan& k, int Mx) {
+  return ((size_t)k.ksplit * Mx * 2 + (size_t)Mx) * sizeof(float);        // (m, l) partials, then the error terms
 }
 
-// the plan of plan(), for the 128-query blocks of the bf16x3 pass
-void plan_x3(int Mx, int Ny, int* nqb, int* ksplit, int* tps, int* ntiles) {
-  *nqb = (Mx + XQ - 1) / XQ;
-  *ntiles = (Ny + XK - 1) / XK;
-  int ks = (512 + *nqb - 1) / *nqb;
-  if (ks > 65535) ks = 65535;
-  if (ks > *ntiles) ks = *ntiles;
-  if (ks < 1) ks = 1;
-  *tps = (*ntiles + ks - 1) / ks;
-  *ksplit = (*ntiles + *tps - 1) / *tps;
+// what follows either LSE pass: the (m, l) partials at the head of the workspace -> out, the rows' error terms behind
+// them -> err
+int lse_finish(void* workspace, const KeySplitPlan& k, int Mx, const float* logw, const float* prev, int average, float* out,
+               float* err, hipStream_t stream) {
+  const float* part_ml = (const float*)workspace;
+  float* err_rows = (float*)workspace + (size_t)k.ksplit * Mx * 2;
+  hipLaunchKernelGGL(sinkhorn_lse_finalize, dim3((Mx + 3) / 4), dim3(256), 0, stream, part_ml, k.ksplit, Mx, logw, prev,
+                     average, out, err ? err_rows : (float*)nullptr);
+  int rc = clipk_check_launch();
+  if (rc || !err) return rc;
+  hipLaunchKernelGGL(sinkhorn_err_reduce, dim3(1), dim3(1024), 0, stream, (const float*)err_rows, Mx, err);
+  return clipk_check_launch();
 }
 
 }  // namespace
 
 extern "C" int clipk_sim_lse_bias_x3_plan(int Mx, int Ny, int* nqb, int* ksplit) {
   if (Mx <= 0 || Ny <= 0 || !nqb || !ksplit) return CLIPK_ERR_BAD_ARG;
-  int tps, nt;
-  plan_x3(Mx, Ny, nqb, ksplit, &tps, &nt);
+  const KeySplitPlan k = key_split_plan(Mx, Ny, XQ);
+  *nqb = k.nqb; *ksplit = k.ksplit;
   return CLIPK_OK;
 }
 
 extern "C" size_t clipk_sim_lse_bias_x3_workspace(int Mx, int Ny, int P) {
   if (!shape_ok(Mx, Ny, P, LSE_PMAX)) return 0;
-  int nqb, ks, tps, nt;
-  plan_x3(Mx, Ny, &nqb, &ks, &tps, &nt);
-  return ((size_t)ks * Mx * 2 + (size_t)Mx) * sizeof(float);              // (m, l) partials, then the error terms
+  return lse_workspace_bytes(key_split_plan(Mx, Ny, XQ), Mx);
 }
 
 extern "C" int clipk_sim_lse_bias_x3(const void* Xhi, const void* Xlo, int Mx, const void* Yhi, const void* Ylo, int Ny,
@@ -538,36 +423,28 @@ extern "C" int clipk_sim_lse_bias_x3(const void* Xhi, const void* Xlo, int Mx, c
   if (!aligned16(Xhi) || !aligned16(Xlo) || !aligned16(Yhi) || !aligned16(Ylo) || !aligned16(workspace))
     return CLIPK_ERR_BAD_ARG;
   if (workspace_bytes < clipk_sim_lse_bias_x3_workspace(Mx, Ny, P)) return CLIPK_ERR_BAD_ARG;
+  const KeySplitPlan k = key_split_plan(Mx, Ny, XQ);
   SLPX p{};
   p.xh = static_cast<const unsigned short*>(Xhi); p.xl = static_cast<const unsigned short*>(Xlo); p.Mx = Mx;
   p.yh = static_cast<const unsigned short*>(Yhi); p.yl = static_cast<const unsigned short*>(Ylo); p.Ny = Ny;
   p.PP = (P + 31) & ~31; p.scale = scale; p.bias = bias; p.part_ml = (float*)workspace;
-  int nqb, ks;
-  plan_x3(Mx, Ny, &nqb, &ks, &p.tiles_per_split, &p.ntiles);
-  float* err_rows = p.part_ml + (size_t)ks * Mx * 2;
-  hipLaunchKernelGGL(sinkhorn_lse_x3_kernel, dim3(nqb, ks), dim3(256), 0, (hipStream_t)stream, p);
-  int rc = clipk_check_launch();
+  p.tiles_per_split = k.tiles_per_split; p.ntiles = k.ntiles;
+  hipLaunchKernelGGL(sinkhorn_lse_x3_kernel, dim3(k.nqb, k.ksplit), dim3(256), 0, (hipStream_t)stream, p);
+  const int rc = clipk_check_launch();
   if (rc) return rc;
-  hipLaunchKernelGGL(sinkhorn_lse_finalize, dim3((Mx + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)p.part_ml, ks, Mx, logw, prev, average, out, err ? err_rows : (float*)nullptr);
-  rc = clipk_check_launch();
-  if (rc || !err) return rc;
-  hipLaunchKernelGGL(sinkhorn_err_reduce, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)err_rows, Mx, err);
-  return clipk_check_launch();
+  return lse_finish(workspace, k, Mx, logw, prev, average, out, err, (hipStream_t)stream);
 }
 
 extern "C" int clipk_sim_lse_bias_plan(int Mx, int Ny, int* nqb, int* ksplit) {
   if (Mx <= 0 || Ny <= 0 || !nqb || !ksplit) return CLIPK_ERR_BAD_ARG;
-  int tps, nt;
-  plan(Mx, Ny, nqb, ksplit, &tps, &nt);
+  const KeySplitPlan k = key_split_plan(Mx, Ny, TQ);
+  *nqb = k.nqb; *ksplit = k.ksplit;
   return CLIPK_OK;
 }
 
 extern "C" size_t clipk_sim_lse_bias_workspace(int Mx, int Ny, int P) {
   if (!shape_ok(Mx, Ny, P, LSE_PMAX)) return 0;
-  int nqb, ks, tps, nt;
-  plan(Mx, Ny, &nqb, &ks, &tps, &nt);
-  return ((size_t)ks * Mx * 2 + (size_t)Mx) * sizeof(float);              // (m, l) partials, then the error terms
+  return lse_workspace_bytes(key_split_plan(Mx, Ny, TQ), Mx);
 }
 
 extern "C" int clipk_sim_lse_bias(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale,
@@ -579,27 +456,20 @@ extern "C" int clipk_sim_lse_bias(const float* X, int Mx, const float* Y, int Ny
   if ((average || err) && !prev) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
   if (workspace_bytes < clipk_sim_lse_bias_workspace(Mx, Ny, P)) return CLIPK_ERR_BAD_ARG;
+  const KeySplitPlan k = key_split_plan(Mx, Ny, TQ);
   SLP p{};
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale; p.bias = bias; p.part_ml = (float*)workspace;
-  int nqb, ks;
-  plan(Mx, Ny, &nqb, &ks, &p.tiles_per_split, &p.ntiles);
-  float* err_rows = p.part_ml + (size_t)ks * Mx * 2;
-  hipLaunchKernelGGL(sinkhorn_lse_kernel, dim3(nqb, ks), dim3(256), 0, (hipStream_t)stream, p);
-  int rc = clipk_check_launch();
+  p.tiles_per_split = k.tiles_per_split; p.ntiles = k.ntiles;
+  hipLaunchKernelGGL(sinkhorn_lse_kernel, dim3(k.nqb, k.ksplit), dim3(256), 0, (hipStream_t)stream, p);
+  const int rc = clipk_check_launch();
   if (rc) return rc;
-  hipLaunchKernelGGL(sinkhorn_lse_finalize, dim3((Mx + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)p.part_ml, ks, Mx, logw, prev, average, out, err ? err_rows : (float*)nullptr);
-  rc = clipk_check_launch();
-  if (rc || !err) return rc;
-  hipLaunchKernelGGL(sinkhorn_err_reduce, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)err_rows, Mx, err);
-  return clipk_check_launch();
+  return lse_finish(workspace, k, Mx, logw, prev, average, out, err, (hipStream_t)stream);
 }
 
 extern "C" size_t clipk_sinkhorn_apply_workspace(int Mx, int Ny, int P) {
   if (!shape_ok(Mx, Ny, P, APMAX)) return 0;
-  int nqb, ks, tps, nt;
-  plan(Mx, Ny, &nqb, &ks, &tps, &nt);
-  return (size_t)ks * Mx * ((size_t)P + 2) * sizeof(float);               // bary slabs, mass and cost partials
+  const size_t ks = key_split_plan(Mx, Ny, TQ).ksplit;
+  return ks * Mx * ((size_t)P + 2) * sizeof(float);                       // bary slabs, mass and cost partials
 }
 
 extern "C" int clipk_sinkhorn_apply(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale,
@@ -611,10 +481,11 @@ extern "C" int clipk_sinkhorn_apply(const float* X, int Mx, const float* Y, int 
   if (cost && (!nx || !ny)) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || !aligned16(workspace) || (bary && !aligned16(bary))) return CLIPK_ERR_BAD_ARG;
   if (workspace_bytes < clipk_sinkhorn_apply_workspace(Mx, Ny, P)) return CLIPK_ERR_BAD_ARG;
+  const KeySplitPlan k = key_split_plan(Mx, Ny, TQ);
+  const int ks = k.ksplit;
   SAP p{};
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale; p.u = u; p.v = v; p.nx = nx; p.ny = ny;
-  int nqb, ks;
-  plan(Mx, Ny, &nqb, &ks, &p.tiles_per_split, &p.ntiles);
+  p.tiles_per_split = k.tiles_per_split; p.ntiles = k.ntiles;
   float* ws = (float*)workspace;
   const size_t slab_n = (size_t)ks * Mx * P;                              // (a multiple of 4 floats: the partials stay aligned)
   p.slab = bary ? ws : nullptr;
@@ -627,16 +498,13 @@ extern "C" int clipk_sinkhorn_apply(const float* X, int Mx, const float* Y, int 
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sinkhorn_apply_kernel<true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
-    hipLaunchKernelGGL(sinkhorn_apply_kernel<true>, dim3(nqb, ks), dim3(256), lds, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(sinkhorn_apply_kernel<true>, dim3(k.nqb, ks), dim3(256), lds, (hipStream_t)stream, p);
   } else {
-    hipLaunchKernelGGL(sinkhorn_apply_kernel<false>, dim3(nqb, ks), dim3(256), (size_t)APPLY_LDS_ROWS * sizeof(float),
+    hipLaunchKernelGGL(sinkhorn_apply_kernel<false>, dim3(k.nqb, ks), dim3(256), (size_t)APPLY_LDS_ROWS * sizeof(float),
                        (hipStream_t)stream, p);
   }
-  int rc = clipk_check_launch();
+  const int rc = clipk_check_launch();
   if (rc) return rc;
-  long blocks = bary ? ((long)Mx * P / 4 + 255) / 256 : (Mx + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(sinkhorn_apply_finalize, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)p.slab,
-                     (const float*)p.mass_part, (const float*)p.cost_part, ks, Mx, P, bary, mass, cost);
+  launch_split_sum_finalize(p.slab, p.mass_part, p.cost_part, ks, Mx, P, bary, mass, cost, (hipStream_t)stream);
   return clipk_check_launch();
 }

@@ -3,8 +3,8 @@
 //
 // The conditional of the plan P_ij = exp(S_ij + u_i + v_j) along a row is softmax_j(S_ij + v_j): u_i is constant along
 // the row and drops out.  Adding Gumbel noise G_ij to every logit and taking the arg max draws from that softmax, so a
-// draw is the tile walk of sinkhorn.hip's sinkhorn_lse_kernel (copied here: 64 queries per workgroup, 64-key tiles on
-// sim_tile.h's exact-f32 block, keys on the MFMA rows, queries on the lanes, the key-range split plan of
+// draw is the tile walk of sinkhorn.hip's sinkhorn_lse_kernel (cloud_tile.h's KeyWalk: 64 queries per workgroup, 64-key
+// tiles on sim_tile.h's exact-f32 block, keys on the MFMA rows, queries on the lanes, the key-range split plan of
 // clipk_sim_lse_bias_plan) with a running (best value, best key) per lane in place of (max, sum):
 //   z_ij = scale <x_i, y_j> + bias_j + G(seed, stream_i, j),   stream_i = stream_offset + i   (64-bit)
 // The noise is a pure function of (seed, stream, key): Philox4x32-10 keyed by the seed, counter (j >> 2, stream lo,
@@ -14,12 +14,11 @@
 // higher z wins, equal z goes to the lower key.  The rule is associative and commutative, so the winner depends on
 // (inputs, seed, stream) and never on the grid.  No float atomics, no cooperative launch.
 #include "common.h"
-#include "sim_tile.h"
+#include "cloud_tile.h"
 #include <math.h>
 
 namespace {
 
-constexpr int TQ = 64, TK = 64;                   // queries per workgroup, keys per tile
 constexpr int SAMPLE_PMAX = 768;                  // contraction limit (that of the LSE pass)
 constexpr int NO_KEY = 0x7fffffff;                // loses every tie: a lane that saw no key below Ny
 
@@ -62,46 +61,25 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_sample_kernel(const SSP p) {
   __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (BKL + 4)];   // 2 buffers x (keys | queries)
   __shared__ float mrg_z[TQ];                                             // key-wave 1's best value / key per query
   __shared__ int mrg_k[TQ];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid >> 1, wn = wid & 1;                                  // key half, query half
-  const int li = lane & 31, h = lane >> 5;
-  const int q0 = blockIdx.x * TQ, ks = blockIdx.y;
-  const int P = p.P, Ny = p.Ny;
   const float scale = p.scale[0];
-  const int qg = q0 + wn * 32 + li;                                       // this lane's query
   const unsigned long long seed = (unsigned long long)p.seed_offset[0];
-  const unsigned long long sid = (unsigned long long)p.seed_offset[1] + (unsigned long long)qg;
+  const unsigned long long stream0 = (unsigned long long)p.seed_offset[1];
+  const KeyWalk<BKL> w(p.X, p.Mx, nullptr, p.Mx, p.Y, p.Ny, p.P, p.tiles_per_split, p.ntiles, smem);
+  const int wm = w.wm, wn = w.wn, li = w.li, h = w.h, ks = w.ks, qg = w.qg;
+  const int Ny = p.Ny;
+  const unsigned long long sid = stream0 + (unsigned long long)qg;
   const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
   const unsigned s_lo = (unsigned)sid, s_hi = (unsigned)(sid >> 32);
   float z_run = -INFINITY;
   int k_run = NO_KEY;
-  const float* xrows[BKL / 16];
-#pragma unroll
-  for (int i = 0; i < BKL / 16; ++i) {
-    int q = q0 + (tid + i * 256) / (BKL / 4); q = q < p.Mx ? q : p.Mx - 1;
-    xrows[i] = p.X + (long)q * P;
-  }
-  const int t_beg = ks * p.tiles_per_split;
-  int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
 
-  for (int kt = t_beg; kt < t_end; ++kt) {
+  for (int kt = w.t_beg; kt < w.t_end; ++kt) {
     const int j0 = kt * TK;
-    const float* yrows[BKL / 16];
-#pragma unroll
-    for (int i = 0; i < BKL / 16; ++i) {
-      int j = j0 + (tid + i * 256) / (BKL / 4); j = j < Ny ? j : Ny - 1;  // clamped: masked in the epilogue
-      yrows[i] = p.Y + (long)j * P;
-    }
     float bk[16];                                                         // bias of this lane's 16 key rows
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = j0 + wm * 32 + keyrow32(r, h);
-      bk[r] = (p.bias && key < Ny) ? p.bias[key] : 0.f;
-    }
+    for (int r = 0; r < 16; ++r) bk[r] = w.key_bias(p.bias, j0, r);
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    s_tile<BKL>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
+    w.product(j0, acc);
     // keys in rising order within the lane (tiles rise, keyrow32 rises with r): `>` keeps the lower key of a tie
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -143,20 +121,12 @@ __global__ __launch_bounds__(256) void sinkhorn_sample_finalize(const float* par
 
 bool shape_ok(int Mx, int Ny, int P) { return Mx > 0 && Ny > 0 && P > 0 && !(P & 3) && P <= SAMPLE_PMAX; }
 
-// the grid of the LSE pass (clipk_sim_lse_bias_plan); its splits are ceil(ntiles / ksplit) tiles long
-void plan(int Mx, int Ny, int* nqb, int* ksplit, int* tps, int* ntiles) {
-  (void)clipk_sim_lse_bias_plan(Mx, Ny, nqb, ksplit);
-  *ntiles = (Ny + TK - 1) / TK;
-  *tps = (*ntiles + *ksplit - 1) / *ksplit;
-}
-
 }  // namespace
 
 extern "C" size_t clipk_sim_sample_workspace(int Mx, int Ny, int P) {
   if (!shape_ok(Mx, Ny, P)) return 0;
-  int nqb, ks, tps, nt;
-  plan(Mx, Ny, &nqb, &ks, &tps, &nt);
-  return (size_t)ks * Mx * (sizeof(float) + sizeof(int));                 // best values, then best keys
+  const size_t ks = key_split_plan(Mx, Ny, TQ).ksplit;
+  return ks * Mx * (sizeof(float) + sizeof(int));                         // best values, then best keys
 }
 
 extern "C" int clipk_sim_sample(const float* X, int Mx, const float* Y, int Ny, int P, const float* scale,
@@ -167,13 +137,14 @@ extern "C" int clipk_sim_sample(const float* X, int Mx, const float* Y, int Ny, 
   if (!X || !Y || !scale || !seed_offset || !idx || !workspace) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
   if (workspace_bytes < clipk_sim_sample_workspace(Mx, Ny, P)) return CLIPK_ERR_BAD_ARG;
+  const KeySplitPlan k = key_split_plan(Mx, Ny, TQ);                      // the grid of the LSE pass
+  const int ks = k.ksplit;
   SSP p{};
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale; p.bias = bias; p.seed_offset = seed_offset;
-  int nqb, ks;
-  plan(Mx, Ny, &nqb, &ks, &p.tiles_per_split, &p.ntiles);
+  p.tiles_per_split = k.tiles_per_split; p.ntiles = k.ntiles;
   p.part_z = (float*)workspace;
   p.part_k = (int*)(p.part_z + (size_t)ks * Mx);
-  hipLaunchKernelGGL(sinkhorn_sample_kernel, dim3(nqb, ks), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(sinkhorn_sample_kernel, dim3(k.nqb, ks), dim3(256), 0, (hipStream_t)stream, p);
   int rc = clipk_check_launch();
   if (rc) return rc;
   hipLaunchKernelGGL(sinkhorn_sample_finalize, dim3((Mx + 255) / 256), dim3(256), 0, (hipStream_t)stream,

@@ -890,13 +890,8 @@ SIM_LSE_BIAS_MAX_P = 768        # clipk_sim_lse_bias
 SINKHORN_APPLY_MAX_P = 512      # clipk_sinkhorn_apply
 
 
-def _sinkhorn_args(x, y, scale, max_p, vectors=()):
-    """Operand checks of the two Sinkhorn entries, before any launch.  vectors: (name, tensor or None, length)."""
-    Mx, Ny, P = _retrieval_args(x, y)
-    if P > max_p:
-        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {max_p})")
-    if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or scale.numel() != 1:
-        raise TypeError("scale must be a one-element float32 device tensor")
+def _f32_vectors(vectors):
+    """Dtype, shape and contiguity of optional f32 vectors.  vectors: (name, tensor or None, length)."""
     for name, t, n in vectors:
         if t is None:
             continue
@@ -904,6 +899,16 @@ def _sinkhorn_args(x, y, scale, max_p, vectors=()):
             raise TypeError(f"{name} must be float32, got {t.dtype}")
         if t.shape != (n,) or not t.is_contiguous():
             raise ValueError(f"{name} must be a contiguous tensor of shape ({n},), got {tuple(t.shape)}")
+
+
+def _sinkhorn_args(x, y, scale, max_p, vectors=()):
+    """Operand checks of the two Sinkhorn entries, before any launch.  vectors: (name, tensor or None, length)."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    if P > max_p:
+        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {max_p})")
+    if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or scale.numel() != 1:
+        raise TypeError("scale must be a one-element float32 device tensor")
+    _f32_vectors(vectors)
     for t in (x, y, scale, *(v[1] for v in vectors)):
         if t is not None and not t.is_cuda:
             raise ValueError("the Sinkhorn kernels need device tensors (there is no CPU fallback)")
@@ -968,13 +973,7 @@ def sim_lse_bias_x3(xhi, xlo, yhi, ylo, P: int, scale, bias=None, logw=None, pre
         raise TypeError("scale must be a one-element float32 device tensor")
     vectors = (("bias", bias, Ny), ("logw", logw, Mx), ("prev", prev, Mx), ("out", out, Mx),
                ("err", None if err is None else err.reshape(-1), 1))
-    for name, t, n in vectors:
-        if t is None:
-            continue
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-        if t.shape != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous tensor of shape ({n},), got {tuple(t.shape)}")
+    _f32_vectors(vectors)
     if (average or err is not None) and prev is None:
         raise ValueError("average=True and err need prev")
     tensors = (xhi, xlo, yhi, ylo, scale, *(v[1] for v in vectors))
@@ -1181,13 +1180,7 @@ def kernel_sums(x, y, gammas, weights, nx=None, ny=None, diag_offset=-1, want_su
     if not 1 <= B <= KERNEL_SUMS_MAX_B or weights.shape[0] != B:
         raise ValueError(f"gammas and weights must have the same 1..{KERNEL_SUMS_MAX_B} entries, got {B} and "
                          f"{weights.shape[0]}")
-    for name, t, n in (("nx", nx, Mx), ("ny", ny, Ny)):
-        if t is None:
-            continue
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-        if t.shape != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous tensor of shape ({n},), got {tuple(t.shape)}")
+    _f32_vectors((("nx", nx, Mx), ("ny", ny, Ny)))
     diag_offset = int(diag_offset)
     if diag_offset < -1:
         raise ValueError(f"diag_offset must be -1 (nothing skipped) or >= 0, got {diag_offset}")
