@@ -34,6 +34,9 @@ from .flow import ExactOptimalTransportConditionalFlowMatcher, linear_conditiona
 from . import flow
 from .distribution import evaluate_distributions, frechet_distance, mmd2
 from . import distribution
+from .cluster import (KMeansResult, adjusted_rand_index, cluster_agreement, contingency, kmeans,
+                      normalized_mutual_info)
+from . import cluster
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -53,4 +56,6 @@ __all__ = [
     "AssignmentResult", "exact_assignment", "wasserstein2_exact",
     "ExactOptimalTransportConditionalFlowMatcher", "linear_conditional_flow",
     "distribution", "mmd2", "frechet_distance", "evaluate_distributions",
+    "cluster", "kmeans", "KMeansResult", "contingency", "adjusted_rand_index", "normalized_mutual_info",
+    "cluster_agreement",
 ]

@@ -1207,6 +1207,62 @@ def kernel_sums(x, y, gammas, weights, nx=None, ny=None, diag_offset=-1, want_su
     return ksum, kbary
 
 
+KMEANS_MAX_P = 512             # clipk_kmeans_step
+KMEANS_MAX_K_FUSED = 64        # ... assignment and update in one launch
+KMEANS_MAX_K = 65536           # ... with the labels given
+KMEANS_MAX_N = 1 << 24         # ... the f32 counts are exact
+
+
+def kmeans_step_plan(N: int, K: int):
+    """(64-centroid blocks, point-range splits) of the grid clipk_kmeans_step launches: that of clipk_sim_lse_bias with
+    the centroids as the queries and the points as the keys."""
+    return sim_lse_bias_plan(K, N)
+
+
+def kmeans_step(x, c, nc=None, labels=None):
+    """One Lloyd iteration (include/clipk.h: clipk_kmeans_step): (labels int32 [N], best f32 [N], sums f32 [K, P],
+    counts f32 [K]).  x [N, P], c [K, P] f32; nc [K]: the centroids' squared norms, computed here when not given (pass
+    zeros for the cosine form).  labels=None (K <= 64): labels[i] = argmax_c 2 <x_i, c_c> - nc[c] with equal scores to
+    the lower c, best[i] = that maximum, sums / counts of those labels - one launch.  labels int32 [N] (K <= 65536): sums
+    and counts of the given labels; the labels are returned as they came and best is None."""
+    N, K, P = _retrieval_args(x, c)
+    if P > KMEANS_MAX_P:
+        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {KMEANS_MAX_P})")
+    if N > KMEANS_MAX_N:
+        raise ValueError(f"N = {N} is outside the kernel's limit (N <= {KMEANS_MAX_N})")
+    kmax = KMEANS_MAX_K_FUSED if labels is None else KMEANS_MAX_K
+    if K > kmax:
+        raise ValueError(f"K = {K} is outside the kernel's limit (K <= {KMEANS_MAX_K_FUSED} without labels, "
+                         f"K <= {KMEANS_MAX_K} with them)")
+    _f32_vectors((("nc", nc, K),))
+    if labels is not None:
+        _int32_vector("labels", labels, N, x.device)
+    for t in (x, c, nc, labels):
+        if t is not None and not t.is_cuda:
+            raise ValueError("the k-means kernel needs device tensors (there is no CPU fallback)")
+    _need_cuda(x, c, nc, labels)
+    dev = x.device
+    fused = labels is None
+    if fused:
+        if nc is None:
+            nc = (c * c).sum(1)
+        labels = torch.empty(N, dtype=torch.int32, device=dev)
+        best = torch.empty(N, dtype=torch.float32, device=dev)
+    else:
+        best = None
+    sums = torch.empty((K, P), dtype=torch.float32, device=dev)
+    counts = torch.empty(K, dtype=torch.float32, device=dev)
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_kmeans_step_workspace(N, K, P), dev, "kmeans", stream)
+    check(_timed("kmeans_step", 2.0 * N * min(K, 64) * P * (2 if fused else 1),
+                 lambda: lib.clipk_kmeans_step(x.data_ptr(), N, c.data_ptr(), K, P, ptr(nc) if fused else None,
+                                               None if fused else labels.data_ptr(), labels.data_ptr() if fused else None,
+                                               ptr(best), sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                               stream)), "clipk_kmeans_step")
+    return labels, best, sums, counts
+
+
 def ce_logits_lse(S, S2=None, columns=False, label_offset=0):
     """LSE over the rows (optionally of [S | S2]) or the columns of materialised f32 logits + the diagonal logit."""
     _need_cuda(S, S2)

@@ -972,6 +972,35 @@ int clipk_auction_rounds(const float* X, const float* Y, int N, int P, float* bi
                          int* n_unassigned /* device int32 */, int* stalled /* device int32 */, int n_rounds,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * One Lloyd (k-means) iteration over an f32 cloud X [N,P] with centroids C [K,P] without the N x K score matrix:
+ * clip_dplm_amd.cluster.kmeans, what the reference's analyze_embedding_alignment (tong/tests/losses/
+ * test_contrastive.py:11-16) takes from a host library.
+ *
+ * clipk_kmeans_step - two modes, chosen by labels_in:
+ *     score_ic  = 2 <X_i, C_c> - nc[c]              nc [K] = |C_c|^2, or zeros for the cosine form (arg max <X_i, C_c>)
+ *     labels[i] = argmax_c score_ic (equal scores go to the LOWER c),   best[i] = max_c score_ic
+ *     sums[c,:] = sum_{i: labels[i] == c} X_i,      counts[c] = #{i: labels[i] == c}   (f32, exact: N <= 2^24)
+ *   The squared distance to the nearest centroid is max(|X_i|^2 - best[i], 0).
+ *   Fused mode (labels_in == NULL, K <= 64): labels int32 [N] and best f32 [N] are written, and sums / counts follow
+ *   those labels - one launch reads each tile of X once for assignment and update.
+ *   Labels-given mode (labels_in int32 [N], K <= 65536): sums / counts follow labels_in (an entry outside [0, K) joins
+ *   no cluster); C, nc, labels and best are not touched and may be NULL.
+ *   Kernel: the structure of clipk_kernel_sums with the roles turned round - the centroids are the 64 queries on the
+ *   lanes, the points the keys of the tile walk (64-point tiles on v_mfma_f32_32x32x2_f32); the score tile goes to LDS,
+ *   four threads per point row take the arg max, the row is overwritten with its one-hot, and sums^T is the second MFMA
+ *   product with the staged point rows; counts are the column sums of the one-hot tile.  Labels-given mode has no first
+ *   product and one workgroup column per 64 centroids.  Point-range splits (the plan of clipk_sim_lse_bias for Mx = K,
+ *   Ny = N) are summed in split order by a finalize launch, so for K <= 64 the two modes give bit-identical sums.
+ *   Supported: 1 <= N <= 2^24, P % 4 == 0, P <= 512, X / C / sums / workspace 16-byte aligned.
+ * Anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED before any launch and the workspace helper returns 0.
+ * Never allocates, never synchronises, capturable, no float atomics: results depend on the shapes and inputs alone. */
+size_t clipk_kmeans_step_workspace(int N, int K, int P);
+int clipk_kmeans_step(const float* X, int N, const float* C /*[K,P] (fused)*/, int K, int P,
+                      const float* nc /*[K] (fused)*/, const int* labels_in /*[N] or NULL: fused mode*/,
+                      int* labels /*[N] (fused)*/, float* best /*[N] (fused)*/, float* sums /*[K,P]*/,
+                      float* counts /*[K]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
