@@ -41,7 +41,6 @@
 namespace {
 
 constexpr int TOP2_PMAX = 768;                    // contraction limit (that of the LSE pass)
-constexpr int NO_KEY = 0x7fffffff;                // loses every tie: a lane that saw no key below Ny
 constexpr int AUCTION_NMAX = 65536;               // one workgroup compacts the rows
 constexpr int RC_THREADS = 1024;
 constexpr int TOP2_KSMAX = 256;                   // key splits at most: one per CU
@@ -68,7 +67,7 @@ __device__ __forceinline__ int active_count(const int* n_active, int Mr) {
 
 // (z1, k1, z2) <- merge with (zo1, ko, zo2)
 __device__ __forceinline__ void merge_top2(float& z1, int& k1, float& z2, float zo1, int ko, float zo2) {
-  if (zo1 > z1 || (zo1 == z1 && ko < k1)) { z2 = fmaxf(z1, zo2); z1 = zo1; k1 = ko; }
+  if (better_key(zo1, ko, z1, k1)) { z2 = fmaxf(z1, zo2); z1 = zo1; k1 = ko; }
   else z2 = fmaxf(z2, zo1);
 }
 
@@ -195,10 +194,6 @@ __global__ __launch_bounds__(RC_THREADS) void auction_resolve_compact(int N, int
   if (tid == 0) n_unassigned[0] = total;
 }
 
-bool shape_ok(int Mx, int Mr, int Ny, int P) {
-  return Mx > 0 && Mr > 0 && Ny > 0 && P > 0 && !(P & 3) && P <= TOP2_PMAX;
-}
-
 // TOP2_TPS tiles per split whatever the row count, longer splits only beyond TOP2_KSMAX of them (the partials are
 // 12 bytes per row and split)
 void plan(int Mr, int Ny, int* nqb, int* ksplit, int* tps, int* ntiles) {
@@ -243,7 +238,7 @@ extern "C" int clipk_sim_top2_bias_plan(int Mr, int Ny, int* nqb, int* ksplit) {
 }
 
 extern "C" size_t clipk_sim_top2_bias_workspace(int Mr, int Ny, int P) {
-  if (!shape_ok(1, Mr, Ny, P)) return 0;
+  if (!cloud_shape_ok(Mr, Ny, P, TOP2_PMAX)) return 0;
   return top2_ws_bytes(Mr, Ny);
 }
 
@@ -251,7 +246,7 @@ extern "C" int clipk_sim_top2_bias(const float* X, int Mx, const int* rows, int 
                                    int Ny, int P, const float* scale, const float* bias, int* idx, float* best, float* gap,
                                    void* workspace, size_t workspace_bytes, void* stream) {
   if (Mx <= 0 || Mr <= 0 || Ny <= 0 || P <= 0) return CLIPK_ERR_BAD_ARG;
-  if (!shape_ok(Mx, Mr, Ny, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (!cloud_shape_ok(Mr, Ny, P, TOP2_PMAX)) return CLIPK_ERR_UNSUPPORTED;
   if (!X || !Y || !scale || !idx || !workspace) return CLIPK_ERR_BAD_ARG;
   if (!rows && Mr > Mx) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
@@ -264,7 +259,7 @@ extern "C" int clipk_sim_top2_bias(const float* X, int Mx, const int* rows, int 
 
 // workspace: offers [N] u64 | list [N] i32 | the scale 2 (f32) | the top-two partials
 extern "C" size_t clipk_auction_rounds_workspace(int N, int P) {
-  if (!shape_ok(N, N, N, P) || N > AUCTION_NMAX) return 0;
+  if (!cloud_shape_ok(N, N, P, TOP2_PMAX) || N > AUCTION_NMAX) return 0;
   return round16((size_t)N * 8) + round16((size_t)N * 4) + 16 + top2_ws_bytes(N, N);
 }
 
@@ -272,7 +267,7 @@ extern "C" int clipk_auction_rounds(const float* X, const float* Y, int N, int P
                                     int* assigned, int* owner, int* n_unassigned, int* stalled, int n_rounds,
                                     void* workspace, size_t workspace_bytes, void* stream) {
   if (N <= 0 || P <= 0 || n_rounds < 0) return CLIPK_ERR_BAD_ARG;
-  if (!shape_ok(N, N, N, P) || N > AUCTION_NMAX) return CLIPK_ERR_UNSUPPORTED;
+  if (!cloud_shape_ok(N, N, P, TOP2_PMAX) || N > AUCTION_NMAX) return CLIPK_ERR_UNSUPPORTED;
   if (!X || !Y || !bias || !eps || !assigned || !owner || !n_unassigned || !stalled || !workspace) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
   if (workspace_bytes < clipk_auction_rounds_workspace(N, P)) return CLIPK_ERR_BAD_ARG;

@@ -1,7 +1,8 @@
 // cloud_tile.h — what the point-cloud kernels (sinkhorn.hip, sinkhorn_sample.hip, auction.hip, kernel_sums.hip) share
 // on top of sim_tile.h's exact-f32 64 x 64 block (keys on the MFMA rows, queries on the lanes):
 //   * KeyWalk: one workgroup's walk over the 64-key tiles of its key split - coordinates, staging rows, the S^T product;
-//   * key_split_plan: the (query block, key split) grid on the host.
+//   * key_split_plan: the (query block, key split) grid on the host; cloud_shape_ok: the shapes the passes accept;
+//   * NO_KEY, better_key, take_better: the (value, key) order of the sampler's and the top-two pass's merges.
 // Each kernel keeps what it does with the products, its merge rule and its own partial format.  What only the two
 // kernels with a weighted key sum share is in cloud_keysum.h; sinkhorn_apply_kernel has the walk in its own body.
 #pragma once
@@ -11,6 +12,17 @@
 namespace {
 
 constexpr int TQ = 64, TK = 64;                   // queries per workgroup, keys per tile
+constexpr int NO_KEY = 0x7fffffff;                // loses every tie: a lane that saw no key below Ny
+
+// what the f32 passes accept: positive sizes, rows of whole 16-byte chunks, a contraction of at most pmax
+inline bool cloud_shape_ok(int Mx, int Ny, int P, int pmax) { return Mx > 0 && Ny > 0 && P > 0 && !(P & 3) && P <= pmax; }
+
+// The order of (value, key) pairs, the same at every merge level: the higher value wins, equal values go to the lower key.
+__device__ __forceinline__ bool better_key(float zo, int ko, float z, int k) { return zo > z || (zo == z && ko < k); }
+
+__device__ __forceinline__ void take_better(float& z, int& k, float zo, int ko) {
+  if (better_key(zo, ko, z, k)) { z = zo; k = ko; }
+}
 
 // ------------------------------------------------------------------------------------------------ key-split plan
 struct KeySplitPlan { int nqb, ksplit, tiles_per_split, ntiles; };

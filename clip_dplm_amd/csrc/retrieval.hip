@@ -21,6 +21,7 @@
 // CLS = false is the plain kernel (the filter sits under `if constexpr`).
 #include "common.h"
 #include "sim_tile.h"
+#include "plane_tile.h"
 #include <limits.h>
 #include <math.h>
 
@@ -300,10 +301,10 @@ __global__ void sim_rank_finalize(const int* part_cnt, int ksplit, int Mx, const
   rank[q] = label_of(labels, label_offset, q, Ny) >= 0 ? r : -1;
 }
 
-// plan: one workgroup per (64-query block, key split), >= 2 workgroups per CU (the LSE pass's plan); the option
+// plan: one workgroup per (query block of qb, key split), >= 2 workgroups per CU (the LSE pass's plan); the option
 // retrieval_splits (> 0) fixes the split count instead
-void plan(int Mx, int Ny, int* nqb, int* ksplit, int* tps, int* ntiles) {
-  *nqb = (Mx + RQ - 1) / RQ;
+void plan(int Mx, int Ny, int qb, int* nqb, int* ksplit, int* tps, int* ntiles) {
+  *nqb = (Mx + qb - 1) / qb;
   *ntiles = (Ny + RK - 1) / RK;
   const int opt = clipk_opt_get(OPT_RETRIEVAL_SPLITS);
   int ks = opt > 0 ? opt : (512 + *nqb - 1) / *nqb;
@@ -324,7 +325,7 @@ int topk_launch(const float* X, int Mx, const float* Y, int Ny, int P, float sca
   TKP p;
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale;
   int nqb, ksplit;
-  plan(Mx, Ny, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  plan(Mx, Ny, RQ, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
   const int la = 4 * ksplit, lb = (la + MG - 1) / MG;
   const size_t per_list = (size_t)Mx * KP;
   float* a_s = reinterpret_cast<float*>(ws);
@@ -358,7 +359,7 @@ int topk_launch(const float* X, int Mx, const float* Y, int Ny, int P, float sca
 extern "C" size_t clipk_sim_topk_workspace(int Mx, int Ny, int P, int k) {
   if (!shape_ok(Mx, Ny, P) || k < 1 || k > 64 || k > Ny) return 0;
   int nqb, ksplit, tps, nt;
-  plan(Mx, Ny, &nqb, &ksplit, &tps, &nt);
+  plan(Mx, Ny, RQ, &nqb, &ksplit, &tps, &nt);
   const size_t la = 4 * (size_t)ksplit, lb = (la + MG - 1) / MG;
   return (la + lb) * (size_t)Mx * kpad(k) * (sizeof(float) + sizeof(int));
 }
@@ -384,7 +385,7 @@ extern "C" int clipk_sim_topk(const float* X, int Mx, const float* Y, int Ny, in
 extern "C" size_t clipk_sim_rank_workspace(int Mx, int Ny, int P) {
   if (!shape_ok(Mx, Ny, P)) return 0;
   int nqb, ksplit, tps, nt;
-  plan(Mx, Ny, &nqb, &ksplit, &tps, &nt);
+  plan(Mx, Ny, RQ, &nqb, &ksplit, &tps, &nt);
   return (size_t)ksplit * Mx * sizeof(int);
 }
 
@@ -401,7 +402,7 @@ extern "C" int clipk_sim_rank(const float* X, int Mx, const float* Y, int Ny, in
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale; p.labels = labels; p.label_offset = label_offset;
   p.part_cnt = static_cast<int*>(workspace); p.pos = pos;
   int nqb, ksplit;
-  plan(Mx, Ny, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  plan(Mx, Ny, RQ, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sim_rank_kernel<false>, dim3(nqb, ksplit), dim3(256), 0, st, p);
   int rc = clipk_check_launch();
@@ -424,7 +425,7 @@ extern "C" int clipk_sim_rank_cls(const float* X, int Mx, const float* Y, int Ny
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale; p.labels = labels; p.label_offset = label_offset;
   p.part_cnt = static_cast<int*>(workspace); p.pos = pos; p.cls = cls;
   int nqb, ksplit;
-  plan(Mx, Ny, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  plan(Mx, Ny, RQ, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sim_rank_kernel<true>, dim3(nqb, ksplit), dim3(256), 0, st, p);
   int rc = clipk_check_launch();
@@ -438,10 +439,11 @@ extern "C" int clipk_sim_rank_cls(const float* X, int Mx, const float* Y, int Ny
 // Prefiltered exact top-k: a bf16 candidate pass, an exact re-rank of the candidates and a per-query certificate
 // (include/clipk.h: clipk_split_bf16, clipk_sim_topk_cand, clipk_sim_rerank; the bound is derived there).
 //
-// Candidate pass tile (sim_cand_kernel): 128 queries x 64 keys per workgroup, 4 waves; wave w owns queries
-// [32 w, +32) against all 64 keys, i.e. two 32x32 accumulators of v_mfma_f32_32x32x16_bf16 sharing one query fragment.
-// 128 queries per workgroup halve the gallery re-reads of the exact kernel's 64 (shape a: 64 instead of 128 passes
-// over the bf16 gallery, most of them L2 / MALL hits because the query blocks of one key split run side by side).
+// Candidate pass tile (sim_cand_kernel): plane_tile.h's PlaneWalk, shared with sinkhorn.hip's bf16x3 LSE pass - 128
+// queries x 64 keys per workgroup, 4 waves; wave w owns queries [32 w, +32) against all 64 keys, i.e. two 32x32
+// accumulators of v_mfma_f32_32x32x16_bf16 sharing one query fragment.  128 queries per workgroup halve the gallery
+// re-reads of the exact kernel's 64 (shape a: 64 instead of 128 passes over the bf16 gallery, most of them L2 / MALL hits
+// because the query blocks of one key split run side by side).
 // A lane keeps ONE list (its query), fed by 32 keys per tile in ascending index order (accumulator 0 then 1, rows
 // ascending), so the sorted-list epilogue and topk_merge_kernel are reused unchanged, with 2 lists per key split.
 // bf16 planes have a row pitch of P rounded up to 32 with zero pads (clipk_split_bf16 writes them): the K loop has no
@@ -453,8 +455,7 @@ extern "C" int clipk_sim_rank_cls(const float* X, int Mx, const float* Y, int Ny
 // ================================================================================================================
 namespace {
 
-constexpr int CQ = 128, CK = 64;          // queries per workgroup, keys per tile of the candidate pass
-constexpr int CBK = 32, CLD = CBK + 8;    // K-step in bf16 elements (two MFMA k-steps), LDS row pitch (80 B)
+static_assert(PLK == RK, "plan() counts tiles of RK keys");
 constexpr int PF_MAX_P = 65536;           // prefilter entries: the norm and bound arithmetic assumes P <= 2^16
 
 int plane_pitch(int P) { return (P + 31) & ~31; }
@@ -509,87 +510,23 @@ struct CKPm {
 
 template <int KP, bool X3>
 __global__ __launch_bounds__(256, 2) void sim_cand_kernel(const CKPm p) {
-  constexpr int NPL = X3 ? 2 : 1, KT = CK * CLD, QT = CQ * CLD, BUF = NPL * (KT + QT);
-  __shared__ __attribute__((aligned(16))) unsigned short sm[2 * BUF];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  const int q0 = blockIdx.x * CQ, ks = blockIdx.y;
-  const int PP = p.PP, Ny = p.Ny;
+  using Walk = PlaneWalk<X3 ? 2 : 1>;
+  __shared__ __attribute__((aligned(16))) unsigned short sm[Walk::LDS_ELEMS];
   const float scale = p.scale;
-  const int sr = tid >> 2, sc = (tid & 3) * 8;                            // staging: row sr (+64), 16-byte chunk sc
-  const unsigned short* xs[2][NPL];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int q = q0 + sr + 64 * i; q = q < p.Mx ? q : p.Mx - 1;               // clamped: computed and dropped
-    xs[i][0] = p.xh + (long)q * PP + sc;
-    if constexpr (X3) xs[i][1] = p.xl + (long)q * PP + sc;
-  }
+  const Walk wk(p.xh, p.xl, p.Mx, p.yh, p.yl, p.Ny, p.PP, p.tiles_per_split, p.ntiles, sm);
+  const int h = wk.h, ks = wk.ks, qg = wk.qg, Ny = p.Ny;
   float s[KP];
   int ix[KP];
 #pragma unroll
   for (int t = 0; t < KP; ++t) { s[t] = -INFINITY; ix[t] = EMPTY; }
-  const int t_beg = ks * p.tiles_per_split;
-  int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
-  const int ns = PP / CBK;
 
-  for (int kt = t_beg; kt < t_end; ++kt) {
-    const int j0 = kt * CK;
-    int j = j0 + sr; j = j < Ny ? j : Ny - 1;
-    const unsigned short* ys[NPL];
-    ys[0] = p.yh + (long)j * PP + sc;
-    if constexpr (X3) ys[1] = p.yl + (long)j * PP + sc;
-    u32x4 ky[NPL], kq[2][NPL];
-    auto load = [&](int k0) {
-#pragma unroll
-      for (int pl = 0; pl < NPL; ++pl) {
-        ky[pl] = *reinterpret_cast<const u32x4*>(ys[pl] + k0);
-        kq[0][pl] = *reinterpret_cast<const u32x4*>(xs[0][pl] + k0);
-        kq[1][pl] = *reinterpret_cast<const u32x4*>(xs[1][pl] + k0);
-      }
-    };
-    auto store = [&](unsigned short* b) {
-#pragma unroll
-      for (int pl = 0; pl < NPL; ++pl) {
-        *reinterpret_cast<u32x4*>(b + pl * KT + sr * CLD + sc) = ky[pl];
-        *reinterpret_cast<u32x4*>(b + NPL * KT + pl * QT + sr * CLD + sc) = kq[0][pl];
-        *reinterpret_cast<u32x4*>(b + NPL * KT + pl * QT + (sr + 64) * CLD + sc) = kq[1][pl];
-      }
-    };
+  for (int kt = wk.t_beg; kt < wk.t_end; ++kt) {
+    const int j0 = kt * PLK;
     f32x16 acc[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    load(0);
-    __syncthreads();                                                      // whoever read these buffers last is done
-    store(sm);
-    __syncthreads();
-    for (int st = 0; st < ns; ++st) {
-      const unsigned short* b = sm + (st & 1) * BUF;
-      if (st + 1 < ns) load((st + 1) * CBK);
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        bf16x8 a[2][NPL], bq[NPL];
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl) {
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
-            a[kb][pl] = *reinterpret_cast<const bf16x8*>(b + pl * KT + (kb * 32 + li) * CLD + kk * 16 + 8 * h);
-          bq[pl] = *reinterpret_cast<const bf16x8*>(b + NPL * KT + pl * QT + (w * 32 + li) * CLD + kk * 16 + 8 * h);
-        }
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kb][0], bq[0], acc[kb], 0, 0, 0);
-          if constexpr (X3) {
-            acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kb][0], bq[1], acc[kb], 0, 0, 0);
-            acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kb][1], bq[0], acc[kb], 0, 0, 0);
-          }
-        }
-      }
-      if (st + 1 < ns) store(sm + ((st + 1) & 1) * BUF);
-      __syncthreads();
-    }
+    wk.product(j0, acc);
     const int kb0 = j0 + 4 * h;                                           // key of acc[kb][r]: kb0 + 32 kb + key_off(r)
     float tmax = -INFINITY;
-    if (j0 + CK <= Ny) {
+    if (j0 + PLK <= Ny) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, fmaxf(scale * acc[0][r], scale * acc[1][r]));
     } else {
@@ -617,25 +554,11 @@ __global__ __launch_bounds__(256, 2) void sim_cand_kernel(const CKPm p) {
     }
   }
 
-  const int qg = q0 + w * 32 + li;
   if (qg < p.Mx) {
     const long o = ((long)(ks * 2 + h) * p.Mx + qg) * KP;
 #pragma unroll
     for (int t = 0; t < KP; ++t) { p.part_s[o + t] = s[t]; p.part_i[o + t] = ix[t]; }
   }
-}
-
-// the plan of plan(), for 128-query blocks
-void cplan(int Mx, int Ny, int* nqb, int* ksplit, int* tps, int* ntiles) {
-  *nqb = (Mx + CQ - 1) / CQ;
-  *ntiles = (Ny + CK - 1) / CK;
-  const int opt = clipk_opt_get(OPT_RETRIEVAL_SPLITS);
-  int ks = opt > 0 ? opt : (512 + *nqb - 1) / *nqb;
-  if (ks > 65535) ks = 65535;
-  if (ks > *ntiles) ks = *ntiles;
-  if (ks < 1) ks = 1;
-  *tps = (*ntiles + ks - 1) / ks;
-  *ksplit = (*ntiles + *tps - 1) / *tps;
 }
 
 int kcpad(int kc) { return kc <= 16 ? 16 : kc <= 32 ? 32 : 64; }
@@ -645,7 +568,7 @@ size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 template <int KP>
 int cand_launch(CKPm p, int Mx, int Ny, int kc, bool x3, float* cs, int64_t* ci, char* lists, hipStream_t st) {
   int nqb, ksplit;
-  cplan(Mx, Ny, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
+  plan(Mx, Ny, PLQ, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
   const int la = 2 * ksplit, lb = (la + MG - 1) / MG;
   const size_t per_list = (size_t)Mx * KP;
   float* a_s = reinterpret_cast<float*>(lists);
@@ -767,7 +690,7 @@ extern "C" int clipk_split_bf16(const float* X, int n_rows, int P, void* hi, voi
 extern "C" size_t clipk_sim_topk_cand_workspace(int Mx, int Ny, int P, int kc, int planes) {
   if (!shape_ok(Mx, Ny, P) || P % 4 || P > PF_MAX_P || kc < 1 || kc > 64 || (planes != 1 && planes != 2)) return 0;
   int nqb, ksplit, tps, nt;
-  cplan(Mx, Ny, &nqb, &ksplit, &tps, &nt);
+  plan(Mx, Ny, PLQ, &nqb, &ksplit, &tps, &nt);
   const size_t la = 2 * (size_t)ksplit, lb = (la + MG - 1) / MG;
   return round256((size_t)planes * Mx * plane_pitch(P) * 2) +
          (la + lb) * (size_t)Mx * kcpad(kc) * (sizeof(float) + sizeof(int));

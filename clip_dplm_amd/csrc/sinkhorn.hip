@@ -9,13 +9,14 @@
 //     (m, l) partials; sinkhorn_lse_finalize merges them in a fixed order, forms logw - LSE, applies the averaged update
 //     of the symmetric problem and leaves each row's marginal-error term for sinkhorn_err_reduce (one workgroup, fixed
 //     order: the error scalar is as deterministic as the potentials);
-//   * sinkhorn_lse_x3_kernel: the same pass with the product as a bf16x3 split on v_mfma_f32_32x32x16_bf16 (128-query
-//     blocks, its own plan), feeding the same finalize and error kernels (clipk_sim_lse_bias_x3);
+//   * sinkhorn_lse_x3_kernel: the same pass with the product as a bf16x3 split on v_mfma_f32_32x32x16_bf16 (plane_tile.h's
+//     PlaneWalk: 128-query blocks, its own plan), feeding the same finalize and error kernels (clipk_sim_lse_bias_x3);
 //   * sinkhorn_apply_kernel: S tile -> P tile into LDS -> cloud_keysum.h's weighted key sum (bary^T = Y^T P^T), mass and
 //     cost from the same P values; key-split slabs are summed in split order by split_sum_finalize.
 // No float atomics, no cooperative launch: results depend on the shapes alone.
 #include "common.h"
 #include "cloud_tile.h"
+#include "plane_tile.h"
 #include <math.h>
 
 namespace {
@@ -87,17 +88,15 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_lse_kernel(const SLP p) {
 // ------------------------------------------------------------------------------------------------ bf16x3 LSE pass
 // The same half-iteration with the product on the bf16 matrix pipe: A = hi.hi + hi.lo + lo.hi over the planes
 // clipk_split_bf16 writes (row pitch PP = P rounded up to 32, pads zero: no K tail, every staging load 16 bytes).  The
-// tile walk is retrieval.hip's sim_cand_kernel<., X3>, statement for statement: 128 queries x 64 keys per workgroup,
-// wave w owns queries [32 w, +32) against all 64 keys (two 32 x 32 accumulators of v_mfma_f32_32x32x16_bf16 sharing one
-// query fragment, three MFMAs per fragment pair), LDS rows of 80 bytes, two staging buffers (60 KiB: two workgroups per
-// CU).  The epilogue is sinkhorn_lse_kernel's running (max, sum) per lane over the lane's 32 keys of the tile; a wave
-// holds all 64 keys of its queries, so only the two lane halves are merged and the workgroup needs no merge slots.  The
-// (m, l) partials have sinkhorn_lse_kernel's format: sinkhorn_lse_finalize and sinkhorn_err_reduce serve both.
+// tile walk is plane_tile.h's PlaneWalk<2>, shared with retrieval.hip's sim_cand_kernel: 128 queries x 64 keys per
+// workgroup, wave w owns queries [32 w, +32) against all 64 keys (two 32 x 32 accumulators of v_mfma_f32_32x32x16_bf16
+// sharing one query fragment, three MFMAs per fragment pair), LDS rows of 80 bytes, two staging buffers (60 KiB: two
+// workgroups per CU).  The epilogue is sinkhorn_lse_kernel's running (max, sum) per lane over the lane's 32 keys of the
+// tile; a wave holds all 64 keys of its queries, so only the two lane halves are merged and the workgroup needs no merge
+// slots.  The (m, l) partials have sinkhorn_lse_kernel's format: sinkhorn_lse_finalize and sinkhorn_err_reduce serve both.
 // The exponentials are __expf (v_exp_f32 of the argument times log2 e): the argument is <= 0, its rounding moves a term
 // by |arg| 2^-24 relative, and 32 of them per tile and lane sit on the VALU, which does not overlap this SIMD's MFMAs.
-constexpr int XQ = 128, XK = 64;                  // queries per workgroup, keys per tile
-static_assert(XK == TK, "key_split_plan counts tiles of TK keys");
-constexpr int XBK = 32, XLD = XBK + 8;            // K-step in bf16 elements (two MFMA k-steps), LDS row pitch (80 B)
+static_assert(PLK == TK, "key_split_plan counts tiles of TK keys");
 
 struct SLPX {
   const unsigned short* xh; const unsigned short* xl; int Mx;
@@ -110,30 +109,14 @@ struct SLPX {
 };
 
 __global__ __launch_bounds__(256, 2) void sinkhorn_lse_x3_kernel(const SLPX p) {
-  constexpr int KT = XK * XLD, QT = XQ * XLD, BUF = 2 * (KT + QT);
-  __shared__ __attribute__((aligned(16))) unsigned short sm[2 * BUF];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  const int q0 = blockIdx.x * XQ, ks = blockIdx.y;
-  const int PP = p.PP, Ny = p.Ny;
+  __shared__ __attribute__((aligned(16))) unsigned short sm[PlaneWalk<2>::LDS_ELEMS];
   const float scale = p.scale[0];
-  const int sr = tid >> 2, sc = (tid & 3) * 8;                            // staging: row sr (+64), 16-byte chunk sc
-  const unsigned short* xs[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int q = q0 + sr + 64 * i; q = q < p.Mx ? q : p.Mx - 1;               // clamped: computed and dropped
-    xs[i][0] = p.xh + (long)q * PP + sc;
-    xs[i][1] = p.xl + (long)q * PP + sc;
-  }
+  const PlaneWalk<2> wk(p.xh, p.xl, p.Mx, p.yh, p.yl, p.Ny, p.PP, p.tiles_per_split, p.ntiles, sm);
+  const int h = wk.h, ks = wk.ks, qg = wk.qg, Ny = p.Ny;
   float m_run = -INFINITY, l_run = 0.f;
-  const int t_beg = ks * p.tiles_per_split;
-  int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
-  const int ns = PP / XBK;
 
-  for (int kt = t_beg; kt < t_end; ++kt) {
-    const int j0 = kt * XK;
-    int j = j0 + sr; j = j < Ny ? j : Ny - 1;                             // clamped: masked in the epilogue
-    const unsigned short* ys[2] = {p.yh + (long)j * PP + sc, p.yl + (long)j * PP + sc};
+  for (int kt = wk.t_beg; kt < wk.t_end; ++kt) {
+    const int j0 = kt * PLK;
     const int kb0 = j0 + 4 * h;                                           // key of acc[kb][r]: kb0 + 32 kb + (keyrow32(r, 0))
     float bk[2][16];                                                      // bias of this lane's 32 keys
 #pragma unroll
@@ -143,56 +126,11 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_lse_x3_kernel(const SLPX p) {
         const int key = kb0 + 32 * kb + keyrow32(r, 0);
         bk[kb][r] = (p.bias && key < Ny) ? p.bias[key] : 0.f;
       }
-    u32x4 ky[2], kq[2][2];
-    auto load = [&](int k0) {
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) {
-        ky[pl] = *reinterpret_cast<const u32x4*>(ys[pl] + k0);
-        kq[0][pl] = *reinterpret_cast<const u32x4*>(xs[0][pl] + k0);
-        kq[1][pl] = *reinterpret_cast<const u32x4*>(xs[1][pl] + k0);
-      }
-    };
-    auto store = [&](unsigned short* b) {
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) {
-        *reinterpret_cast<u32x4*>(b + pl * KT + sr * XLD + sc) = ky[pl];
-        *reinterpret_cast<u32x4*>(b + 2 * KT + pl * QT + sr * XLD + sc) = kq[0][pl];
-        *reinterpret_cast<u32x4*>(b + 2 * KT + pl * QT + (sr + 64) * XLD + sc) = kq[1][pl];
-      }
-    };
     f32x16 acc[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    load(0);
-    __syncthreads();                                                      // whoever read these buffers last is done
-    store(sm);
-    __syncthreads();
-    for (int st = 0; st < ns; ++st) {
-      const unsigned short* b = sm + (st & 1) * BUF;
-      if (st + 1 < ns) load((st + 1) * XBK);
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        bf16x8 a[2][2], bq[2];
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
-            a[kb][pl] = *reinterpret_cast<const bf16x8*>(b + pl * KT + (kb * 32 + li) * XLD + kk * 16 + 8 * h);
-          bq[pl] = *reinterpret_cast<const bf16x8*>(b + 2 * KT + pl * QT + (w * 32 + li) * XLD + kk * 16 + 8 * h);
-        }
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kb][0], bq[0], acc[kb], 0, 0, 0);
-          acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kb][0], bq[1], acc[kb], 0, 0, 0);
-          acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kb][1], bq[0], acc[kb], 0, 0, 0);
-        }
-      }
-      if (st + 1 < ns) store(sm + ((st + 1) & 1) * BUF);
-      __syncthreads();
-    }
+    wk.product(j0, acc);
     // ---- running (max, sum) over the lane's 32 keys of this tile
     float sv[2][16], tmax = -INFINITY;
-    const bool full = j0 + XK <= Ny;
+    const bool full = j0 + PLK <= Ny;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -216,7 +154,6 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_lse_x3_kernel(const SLPX p) {
   const float m_n = fmaxf(m_run, m_o);
   float l_n = 0.f;
   if (m_n > -INFINITY) l_n = l_run * __expf(m_run - m_n) + l_o * __expf(m_o - m_n);
-  const int qg = q0 + w * 32 + li;
   if (h == 0 && qg < p.Mx) {
     float* o = p.part_ml + ((long)ks * p.Mx + qg) * 2;
     o[0] = m_n; o[1] = l_n;
@@ -378,8 +315,6 @@ __global__ __launch_bounds__(256, 2) void sinkhorn_apply_kernel(const SAP p) {
   }
 }
 
-bool shape_ok(int Mx, int Ny, int P, int pmax) { return Mx > 0 && Ny > 0 && P > 0 && !(P & 3) && P <= pmax; }
-
 size_t lse_workspace_bytes(const KeySplitPlan& k, int Mx) {
   return ((size_t)k.ksplit * Mx * 2 + (size_t)Mx) * sizeof(float);        // (m, l) partials, then the error terms
 }
@@ -402,14 +337,14 @@ int lse_finish(void* workspace, const KeySplitPlan& k, int Mx, const float* logw
 
 extern "C" int clipk_sim_lse_bias_x3_plan(int Mx, int Ny, int* nqb, int* ksplit) {
   if (Mx <= 0 || Ny <= 0 || !nqb || !ksplit) return CLIPK_ERR_BAD_ARG;
-  const KeySplitPlan k = key_split_plan(Mx, Ny, XQ);
+  const KeySplitPlan k = key_split_plan(Mx, Ny, PLQ);
   *nqb = k.nqb; *ksplit = k.ksplit;
   return CLIPK_OK;
 }
 
 extern "C" size_t clipk_sim_lse_bias_x3_workspace(int Mx, int Ny, int P) {
-  if (!shape_ok(Mx, Ny, P, LSE_PMAX)) return 0;
-  return lse_workspace_bytes(key_split_plan(Mx, Ny, XQ), Mx);
+  if (!cloud_shape_ok(Mx, Ny, P, LSE_PMAX)) return 0;
+  return lse_workspace_bytes(key_split_plan(Mx, Ny, PLQ), Mx);
 }
 
 extern "C" int clipk_sim_lse_bias_x3(const void* Xhi, const void* Xlo, int Mx, const void* Yhi, const void* Ylo, int Ny,
@@ -417,13 +352,13 @@ extern "C" int clipk_sim_lse_bias_x3(const void* Xhi, const void* Xlo, int Mx, c
                                      int average, float* out, float* err, void* workspace, size_t workspace_bytes,
                                      void* stream) {
   if (Mx <= 0 || Ny <= 0 || P <= 0) return CLIPK_ERR_BAD_ARG;
-  if (!shape_ok(Mx, Ny, P, LSE_PMAX)) return CLIPK_ERR_UNSUPPORTED;
+  if (!cloud_shape_ok(Mx, Ny, P, LSE_PMAX)) return CLIPK_ERR_UNSUPPORTED;
   if (!Xhi || !Xlo || !Yhi || !Ylo || !scale || !out || !workspace) return CLIPK_ERR_BAD_ARG;
   if ((average || err) && !prev) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(Xhi) || !aligned16(Xlo) || !aligned16(Yhi) || !aligned16(Ylo) || !aligned16(workspace))
     return CLIPK_ERR_BAD_ARG;
   if (workspace_bytes < clipk_sim_lse_bias_x3_workspace(Mx, Ny, P)) return CLIPK_ERR_BAD_ARG;
-  const KeySplitPlan k = key_split_plan(Mx, Ny, XQ);
+  const KeySplitPlan k = key_split_plan(Mx, Ny, PLQ);
   SLPX p{};
   p.xh = static_cast<const unsigned short*>(Xhi); p.xl = static_cast<const unsigned short*>(Xlo); p.Mx = Mx;
   p.yh = static_cast<const unsigned short*>(Yhi); p.yl = static_cast<const unsigned short*>(Ylo); p.Ny = Ny;
@@ -443,7 +378,7 @@ extern "C" int clipk_sim_lse_bias_plan(int Mx, int Ny, int* nqb, int* ksplit) {
 }
 
 extern "C" size_t clipk_sim_lse_bias_workspace(int Mx, int Ny, int P) {
-  if (!shape_ok(Mx, Ny, P, LSE_PMAX)) return 0;
+  if (!cloud_shape_ok(Mx, Ny, P, LSE_PMAX)) return 0;
   return lse_workspace_bytes(key_split_plan(Mx, Ny, TQ), Mx);
 }
 
@@ -451,7 +386,7 @@ extern "C" int clipk_sim_lse_bias(const float* X, int Mx, const float* Y, int Ny
                                   const float* bias, const float* logw, const float* prev, int average, float* out,
                                   float* err, void* workspace, size_t workspace_bytes, void* stream) {
   if (Mx <= 0 || Ny <= 0 || P <= 0) return CLIPK_ERR_BAD_ARG;
-  if (!shape_ok(Mx, Ny, P, LSE_PMAX)) return CLIPK_ERR_UNSUPPORTED;
+  if (!cloud_shape_ok(Mx, Ny, P, LSE_PMAX)) return CLIPK_ERR_UNSUPPORTED;
   if (!X || !Y || !scale || !out || !workspace) return CLIPK_ERR_BAD_ARG;
   if ((average || err) && !prev) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
@@ -467,7 +402,7 @@ extern "C" int clipk_sim_lse_bias(const float* X, int Mx, const float* Y, int Ny
 }
 
 extern "C" size_t clipk_sinkhorn_apply_workspace(int Mx, int Ny, int P) {
-  if (!shape_ok(Mx, Ny, P, APMAX)) return 0;
+  if (!cloud_shape_ok(Mx, Ny, P, APMAX)) return 0;
   const size_t ks = key_split_plan(Mx, Ny, TQ).ksplit;
   return ks * Mx * ((size_t)P + 2) * sizeof(float);                       // bary slabs, mass and cost partials
 }
@@ -476,7 +411,7 @@ extern "C" int clipk_sinkhorn_apply(const float* X, int Mx, const float* Y, int 
                                     const float* u, const float* v, const float* nx, const float* ny, float* mass,
                                     float* bary, float* cost, void* workspace, size_t workspace_bytes, void* stream) {
   if (Mx <= 0 || Ny <= 0 || P <= 0) return CLIPK_ERR_BAD_ARG;
-  if (!shape_ok(Mx, Ny, P, APMAX)) return CLIPK_ERR_UNSUPPORTED;
+  if (!cloud_shape_ok(Mx, Ny, P, APMAX)) return CLIPK_ERR_UNSUPPORTED;
   if (!X || !Y || !scale || !u || !v || !workspace || (!mass && !bary && !cost)) return CLIPK_ERR_BAD_ARG;
   if (cost && (!nx || !ny)) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || !aligned16(workspace) || (bary && !aligned16(bary))) return CLIPK_ERR_BAD_ARG;

@@ -20,7 +20,6 @@
 namespace {
 
 constexpr int SAMPLE_PMAX = 768;                  // contraction limit (that of the LSE pass)
-constexpr int NO_KEY = 0x7fffffff;                // loses every tie: a lane that saw no key below Ny
 
 struct SSP {
   const float* X; int Mx;
@@ -50,10 +49,6 @@ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, unsigned k0, unsigned k1
 __device__ __forceinline__ float gumbel(unsigned w) {
   const float u = (float)(2u * (w >> 9) + 1u) * 0x1p-24f;
   return -logf(-logf(u));
-}
-
-__device__ __forceinline__ void take_better(float& z, int& k, float zo, int ko) {
-  if (zo > z || (zo == z && ko < k)) { z = zo; k = ko; }
 }
 
 __global__ __launch_bounds__(256, 2) void sinkhorn_sample_kernel(const SSP p) {
@@ -119,12 +114,10 @@ __global__ __launch_bounds__(256) void sinkhorn_sample_finalize(const float* par
   if (score) score[i] = z;
 }
 
-bool shape_ok(int Mx, int Ny, int P) { return Mx > 0 && Ny > 0 && P > 0 && !(P & 3) && P <= SAMPLE_PMAX; }
-
 }  // namespace
 
 extern "C" size_t clipk_sim_sample_workspace(int Mx, int Ny, int P) {
-  if (!shape_ok(Mx, Ny, P)) return 0;
+  if (!cloud_shape_ok(Mx, Ny, P, SAMPLE_PMAX)) return 0;
   const size_t ks = key_split_plan(Mx, Ny, TQ).ksplit;
   return ks * Mx * (sizeof(float) + sizeof(int));                         // best values, then best keys
 }
@@ -133,7 +126,7 @@ extern "C" int clipk_sim_sample(const float* X, int Mx, const float* Y, int Ny, 
                                 const float* bias, const long long* seed_offset, long long* idx, float* score,
                                 void* workspace, size_t workspace_bytes, void* stream) {
   if (Mx <= 0 || Ny <= 0 || P <= 0) return CLIPK_ERR_BAD_ARG;
-  if (!shape_ok(Mx, Ny, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (!cloud_shape_ok(Mx, Ny, P, SAMPLE_PMAX)) return CLIPK_ERR_UNSUPPORTED;
   if (!X || !Y || !scale || !seed_offset || !idx || !workspace) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
   if (workspace_bytes < clipk_sim_sample_workspace(Mx, Ny, P)) return CLIPK_ERR_BAD_ARG;

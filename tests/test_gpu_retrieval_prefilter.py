@@ -90,6 +90,21 @@ def test_equals_exact_path(dev, P, kind):
     torch.cuda.empty_cache()
 
 
+@pytest.mark.parametrize("Ny", [65, 4097])               # a one-key tail tile; several key splits
+@pytest.mark.parametrize("kc", [16, 32, 64])             # the three list widths of the candidate pass
+@pytest.mark.parametrize("mode", MODES)
+def test_equals_exact_path_every_list_width(dev, mode, kc, Ny):
+    """All six candidate kernels at a ragged shape: one full query block plus one row, plane pitch 64 with a zero pad."""
+    Mq, P, k = 129, 36, kc // 2
+    g = torch.Generator(device=dev).manual_seed(kc * 7 + Ny)
+    for kind in ("random", "grid"):
+        x, y = _data(kind, Mq, Ny, P, g, dev)
+        s0, i0 = retrieval.topk(x, y, k)
+        s1, i1, st = retrieval.topk(x, y, k, prefilter=mode, candidates=kc, return_stats=True)
+        assert torch.equal(i1, i0) and torch.equal(s1, s0), (kind, mode, kc, Ny, st)
+        assert st["queries"] == Mq and st["candidates"] == kc and st["prefilter"] == mode
+
+
 def test_certified_fraction_and_fallback(dev):
     g = torch.Generator(device=dev).manual_seed(11)
     for P in (120, 512):
