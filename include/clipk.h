@@ -517,8 +517,8 @@ int clipk_linear_ce_bwd(const float* X1, int K1, const float* X2, int K2, const 
  *   workgroups when M alone does not fill the chip; the partials [split][M][5] go to the workspace and a second kernel
  *   merges them in split order.
  * bwd: the forward's kernel recomputes Z with the forward's bits and writes G to the workspace (pitch C rounded up to 4,
- *   zeros in the padding); dW and dbias are summed over row splits and 64-class groups by a kernel of clipk_linear_ce_bwd's
- *   layout and the splits are added in split order (clipk_gemm_f32 does not split its contraction, here the M rows: at
+ *   zeros in the padding); dW and dbias are summed over row splits and 64-class groups by the weight-gradient kernel that
+ *   clipk_linear_ce_bwd runs too (csrc/linear_ce_bwd.h) and the splits are added in split order (clipk_gemm_f32 does not split its contraction, here the M rows: at
  *   C = 158 it ran 24 workgroups); dX comes from clipk_gemm_f32 on G, one call per source.  The rows are processed in
  *   slabs whose G stays at 128 MiB or less (half of the Infinity Cache); dW / dbias accumulate over the slabs in slab
  *   order (record of the slab A/B: profiles/probe/README.md).

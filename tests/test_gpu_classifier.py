@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 U = 2.0 ** -24
 KSTEP = 16            # LCE_KSTEP of clip_dplm_amd/csrc/linear_ce.hip: contraction columns per main-loop step
-WCOLS = 64            # LCE_WCOLS: dW columns per wave of the weight-gradient kernel
+WCOLS = 64            # LCE_WCOLS of csrc/linear_ce_bwd.h: dW columns per wave of the weight-gradient kernel
 PAD = 64              # canary elements on each side of every output buffer
 
 SHAPES = [(1, 4, 0, 1), (37, 128, 128, 7), (64, 256, 0, 16), (65, 132, 124, 17), (257, 512, 512, 64), (1000, 36, 0, 33),
@@ -49,7 +49,8 @@ class Arena:
         return all(bool((f[:PAD] == c).all()) and bool((f[PAD + n:] == c).all()) for f, n, c in self.bufs)
 
 
-def raw_fwd(dev, x1, x2, w, b, labels, want_logits=True, ldz=None):
+def raw_fwd(dev, x1, x2, w, b, labels, want_logits=True, ldz=None, tiled=False):
+    """tiled: clipk_linear_ce_tiled_fwd on exactly its workspace bytes; it has no logits output, so three results."""
     from clip_dplm_amd import _ffi, ops
     lib = _ffi.load()
     M, K1 = x1.shape
@@ -58,39 +59,49 @@ def raw_fwd(dev, x1, x2, w, b, labels, want_logits=True, ldz=None):
     ldz = C if ldz is None else ldz
     a = Arena(dev)
     lse, tgt, pred = a.out(M), a.out(M), a.out(M, torch.int64)
-    logits = a.out(M * ldz) if want_logits else None
-    _ffi.check(lib.clipk_linear_ce_fwd(x1.data_ptr(), K1, _ffi.ptr(x2), K2, w.data_ptr(), _ffi.ptr(b), labels.data_ptr(), M, C,
-                                       lse.data_ptr(), tgt.data_ptr(), pred.data_ptr(), _ffi.ptr(logits), ldz,
-                                       ops._stream()), "clipk_linear_ce_fwd")
+    head = (x1.data_ptr(), K1, _ffi.ptr(x2), K2, w.data_ptr(), _ffi.ptr(b), labels.data_ptr(), M, C, lse.data_ptr(),
+            tgt.data_ptr(), pred.data_ptr())
+    if tiled:
+        nws = lib.clipk_linear_ce_tiled_workspace(M, K1, K2, C)
+        assert nws > 0
+        ws = a.out(nws, torch.uint8)                       # exactly the bytes the helper asks for, guard words around
+        _ffi.check(lib.clipk_linear_ce_tiled_fwd(*head, ws.data_ptr(), nws, ops._stream()), "clipk_linear_ce_tiled_fwd")
+    else:
+        logits = a.out(M * ldz) if want_logits else None
+        _ffi.check(lib.clipk_linear_ce_fwd(*head, _ffi.ptr(logits), ldz, ops._stream()), "clipk_linear_ce_fwd")
     torch.cuda.synchronize()
     assert a.intact()
+    if tiled:
+        return lse, tgt, pred
     return lse, tgt, pred, (None if logits is None else logits.view(M, ldz))
 
 
-def raw_bwd(dev, x1, x2, w, b, labels, lse, g, want_dx=True, init=None):
-    """init: (dW0, db0) to accumulate onto."""
+def raw_bwd(dev, x1, x2, w, b, labels, lse, g, want_dx=True, init=None, tiled=False, want_dw=True, want_db=True):
+    """init: (dW0, db0) to accumulate onto.  tiled: clipk_linear_ce_tiled_bwd and its workspace helper."""
     from clip_dplm_amd import _ffi, ops
     lib = _ffi.load()
     M, K1 = x1.shape
     K2 = 0 if x2 is None else x2.shape[1]
     C, K = w.shape
     a = Arena(dev)
-    dW, db = a.out(C * K), a.out(C)
+    dW = a.out(C * K) if want_dw else None
+    db = a.out(C) if want_db else None
     if init is not None:
         dW.copy_(init[0].reshape(-1))
         db.copy_(init[1])
     dx1 = a.out(M * K1) if want_dx else None
     dx2 = a.out(M * K2) if want_dx and K2 else None
-    nws = lib.clipk_linear_ce_workspace(M, K1, K2, C)
+    name = "clipk_linear_ce_tiled" if tiled else "clipk_linear_ce"
+    nws = getattr(lib, name + "_workspace")(M, K1, K2, C)
     assert nws > 0
     ws = a.out(nws, torch.uint8)                           # exactly the bytes the helper asks for, guard words around
-    _ffi.check(lib.clipk_linear_ce_bwd(x1.data_ptr(), K1, _ffi.ptr(x2), K2, w.data_ptr(), _ffi.ptr(b), labels.data_ptr(), M, C,
-                                       lse.data_ptr(), g.data_ptr(), int(init is not None), dW.data_ptr(), db.data_ptr(),
-                                       _ffi.ptr(dx1), _ffi.ptr(dx2), ws.data_ptr(), nws, ops._stream()),
-               "clipk_linear_ce_bwd")
+    _ffi.check(getattr(lib, name + "_bwd")(x1.data_ptr(), K1, _ffi.ptr(x2), K2, w.data_ptr(), _ffi.ptr(b), labels.data_ptr(), M, C,
+                                           lse.data_ptr(), g.data_ptr(), int(init is not None), _ffi.ptr(dW), _ffi.ptr(db),
+                                           _ffi.ptr(dx1), _ffi.ptr(dx2), ws.data_ptr(), nws, ops._stream()), name + "_bwd")
     torch.cuda.synchronize()
     assert a.intact()
-    return (dW.view(C, K), db, None if dx1 is None else dx1.view(M, K1), None if dx2 is None else dx2.view(M, K2))
+    return (None if dW is None else dW.view(C, K), db, None if dx1 is None else dx1.view(M, K1),
+            None if dx2 is None else dx2.view(M, K2))
 
 
 def bounds(x1, x2, w, b, labels, g):

@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 import linear_ce_ref as R
-from test_gpu_classifier import Arena, _f64_adam_losses, bounds, make, n64, raw_bwd, raw_fwd
+from test_gpu_classifier import _f64_adam_losses, bounds, make, n64, raw_bwd, raw_fwd
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -22,57 +22,13 @@ SHAPES = [(1, 4, 0, 65), (63, 36, 0, 64), (64, 32, 0, 1), (65, 132, 124, 127), (
           (257, 512, 512, 158), (33, 4092, 4, 70), (32, 1024, 0, 2547), (300, 128, 128, 2547)]
 
 
-def tiled_fwd(dev, x1, x2, w, b, labels):
-    from clip_dplm_amd import _ffi, ops
-    lib = _ffi.load()
-    M, K1 = x1.shape
-    K2 = 0 if x2 is None else x2.shape[1]
-    C = w.shape[0]
-    a = Arena(dev)
-    lse, tgt, pred = a.out(M), a.out(M), a.out(M, torch.int64)
-    nws = lib.clipk_linear_ce_tiled_workspace(M, K1, K2, C)
-    assert nws > 0
-    ws = a.out(nws, torch.uint8)                           # exactly the bytes the helper asks for, guard words around
-    _ffi.check(lib.clipk_linear_ce_tiled_fwd(x1.data_ptr(), K1, _ffi.ptr(x2), K2, w.data_ptr(), _ffi.ptr(b), labels.data_ptr(),
-                                             M, C, lse.data_ptr(), tgt.data_ptr(), pred.data_ptr(), ws.data_ptr(), nws,
-                                             ops._stream()), "clipk_linear_ce_tiled_fwd")
-    torch.cuda.synchronize()
-    assert a.intact()
-    return lse, tgt, pred
-
-
-def tiled_bwd(dev, x1, x2, w, b, labels, lse, g, init=None):
-    """init: (dW0, db0) to accumulate onto."""
-    from clip_dplm_amd import _ffi, ops
-    lib = _ffi.load()
-    M, K1 = x1.shape
-    K2 = 0 if x2 is None else x2.shape[1]
-    C, K = w.shape
-    a = Arena(dev)
-    dW, db = a.out(C * K), a.out(C)
-    if init is not None:
-        dW.copy_(init[0].reshape(-1))
-        db.copy_(init[1])
-    dx1 = a.out(M * K1)
-    dx2 = a.out(M * K2) if K2 else None
-    nws = lib.clipk_linear_ce_tiled_workspace(M, K1, K2, C)
-    ws = a.out(nws, torch.uint8)
-    _ffi.check(lib.clipk_linear_ce_tiled_bwd(x1.data_ptr(), K1, _ffi.ptr(x2), K2, w.data_ptr(), _ffi.ptr(b), labels.data_ptr(),
-                                             M, C, lse.data_ptr(), g.data_ptr(), int(init is not None), dW.data_ptr(),
-                                             db.data_ptr(), dx1.data_ptr(), _ffi.ptr(dx2), ws.data_ptr(), nws, ops._stream()),
-               "clipk_linear_ce_tiled_bwd")
-    torch.cuda.synchronize()
-    assert a.intact()
-    return dW.view(C, K), db, dx1.view(M, K1), (None if dx2 is None else dx2.view(M, K2))
-
-
 def run_tiled(dev, M, K1, K2, C, g=1.0, labels=None, seed=0):
     x1, x2, w, b, lab = make(M, K1, K2, C, seed)
     lab = lab if labels is None else labels
     d = [None if t is None else t.to(dev) for t in (x1, x2, w, b, lab)]
     gd = torch.tensor([g], dtype=torch.float32, device=dev)
-    fw = tiled_fwd(dev, *d)
-    bw = tiled_bwd(dev, *d, fw[0], gd)
+    fw = raw_fwd(dev, *d, tiled=True)
+    bw = raw_bwd(dev, *d, fw[0], gd, tiled=True)
     return (x1, x2, w, b, lab), d, gd, fw, bw
 
 
@@ -127,7 +83,7 @@ def test_ties_resolve_to_the_lower_class_across_tiles_and_splits(dev):
     lab = torch.randint(0, C, (M,), generator=g)
     z = R.logits(x.numpy(), w.numpy(), b.numpy())
     assert np.array_equal(z, z.astype(np.float32)) and np.array_equal(z[:, 3], z[:, 67]) and np.array_equal(z[:, 3], z[:, 130])
-    lse, tgt, pred = tiled_fwd(dev, x.to(dev), None, w.to(dev), b.to(dev), lab.to(dev))
+    lse, tgt, pred = raw_fwd(dev, x.to(dev), None, w.to(dev), b.to(dev), lab.to(dev), tiled=True)
     p = pred.cpu().numpy()
     assert np.array_equal(p, R.first_argmax(z))
     assert (p == 3).sum() > 5 and not ((p == 67) | (p == 130)).any()
@@ -164,7 +120,7 @@ def test_accumulate_and_determinism(dev):
     # accumulate: buffer + fresh result, one rounding of the sum (1 ulp); dX is not touched by the flag
     g0 = torch.Generator().manual_seed(5)
     dW0, db0 = torch.randn(C, K1 + K2, generator=g0).to(dev), torch.randn(C, generator=g0).to(dev)
-    bw3 = tiled_bwd(dev, *d, fw[0], gd, init=(dW0, db0))
+    bw3 = raw_bwd(dev, *d, fw[0], gd, init=(dW0, db0), tiled=True)
     for got, base, fresh in ((bw3[0], dW0, bw[0]), (bw3[1], db0, bw[1])):
         want = base.double() + fresh.double()
         ulp = torch.maximum(want.abs(), torch.tensor(2.0 ** -126, dtype=torch.float64, device=dev)) * 2.0 ** -23
@@ -201,16 +157,29 @@ def test_backward_over_two_row_slabs_at_the_class_limit(dev):
     assert (~sure).sum() <= 0.10 * M and np.array_equal(pred.cpu().numpy()[sure], r_pred[sure])
     assert dx1[512:].any() and db.any()                      # the second slab did write
     # a second call has the same bits
-    bw2 = tiled_bwd(dev, *d, lse, gd)
+    bw2 = raw_bwd(dev, *d, lse, gd, tiled=True)
     assert torch.equal(bw2[0], dW) and torch.equal(bw2[1], db) and torch.equal(bw2[2], dx1)
     # accumulate over two slabs is fl(fl(base + s1) + s2) against base + fl(s1 + s2): three roundings of at most u times
     # |base + s1|, |result| and |s1 + s2|, each below |base| + A with A = sum_i |G x| >= |s1| + |s2|
     g0 = torch.Generator().manual_seed(6)
     dW0, db0 = torch.randn(C, K1, generator=g0).to(dev), torch.randn(C, generator=g0).to(dev)
-    bw3 = tiled_bwd(dev, *d, lse, gd, init=(dW0, db0))
+    bw3 = raw_bwd(dev, *d, lse, gd, init=(dW0, db0), tiled=True)
     for got, base, fresh, A in ((bw3[0], dW0, dW, np.abs(rG).T @ np.abs(a[0])), (bw3[1], db0, db, np.abs(rG).sum(axis=0))):
         tol = 3.0 * U * 1.001 * (np.abs(n64(base)) + A)
         assert (np.abs(n64(got) - (n64(base) + n64(fresh))) <= tol).all()
+
+
+def test_each_output_alone_has_the_bits_of_the_full_call(dev):
+    """dW only, dbias only, dX only: the weight-gradient kernel's null-partials branches.  Nothing is atomic, so each
+    output has the bits it has when every output is asked for (canaries inside raw_bwd)."""
+    _, d, gd, fw, (dW, db, dx1, dx2) = run_tiled(dev, 65, 132, 124, 127, 0.75)
+    only = lambda **kw: raw_bwd(dev, *d, fw[0], gd, tiled=True, **kw)
+    o = only(want_db=False, want_dx=False)
+    assert torch.equal(o[0], dW) and o[1] is None and o[2] is None and o[3] is None
+    o = only(want_dw=False, want_dx=False)
+    assert torch.equal(o[1], db) and o[0] is None and o[2] is None and o[3] is None
+    o = only(want_dw=False, want_db=False)
+    assert torch.equal(o[2], dx1) and torch.equal(o[3], dx2) and o[0] is None and o[1] is None
 
 
 @pytest.mark.parametrize("C", [17, 64])

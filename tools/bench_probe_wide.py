@@ -8,7 +8,7 @@ two fused entries are also timed alone (dW and dbias, no dX: frozen inputs), wit
 computed from the shapes (CP = C padded to the 64-class tile):
 
     forward   MFMA flop = 2 M K CP
-    backward  MFMA flop = 2 M K (CP + C)     (Z again in the tiles, then G^T X in lcet_wgrad_kernel)
+    backward  MFMA flop = 2 M K (CP + C)     (Z again in the tiles, then G^T X in lce_wgrad_kernel<4, true>)
 
     python tools/bench_probe_wide.py --out profiles/probe/bench_probe_wide.jsonl
     python tools/bench_probe_wide.py --lib build_alt/libclipk.so --arms bwd --shapes 131072,1024,2547   # another build
