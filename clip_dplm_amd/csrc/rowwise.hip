@@ -168,6 +168,15 @@ struct LnPool {
   int L, cols;
 };
 
+// wave sums of one running sum, or of four segment sums combined as ln_fwd_wide_kernel combines its four waves' sums
+template <int NS>
+__device__ __forceinline__ float segment_total(float (&a)[NS]) {
+#pragma unroll
+  for (int w = 0; w < NS; ++w) a[w] = wave_sum(a[w]);
+  if constexpr (NS == 4) return (a[0] + a[1]) + (a[2] + a[3]);
+  else return a[0];
+}
+
 template <int VPL, bool XBF16>
 __global__ __launch_bounds__(256) void ln_pool_fwd_kernel(const LnPool p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -190,25 +199,28 @@ __global__ __launch_bounds__(256) void ln_pool_fwd_kernel(const LnPool p) {
   for (int l = wid; l < p.L; l += 4) {
     const long row = (long)b * p.L + l;
     f32x4 x[VPL];
-    float s = 0.f;
+    // same statistics arithmetic as clipk_layernorm_fwd at this width, so that mean / rstd are ITS bits: one running sum
+    // (ln_fwd_kernel), or beyond 2048 columns (VPL 20) the four interleaved segment sums of ln_fwd_wide_kernel - chunk
+    // lane + 64 (4 v + w) belongs to that kernel's wave w - combined pairwise
+    constexpr int NS = VPL == 20 ? 4 : 1;
+    float s[NS] = {}, q[NS] = {};
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
       const int c = lane + 64 * v;
       x[v] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (c < nch) x[v] = load4<XBF16>(p.x, row * p.ldx + 4 * c);
-      s += (x[v][0] + x[v][1]) + (x[v][2] + x[v][3]);
+      s[v % NS] += (x[v][0] + x[v][1]) + (x[v][2] + x[v][3]);
     }
-    const float mean = wave_sum(s) * inv_n;                      // same statistics arithmetic as ln_fwd_kernel
-    float q = 0.f;
+    const float mean = segment_total(s) * inv_n;
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
       const int c = lane + 64 * v;
       if (c < nch) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = x[v][e] - mean; q += d * d; }
+        for (int e = 0; e < 4; ++e) { const float d = x[v][e] - mean; q[v % NS] += d * d; }
       }
     }
-    const float rstd = rsqrtf(wave_sum(q) * inv_n + p.eps);
+    const float rstd = rsqrtf(segment_total(q) * inv_n + p.eps);
     if (lane == 0) { p.mean[row] = mean; p.rstd[row] = rstd; }
     const bool ok = !p.mask || p.mask[row];                      // wave-uniform
     if (ok) {

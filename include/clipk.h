@@ -630,8 +630,9 @@ int clipk_layernorm_bwd2(const float* g, const float* dy, const float* a, int64_
  * mean_{l valid} LN(x[b, l]) (the pooling of run1/configuration_hybrid_clip.py:109,148 `use_mean_pooling`, fair-esm
  * mean over residues current/tf_clip_codes (1).ipynb:1188, behind the encoders' last LayerNorm modeling_esm.py:552-553 /
  * rna_clip_codes.ipynb:1923).  The normalised rows are never written.  x f32 or bf16 [B*L, cols], mask u8 [B*L] (1 = valid) or
- * NULL; outputs pooled f32 [B, cols], mean / rstd f32 [B*L] (for the backward), row_weight f32 [B*L] = the row's weight in
- * its sample's mean (1 / #valid rows, 0 for a masked row or an empty sample).
+ * NULL; outputs pooled f32 [B, cols], mean / rstd f32 [B*L] (for the backward; the bits clipk_layernorm_fwd gives for the
+ * same rows, at every width), row_weight f32 [B*L] = the row's weight in its sample's mean (1 / #valid rows, 0 for a masked
+ * row or an empty sample).
  * Backward: row r gets dy = dpooled[r / L] * row_weight[r] and goes through the LayerNorm backward
  * (outputs / workspace / dgamma / dbeta as clipk_layernorm_bwd, workspace size clipk_layernorm_bwd_workspace(B*L, cols)). */
 int clipk_layernorm_meanpool_fwd(const void* x, int x_dtype, int64_t ldx, const float* gamma, const float* beta, float eps,
