@@ -2365,12 +2365,8 @@ int check_common(const void* qkv, int B, int L, int H, int D, bool rope) {
 
 static inline int set_dropout(AP& p, float dropout_p, unsigned seed) {
   if (!(dropout_p >= 0.f) || dropout_p >= 1.f) return CLIPK_ERR_BAD_ARG;
-  p.drop_epoch = clipk_drop_epoch();
-  if (dropout_p == 0.f) { p.drop_thr = 0; p.drop_seed = 0; p.drop_scale = 1.f; return CLIPK_OK; }
-  double t = (double)dropout_p * 4294967296.0;
-  p.drop_thr = t < 1.0 ? 1u : (t >= 4294967295.0 ? 4294967295u : (unsigned)t);
-  p.drop_seed = seed;
-  p.drop_scale = 1.0f / (1.0f - dropout_p);
+  const DropParams d = drop_params(dropout_p);
+  p.drop_thr = d.thr; p.drop_seed = d.thr ? seed : 0; p.drop_scale = d.scale; p.drop_epoch = clipk_drop_epoch();
   return CLIPK_OK;
 }
 

@@ -235,6 +235,14 @@ __device__ __forceinline__ unsigned drop_seed_eff(unsigned seed, const unsigned*
   return epoch ? seed + epoch[0] * 0x9E3779B9u : seed;
 }
 const unsigned* clipk_drop_epoch();                      // host side: the registered pointer or nullptr (core.hip)
+// host side: drop_keep's threshold p * 2^32 (never 0 for p > 0, nor 2^32) and the survivors' scale 1 / (1 - p) in f32;
+// p outside (0, 1) is no dropout: thr 0, scale 1 (each entry point refuses what it does not take before it asks)
+struct DropParams { unsigned thr; float scale; };
+static inline DropParams drop_params(float p) {
+  if (!(p > 0.f && p < 1.f)) return {0u, 1.0f};
+  const double t = (double)p * 4294967296.0;
+  return {t < 1.0 ? 1u : (t >= 4294967295.0 ? 4294967295u : (unsigned)t), 1.0f / (1.0f - p)};
+}
 
 // ---- pair-interleaved head order (round 4: RoPE of the hd-24 ESM heads in the qkv GEMM's epilogue).  The first il_rows
 // output columns of a fused [q | k | v] projection (the q and k sections) are computed in an order in which the two

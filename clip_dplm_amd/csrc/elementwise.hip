@@ -539,10 +539,9 @@ extern "C" int clipk_axpby_dev(const float* a, const float* b, const float* s, f
 extern "C" int clipk_dropout_f32(const float* x, const float* addend, float* y, int64_t n, float p, uint32_t seed,
                                  void* stream) {
   if (!x || !y || n <= 0 || !(p >= 0.f) || p >= 1.f) return CLIPK_ERR_BAD_ARG;
-  const double t = (double)p * 4294967296.0;
-  const unsigned thr = p == 0.f ? 0u : (t < 1.0 ? 1u : (t >= 4294967295.0 ? 4294967295u : (unsigned)t));
+  const DropParams d = drop_params(p);
   hipLaunchKernelGGL(dropout_f32_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, (hipStream_t)stream, x, addend, y,
-                     (long)n, thr, seed, 1.0f / (1.0f - p), clipk_drop_epoch());
+                     (long)n, d.thr, seed, d.scale, clipk_drop_epoch());
   return clipk_check_launch();
 }
 

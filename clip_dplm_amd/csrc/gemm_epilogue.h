@@ -505,11 +505,7 @@ static inline EpiArgs epi_args_from(const clipk_gemm_args* a) {
   e.nt = clipk_opt_get(OPT_EPI_NT);
   e.rope_cos = a->rope_cos; e.rope_sin = a->rope_sin; e.rope_L = a->rope_L; e.rope_hd = a->rope_hd;
   e.rope_cols = a->rope_cols; e.rope_row0 = a->rope_row0;
-  e.drop_thr = 0; e.drop_seed = a->drop_seed; e.drop_scale = 1.f; e.drop_epoch = clipk_drop_epoch();
-  if (a->drop_p > 0.f && a->drop_p < 1.f) {
-    const double t = (double)a->drop_p * 4294967296.0;
-    e.drop_thr = t < 1.0 ? 1u : (t >= 4294967295.0 ? 4294967295u : (unsigned)t);
-    e.drop_scale = 1.0f / (1.0f - a->drop_p);
-  }
+  const DropParams d = drop_params(a->drop_p);
+  e.drop_thr = d.thr; e.drop_seed = a->drop_seed; e.drop_scale = d.scale; e.drop_epoch = clipk_drop_epoch();
   return e;
 }

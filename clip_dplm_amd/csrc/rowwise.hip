@@ -1,6 +1,7 @@
 // rowwise.hip — HBM-bound row kernels: LayerNorm fwd/bwd (+fused activation), L2-normalise fwd/bwd.
 // One wave (64 lanes) per row, whole row held in registers as 4-element chunks (16-byte f32 loads,
-// 8-byte bf16 loads), f32 statistics with wave-shuffle reductions — no LDS, no re-reads.
+// 8-byte bf16 loads), f32 statistics with wave-shuffle reductions — no LDS, no re-reads; beyond 2048 columns the
+// LayerNorm forward and its all-f32 backward give a row to a whole workgroup (RowGeom below).
 // Reference ops: nn.LayerNorm at old/clip.py:12,28,32, the LayerNorms inside nn.TransformerEncoderLayer
 // (rna_clip_codes.ipynb:1915-1916) and EsmLayer (modeling_esm.py:429-438,552-553); F.normalize at
 // old/clip.py:63-64.
@@ -25,6 +26,170 @@ __device__ __forceinline__ void store4_bf16(void* base, long off, f32x4 v) {
   *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(base) + off) = o;
 }
 
+__device__ __forceinline__ float sum4(float a, float b, float c, float d) { return (a + b) + (c + d); }
+
+// ---- row geometry: NW waves share a row ------------------------------------------------------------
+// NW = 1: a wave per row, four rows per block, lane l holds the chunks l + 64 v.  NW = 4 (wide rows, cols > 2048: the
+// 2560-wide hidden LayerNorms of the notebook's projection heads, rna_clip_codes.ipynb:1887-1903): a WORKGROUP per row,
+// the four waves take interleaved 256-float segments (chunk = lane + 64 (4 v + wave)) and row sums meet in LDS.  The
+// one-wave form needs 20 float4 per lane and array there (560 registers in the backward: it lived in scratch, 48 us
+// for 32 rows).  A row's arithmetic depends on NW and the width only, never on the batch.
+template <int NW>
+struct RowGeom {
+  static_assert(NW == 1 || NW == 4, "a wave or a 256-thread workgroup per row");
+  // ---- the geometry itself, stateless (lane: of its wave, wid: the wave of its block)
+  __device__ __forceinline__ static int chunk(int lane, int wid, int v) {
+    return NW == 1 ? lane + 64 * v : lane + 64 * (NW * v + wid);
+  }
+  // the grid-stride walk over rows: a kernel's waves (NW = 1) or blocks (NW = 4).  block_threads: blockDim.x, read in the
+  // kernel itself - there the compiler knows that no workgroup of the grid is a partial one; read in a device function it
+  // costs a compare and a select on the block index per use
+  __device__ __forceinline__ static int first_row(unsigned block_threads) {
+    return NW == 1 ? (blockIdx.x * block_threads + threadIdx.x) >> 6 : blockIdx.x;
+  }
+  __device__ __forceinline__ static int row_step(unsigned block_threads) {
+    return NW == 1 ? (gridDim.x * block_threads) >> 6 : gridDim.x;
+  }
+  // The mean of a row quantity from every lane's partial sum: wave shuffles, and for NW = 4 one float per wave in LDS
+  // slot 0 or 1, added as (w0 + w1) + (w2 + w3).  One barrier: a caller alternates the slots, so every wave has read a
+  // slot's last sums before anyone passes the barrier behind which it is written again.
+  __device__ __forceinline__ static float* red(int slot) {
+    __shared__ float r[2][4];
+    return r[slot];
+  }
+  __device__ __forceinline__ static float row_mean(int lane, int wid, float s, float inv_n, int slot) {
+    s = wave_sum(s);
+    if constexpr (NW == 4) {
+      float* r = red(slot);
+      if (lane == 0) r[wid] = s;
+      __syncthreads();
+      s = sum4(r[0], r[1], r[2], r[3]);
+    }
+    return s * inv_n;
+  }
+  // Two at once, both slots every row: a second barrier, "the previous row's sums have been read by every wave"
+  __device__ __forceinline__ static void row_means(int lane, int wid, float& a, float& b, float inv_n) {
+    if constexpr (NW == 4) {
+      a = wave_sum(a); b = wave_sum(b);
+      float *r0 = red(0), *r1 = red(1);
+      __syncthreads();
+      if (lane == 0) { r0[wid] = a; r1[wid] = b; }
+      __syncthreads();
+      a = sum4(r0[0], r0[1], r0[2], r0[3]) * inv_n;
+      b = sum4(r1[0], r1[1], r1[2], r1[3]) * inv_n;
+    } else {
+      a = wave_sum(a) * inv_n;
+      b = wave_sum(b) * inv_n;
+    }
+  }
+
+  // ---- one thread's view of it, for the kernels that hand it to the helpers below.  (ln_bwd_kernel uses the static
+  // functions with locals of its own: with an object its NW = 1 forms order their address arithmetic differently from the
+  // parent's, profiles/ln_fold/README.md.)
+  const int lane, wid;
+  const unsigned block_threads;
+  const int row0, step;
+  __device__ __forceinline__ explicit RowGeom(unsigned block_dim_x)
+      : lane(threadIdx.x & 63), wid(threadIdx.x >> 6), block_threads(block_dim_x),
+        row0(first_row(block_dim_x)), step(row_step(block_dim_x)) {}
+  __device__ __forceinline__ int chunk(int v) const { return chunk(lane, wid, v); }
+  __device__ __forceinline__ bool row_leader() const { return NW == 1 ? lane == 0 : threadIdx.x == 0; }
+  __device__ __forceinline__ float row_mean(float s, float inv_n, int slot) const { return row_mean(lane, wid, s, inv_n, slot); }
+  // One row sum kept as NS segment sums.  NS = 4 is a lone wave walking a wide row (NW = 1): its chunk v is the NW = 4
+  // geometry's chunk v / 4 of wave v % 4, so segment v % 4 adds what that wave adds, in its order, and the four
+  // segment totals are added as the one-sum row_mean adds the four waves' - the bits of the NW = 4 mean.
+  template <int NS>
+  __device__ __forceinline__ float row_mean(const float (&s)[NS], float inv_n, int slot) const {
+    static_assert(NS == 1 || (NS == 4 && NW == 1), "segments stand in for the waves of the NW = 4 form");
+    if constexpr (NS == 4) return sum4(wave_sum(s[0]), wave_sum(s[1]), wave_sum(s[2]), wave_sum(s[3])) * inv_n;
+    else return row_mean(s[0], inv_n, slot);
+  }
+};
+
+// the waves that share a row of VPL-wide chunk arrays in clipk_layernorm_fwd: what launches its kernel, and what
+// ln_pool_fwd_kernel sums its segments by so that mean / rstd are that entry's bits
+constexpr int ln_fwd_row_waves(int vpl) { return vpl == 20 ? 4 : 1; }
+
+// gamma and (want_beta) beta chunks of this lane, zero beyond the row's end
+template <int V, int NW>
+__device__ __forceinline__ void ln_load_params(const RowGeom<NW> t, int nch, const float* gamma, const float* beta,
+                                               bool want_beta, f32x4 (&g)[V], f32x4 (&b)[V]) {
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const int c = t.chunk(v);
+    g[v] = f32x4{0.f, 0.f, 0.f, 0.f}; b[v] = g[v];
+    if (c < nch) {
+      g[v] = *reinterpret_cast<const f32x4*>(gamma + 4 * c);
+      if (want_beta) b[v] = *reinterpret_cast<const f32x4*>(beta + 4 * c);
+    }
+  }
+}
+
+// A row into registers (zeros beyond its end) with its two-pass mean and rstd, the sums in NS segments (RowGeom::row_mean)
+template <bool XBF16, int NS, int V, int NW>
+__device__ __forceinline__ void ln_load_row_stats(const RowGeom<NW> t, int nch, const void* xp, long rowoff, float inv_n,
+                                                  float eps, f32x4 (&x)[V], float& mean, float& rstd) {
+  float s[NS] = {}, q[NS] = {};
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const int c = t.chunk(v);
+    f32x4 xv = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (c < nch) xv = load4<XBF16>(xp, rowoff + 4 * c);
+    s[NS == 1 ? 0 : v % NS] += (xv[0] + xv[1]) + (xv[2] + xv[3]);
+    x[v] = xv;
+  }
+  mean = t.row_mean(s, inv_n, 0);
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    if (t.chunk(v) < nch) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const float d = x[v][e] - mean; q[NS == 1 ? 0 : v % NS] += d * d; }
+    }
+  }
+  const float var = t.row_mean(q, inv_n, 1);   // (slot 1: every wave has read slot 0 before the next row's barrier)
+  rstd = rsqrtf(var + eps);
+}
+
+// This block's dgamma / dbeta partial row part[blockIdx.x][2][cols], NW = 4: every wave writes its own columns
+template <int V>
+__device__ __forceinline__ void ln_partials_direct(int lane, int wid, int cols, const f32x4 (&dg)[V], const f32x4 (&db)[V],
+                                                   float* part) {
+  const int nch = cols >> 2;
+  float* out = part + (long)blockIdx.x * 2 * cols;
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const int c = RowGeom<4>::chunk(lane, wid, v);
+    if (c < nch) {
+      *reinterpret_cast<f32x4*>(out + 4 * c) = dg[v];
+      *reinterpret_cast<f32x4*>(out + cols + 4 * c) = db[v];
+    }
+  }
+}
+
+// ... NW = 1: the four waves hold partials of the same columns, combined through dynamic LDS [4][2][cols]
+template <int V>
+__device__ __forceinline__ void ln_partials_through_lds(const RowGeom<1> t, int cols, const f32x4 (&dg)[V],
+                                                        const f32x4 (&db)[V], float* part) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sm = reinterpret_cast<float*>(smem);          // [4][2][cols]
+  const int nch = cols >> 2;
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const int c = t.chunk(v);
+    if (c < nch) {
+      *reinterpret_cast<f32x4*>(sm + (t.wid * 2 + 0) * cols + 4 * c) = dg[v];
+      *reinterpret_cast<f32x4*>(sm + (t.wid * 2 + 1) * cols + 4 * c) = db[v];
+    }
+  }
+  __syncthreads();
+  const int nw = t.block_threads >> 6;
+  for (int i = threadIdx.x; i < 2 * cols; i += t.block_threads) {
+    float a = 0.f;
+    for (int w = 0; w < nw; ++w) a += sm[w * 2 * cols + i];
+    part[(long)blockIdx.x * 2 * cols + i] = a;
+  }
+}
+
 struct LnFwd {
   const void* x; long ldx;
   const float* gamma; const float* beta; float eps; int act;
@@ -32,118 +197,51 @@ struct LnFwd {
   float* mean; float* rstd; int rows, cols;
 };
 
-template <int VPL, bool XBF16>
+// f32 or bf16 in, f32 and / or bf16 out
+template <int V, int NW, bool XBF16>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwd p) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  const RowGeom<NW> t(blockDim.x);
   const int nch = p.cols >> 2;
-  f32x4 g[VPL], b[VPL];
-#pragma unroll
-  for (int v = 0; v < VPL; ++v) {
-    const int c = lane + 64 * v;
-    g[v] = f32x4{0.f, 0.f, 0.f, 0.f}; b[v] = g[v];
-    if (c < nch) {
-      g[v] = *reinterpret_cast<const f32x4*>(p.gamma + 4 * c);
-      b[v] = *reinterpret_cast<const f32x4*>(p.beta + 4 * c);
-    }
-  }
+  f32x4 g[V], b[V];
+  ln_load_params(t, nch, p.gamma, p.beta, true, g, b);
   const float inv_n = 1.0f / (float)p.cols;
-  for (int row = wave; row < p.rows; row += nwaves) {
-    f32x4 x[VPL];
-    float s = 0.f;
+  for (int row = t.row0; row < p.rows; row += t.step) {
+    f32x4 x[V];
+    float mean, rstd;
+    if constexpr (NW == 1 && !XBF16) {
+      // ln_load_row_stats<false, 1> spelled out: behind the call (the row array passed by reference) the three f32
+      // instantiations allocate 66 / 92 / 140 registers instead of 64 / 90 / 138, and 66 is 7 waves per SIMD instead
+      // of 8 at the 480-wide rows (profiles/ln_fold/README.md).  Same operations in the same order.
+      float s = 0.f;
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
-      x[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (c < nch) x[v] = load4<XBF16>(p.x, (long)row * p.ldx + 4 * c);
-      s += (x[v][0] + x[v][1]) + (x[v][2] + x[v][3]);
-    }
-    const float mean = wave_sum(s) * inv_n;
-    float q = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
-      if (c < nch) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = x[v][e] - mean; q += d * d; }
+      for (int v = 0; v < V; ++v) {
+        const int c = t.chunk(v);
+        x[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < nch) x[v] = load4<XBF16>(p.x, (long)row * p.ldx + 4 * c);
+        s += (x[v][0] + x[v][1]) + (x[v][2] + x[v][3]);
       }
+      mean = wave_sum(s) * inv_n;
+      float q = 0.f;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        const int c = t.chunk(v);
+        if (c < nch) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { const float d = x[v][e] - mean; q += d * d; }
+        }
+      }
+      const float var = wave_sum(q) * inv_n;
+      rstd = rsqrtf(var + p.eps);
+    } else {
+      ln_load_row_stats<XBF16, 1>(t, nch, p.x, (long)row * p.ldx, inv_n, p.eps, x, mean, rstd);
     }
-    const float var = wave_sum(q) * inv_n;
-    const float rstd = rsqrtf(var + p.eps);
-    if (lane == 0) {
+    if (t.row_leader()) {
       if (p.mean) p.mean[row] = mean;
       if (p.rstd) p.rstd[row] = rstd;
     }
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
-      if (c < nch) {
-        f32x4 y;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = act_apply((x[v][e] - mean) * rstd * g[v][e] + b[v][e], p.act);
-        if (p.y_f32) *reinterpret_cast<f32x4*>(p.y_f32 + (long)row * p.ldy + 4 * c) = y;
-        if (p.y_bf16) store4_bf16(p.y_bf16, (long)row * p.ldy + 4 * c, y);
-      }
-    }
-  }
-}
-
-// Wide rows (cols > 2048: the 2560-wide hidden LayerNorms of the notebook's projection heads, rna_clip_codes.ipynb:1887-1903):
-// one WORKGROUP per row, the four waves take interleaved 256-float segments (chunk = lane + 64 (4 v + wave)), row sums meet
-// in LDS.  The one-wave-per-row form needs 20 float4 per lane and array (560 registers in the backward: it lived in scratch,
-// 48 us for 32 rows).  f32 in / f32 or bf16 out like the narrow kernel; the row statistics are sums of four wave sums.
-template <int VPW, bool XBF16>
-__global__ __launch_bounds__(256) void ln_fwd_wide_kernel(const LnFwd p) {
-  __shared__ float red[2][4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int nch = p.cols >> 2;
-  f32x4 g[VPW], b[VPW];
-#pragma unroll
-  for (int v = 0; v < VPW; ++v) {
-    const int c = lane + 64 * (4 * v + wid);
-    g[v] = f32x4{0.f, 0.f, 0.f, 0.f}; b[v] = g[v];
-    if (c < nch) {
-      g[v] = *reinterpret_cast<const f32x4*>(p.gamma + 4 * c);
-      b[v] = *reinterpret_cast<const f32x4*>(p.beta + 4 * c);
-    }
-  }
-  const float inv_n = 1.0f / (float)p.cols;
-  for (int row = blockIdx.x; row < p.rows; row += gridDim.x) {
-    f32x4 x[VPW];
-    float s = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPW; ++v) {
-      const int c = lane + 64 * (4 * v + wid);
-      x[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (c < nch) x[v] = load4<XBF16>(p.x, (long)row * p.ldx + 4 * c);
-      s += (x[v][0] + x[v][1]) + (x[v][2] + x[v][3]);
-    }
-    s = wave_sum(s);
-    if (lane == 0) red[0][wid] = s;
-    __syncthreads();
-    const float mean = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * inv_n;
-    float q = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPW; ++v) {
-      const int c = lane + 64 * (4 * v + wid);
-      if (c < nch) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = x[v][e] - mean; q += d * d; }
-      }
-    }
-    q = wave_sum(q);
-    if (lane == 0) red[1][wid] = q;
-    __syncthreads();                       // (also: every wave has read red[0] before the next row overwrites it)
-    const float var = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) * inv_n;
-    const float rstd = rsqrtf(var + p.eps);
-    if (threadIdx.x == 0) {
-      if (p.mean) p.mean[row] = mean;
-      if (p.rstd) p.rstd[row] = rstd;
-    }
-#pragma unroll
-    for (int v = 0; v < VPW; ++v) {
-      const int c = lane + 64 * (4 * v + wid);
+    for (int v = 0; v < V; ++v) {
+      const int c = t.chunk(v);
       if (c < nch) {
         f32x4 y;
 #pragma unroll
@@ -168,20 +266,11 @@ struct LnPool {
   int L, cols;
 };
 
-// wave sums of one running sum, or of four segment sums combined as ln_fwd_wide_kernel combines its four waves' sums
-template <int NS>
-__device__ __forceinline__ float segment_total(float (&a)[NS]) {
-#pragma unroll
-  for (int w = 0; w < NS; ++w) a[w] = wave_sum(a[w]);
-  if constexpr (NS == 4) return (a[0] + a[1]) + (a[2] + a[3]);
-  else return a[0];
-}
-
 template <int VPL, bool XBF16>
 __global__ __launch_bounds__(256) void ln_pool_fwd_kernel(const LnPool p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sm = reinterpret_cast<float*>(smem);                    // [4][cols] partial sums, then [4] counts
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;     // a wave per row, whatever the width
   const int b = blockIdx.x;
   const int nch = p.cols >> 2;
   f32x4 g[VPL], be[VPL], acc[VPL];
@@ -199,28 +288,33 @@ __global__ __launch_bounds__(256) void ln_pool_fwd_kernel(const LnPool p) {
   for (int l = wid; l < p.L; l += 4) {
     const long row = (long)b * p.L + l;
     f32x4 x[VPL];
-    // same statistics arithmetic as clipk_layernorm_fwd at this width, so that mean / rstd are ITS bits: one running sum
-    // (ln_fwd_kernel), or beyond 2048 columns (VPL 20) the four interleaved segment sums of ln_fwd_wide_kernel - chunk
-    // lane + 64 (4 v + w) belongs to that kernel's wave w - combined pairwise
-    constexpr int NS = VPL == 20 ? 4 : 1;
-    float s[NS] = {}, q[NS] = {};
+    float mean, rstd;
+    constexpr int NS = ln_fwd_row_waves(VPL);
+    if constexpr (NS == 1) {
+      // ln_load_row_stats<XBF16, 1> spelled out: behind the call the VPL 2 / 4 / 8 forms allocate 60 / 94 / 408 registers
+      // instead of 58 / 92 / 404; with it, the preamble above and no RowGeom object they are the parent's instruction
+      // stream (profiles/ln_fold/README.md).  Same operations in the same order.
+      float s[NS] = {}, q[NS] = {};
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
-      x[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (c < nch) x[v] = load4<XBF16>(p.x, row * p.ldx + 4 * c);
-      s[v % NS] += (x[v][0] + x[v][1]) + (x[v][2] + x[v][3]);
-    }
-    const float mean = segment_total(s) * inv_n;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
-      if (c < nch) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = x[v][e] - mean; q[v % NS] += d * d; }
+      for (int v = 0; v < VPL; ++v) {
+        const int c = lane + 64 * v;
+        x[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < nch) x[v] = load4<XBF16>(p.x, row * p.ldx + 4 * c);
+        s[v % NS] += (x[v][0] + x[v][1]) + (x[v][2] + x[v][3]);
       }
+      mean = wave_sum(s[0]) * inv_n;
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) {
+        const int c = lane + 64 * v;
+        if (c < nch) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { const float d = x[v][e] - mean; q[v % NS] += d * d; }
+        }
+      }
+      rstd = rsqrtf(wave_sum(q[0]) * inv_n + p.eps);
+    } else {     // beyond 2048 columns: the four segment sums of the forward's NW = 4 form
+      ln_load_row_stats<XBF16, NS>(RowGeom<1>(blockDim.x), nch, p.x, row * p.ldx, inv_n, p.eps, x, mean, rstd);
     }
-    const float rstd = rsqrtf(segment_total(q) * inv_n + p.eps);
     if (lane == 0) { p.mean[row] = mean; p.rstd[row] = rstd; }
     const bool ok = !p.mask || p.mask[row];                      // wave-uniform
     if (ok) {
@@ -268,17 +362,22 @@ struct LnBwd {
   const unsigned* drop_epoch;   // common.h drop_seed_eff (last member: the aggregate initialisers below leave it nullptr)
 };
 
-template <int VPL, bool DYBF16, bool XBF16, bool ADD16 = false, bool POOL = false>
+// NW = 4 (launch_ln_bwd: f32 dy / x beyond 2048 columns): two barriers per row, none for the partial row.
+// The kernel keeps lane / wid / the row walk as locals over RowGeom's static functions, and its preamble and NW = 1 tail are
+// ln_load_params and ln_partials_through_lds spelled out: so built, every NW = 1 instantiation is the parent's instruction
+// stream.  With a RowGeom object they order their address arithmetic differently; with the two helper calls (four arrays
+// passed by reference) the VPL 8 forms allocate up to 275 registers instead of 271 and the VPL 20 forms spill 8 to 24 B more
+// per lane (profiles/ln_fold/README.md).
+template <int V, int NW, bool DYBF16, bool XBF16, bool ADD16 = false, bool POOL = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwd p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  using G = RowGeom<NW>;
+  const int row0 = G::first_row(blockDim.x), row_step = G::row_step(blockDim.x);
   const int nch = p.cols >> 2;
-  f32x4 g[VPL], b[VPL], dg[VPL], db[VPL];
+  f32x4 g[V], b[V], dg[V], db[V];
 #pragma unroll
-  for (int v = 0; v < VPL; ++v) {
-    const int c = lane + 64 * v;
+  for (int v = 0; v < V; ++v) {
+    const int c = G::chunk(lane, wid, v);
     g[v] = f32x4{0.f, 0.f, 0.f, 0.f}; b[v] = g[v]; dg[v] = g[v]; db[v] = g[v];
     if (c < nch) {
       g[v] = *reinterpret_cast<const f32x4*>(p.gamma + 4 * c);
@@ -286,9 +385,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwd p) {
     }
   }
   const float inv_n = 1.0f / (float)p.cols;
-  for (int row = wave; row < p.rows; row += nwaves) {
+  for (int row = row0; row < p.rows; row += row_step) {
     const float mean = p.mean[row], rstd = p.rstd[row];
-    f32x4 xh[VPL], gy[VPL], addv[VPL];
+    f32x4 xh[V], gy[V], addv[V];
     float s1 = 0.f, s2 = 0.f;
     long dyrow = row;
     float pw = 1.f;
@@ -298,10 +397,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwd p) {
     }
     // the residual-path gradient is only needed after the row reductions: issue its load with the others, so the
     // row costs one memory round trip instead of two
-    u32x2 addp[VPL];                            // ADD16: the residual-path gradient stays packed bf16 until it is added
+    u32x2 addp[V];                              // ADD16: the residual-path gradient stays packed bf16 until it is added
 #pragma unroll                                  // (2 instead of 4 registers per chunk: 100 -> 96 VGPRs at VPL 2 = 5 waves / SIMD)
-    for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
+    for (int v = 0; v < V; ++v) {
+      const int c = G::chunk(lane, wid, v);
       addv[v] = f32x4{0.f, 0.f, 0.f, 0.f};
       addp[v] = u32x2{0u, 0u};
       if constexpr (!POOL) {                    // (the pooled form has no residual-path gradient: 16 registers at VPL 4,
@@ -314,8 +413,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwd p) {
       }
     }
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
+    for (int v = 0; v < V; ++v) {
+      const int c = G::chunk(lane, wid, v);
       xh[v] = f32x4{0.f, 0.f, 0.f, 0.f}; gy[v] = xh[v];
       if (c < nch) {
         const f32x4 xv = load4<XBF16>(p.x, (long)row * p.ldx + 4 * c);
@@ -334,10 +433,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwd p) {
         }
       }
     }
-    const float c1 = wave_sum(s1) * inv_n, c2 = wave_sum(s2) * inv_n;
+    float c1 = s1, c2 = s2;
+    G::row_means(lane, wid, c1, c2, inv_n);
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
+    for (int v = 0; v < V; ++v) {
+      const int c = G::chunk(lane, wid, v);
       if (c < nch) {
         f32x4 dx;
 #pragma unroll
@@ -362,106 +462,25 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwd p) {
       }
     }
   }
-  // block-level combine of the 4 waves' dgamma/dbeta partials through LDS, then one partial row / block
-  float* sm = reinterpret_cast<float*>(smem);          // [4][2][cols]
+  if constexpr (NW == 4) {
+    ln_partials_direct(lane, wid, p.cols, dg, db, p.part);
+  } else {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* sm = reinterpret_cast<float*>(smem);          // [4][2][cols]
 #pragma unroll
-  for (int v = 0; v < VPL; ++v) {
-    const int c = lane + 64 * v;
-    if (c < nch) {
-      *reinterpret_cast<f32x4*>(sm + (wid * 2 + 0) * p.cols + 4 * c) = dg[v];
-      *reinterpret_cast<f32x4*>(sm + (wid * 2 + 1) * p.cols + 4 * c) = db[v];
-    }
-  }
-  __syncthreads();
-  const int nw = blockDim.x >> 6;
-  for (int i = threadIdx.x; i < 2 * p.cols; i += blockDim.x) {
-    float a = 0.f;
-    for (int w = 0; w < nw; ++w) a += sm[w * 2 * p.cols + i];
-    p.part[(long)blockIdx.x * 2 * p.cols + i] = a;
-  }
-}
-
-// Wide rows, backward (see ln_fwd_wide_kernel): one workgroup per row, f32 dy / x, optional f32 residual-path gradient;
-// every wave keeps the dgamma / dbeta partials of ITS columns and writes them to the block's partial row itself.
-template <int VPW>
-__global__ __launch_bounds__(256) void ln_bwd_wide_kernel(const LnBwd p) {
-  __shared__ float red[2][4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int nch = p.cols >> 2;
-  f32x4 g[VPW], b[VPW], dg[VPW], db[VPW];
-#pragma unroll
-  for (int v = 0; v < VPW; ++v) {
-    const int c = lane + 64 * (4 * v + wid);
-    g[v] = f32x4{0.f, 0.f, 0.f, 0.f}; b[v] = g[v]; dg[v] = g[v]; db[v] = g[v];
-    if (c < nch) {
-      g[v] = *reinterpret_cast<const f32x4*>(p.gamma + 4 * c);
-      if (p.act != CLIPK_ACT_NONE) b[v] = *reinterpret_cast<const f32x4*>(p.beta + 4 * c);
-    }
-  }
-  const float inv_n = 1.0f / (float)p.cols;
-  for (int row = blockIdx.x; row < p.rows; row += gridDim.x) {
-    const float mean = p.mean[row], rstd = p.rstd[row];
-    f32x4 xh[VPW], gy[VPW], addv[VPW];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPW; ++v) {
-      const int c = lane + 64 * (4 * v + wid);
-      addv[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (p.dx_add && c < nch) addv[v] = load4<false>(p.dx_add, (long)row * p.lddx + 4 * c);
-    }
-#pragma unroll
-    for (int v = 0; v < VPW; ++v) {
-      const int c = lane + 64 * (4 * v + wid);
-      xh[v] = f32x4{0.f, 0.f, 0.f, 0.f}; gy[v] = xh[v];
+    for (int v = 0; v < V; ++v) {
+      const int c = G::chunk(lane, wid, v);
       if (c < nch) {
-        const f32x4 xv = load4<false>(p.x, (long)row * p.ldx + 4 * c);
-        f32x4 dyv = load4<false>(p.dy, (long)row * p.lddy + 4 * c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float xhat = (xv[e] - mean) * rstd;
-          if (p.act != CLIPK_ACT_NONE) dyv[e] *= act_grad(xhat * g[v][e] + b[v][e], p.act);
-          xh[v][e] = xhat;
-          dg[v][e] += dyv[e] * xhat;
-          db[v][e] += dyv[e];
-          const float gg = dyv[e] * g[v][e];
-          gy[v][e] = gg;
-          s1 += gg; s2 += gg * xhat;
-        }
+        *reinterpret_cast<f32x4*>(sm + (wid * 2 + 0) * p.cols + 4 * c) = dg[v];
+        *reinterpret_cast<f32x4*>(sm + (wid * 2 + 1) * p.cols + 4 * c) = db[v];
       }
     }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    __syncthreads();                       // the previous row's sums have been read by every wave
-    if (lane == 0) { red[0][wid] = s1; red[1][wid] = s2; }
     __syncthreads();
-    const float c1 = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * inv_n;
-    const float c2 = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) * inv_n;
-#pragma unroll
-    for (int v = 0; v < VPW; ++v) {
-      const int c = lane + 64 * (4 * v + wid);
-      if (c < nch) {
-        f32x4 dx;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dx[e] = rstd * (gy[v][e] - c1 - xh[v][e] * c2);
-        dx += addv[v];
-        if (p.dx_f32) *reinterpret_cast<f32x4*>(p.dx_f32 + (long)row * p.lddx + 4 * c) = dx;
-        if (p.dx_bf16) {
-          if (p.drop_thr) {
-            const unsigned long long base = (unsigned long long)row * (unsigned)p.cols + 4u * c;
-            const unsigned dseed = drop_seed_eff(p.drop_seed, p.drop_epoch);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) dx[e] *= drop_mul(dseed, base + e, p.drop_thr, p.drop_scale);
-          }
-          store4_bf16(p.dx_bf16, (long)row * p.lddx + 4 * c, dx);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < VPW; ++v) {            // this block's partial row: every wave writes its own columns
-    const int c = lane + 64 * (4 * v + wid);
-    if (c < nch) {
-      *reinterpret_cast<f32x4*>(p.part + (long)blockIdx.x * 2 * p.cols + 4 * c) = dg[v];
-      *reinterpret_cast<f32x4*>(p.part + (long)blockIdx.x * 2 * p.cols + p.cols + 4 * c) = db[v];
+    const int nw = blockDim.x >> 6;
+    for (int i = threadIdx.x; i < 2 * p.cols; i += blockDim.x) {
+      float a = 0.f;
+      for (int w = 0; w < nw; ++w) a += sm[w * 2 * p.cols + i];
+      p.part[(long)blockIdx.x * 2 * p.cols + i] = a;
     }
   }
 }
@@ -488,29 +507,20 @@ struct LnBwd2 {
 
 template <int VPL>
 __global__ __launch_bounds__(256) void ln_bwd2_kernel(const LnBwd2 p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  const RowGeom<1> t(blockDim.x);
   const int nch = p.cols >> 2;
   f32x4 gm[VPL], bt[VPL], dgm[VPL], dbt[VPL];
+  ln_load_params(t, nch, p.gamma, p.beta, p.act != CLIPK_ACT_NONE, gm, bt);
 #pragma unroll
-  for (int v = 0; v < VPL; ++v) {
-    const int c = lane + 64 * v;
-    gm[v] = f32x4{0.f, 0.f, 0.f, 0.f}; bt[v] = gm[v]; dgm[v] = gm[v]; dbt[v] = gm[v];
-    if (c < nch) {
-      gm[v] = *reinterpret_cast<const f32x4*>(p.gamma + 4 * c);
-      if (p.act != CLIPK_ACT_NONE) bt[v] = *reinterpret_cast<const f32x4*>(p.beta + 4 * c);
-    }
-  }
+  for (int v = 0; v < VPL; ++v) { dgm[v] = f32x4{0.f, 0.f, 0.f, 0.f}; dbt[v] = dgm[v]; }
   const float inv_n = 1.0f / (float)p.cols;
-  for (int row = wave; row < p.rows; row += nwaves) {
+  for (int row = t.row0; row < p.rows; row += t.step) {
     const float mean = p.mean[row], r = p.rstd[row];
     f32x4 xh[VPL], gv[VPL], u[VPL], k1[VPL], k2[VPL];      // u = dy act'(n), k1 = act'(n), k2 = gamma dy act''(n)
     float su = 0.f, sux = 0.f, sg = 0.f, sgx = 0.f, sgu = 0.f;
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
+      const int c = t.chunk(v);
       xh[v] = f32x4{0.f, 0.f, 0.f, 0.f}; gv[v] = xh[v]; u[v] = xh[v]; k1[v] = xh[v]; k2[v] = xh[v];
       if (c < nch) {
         const long o = (long)row * p.ld + 4 * c;
@@ -543,7 +553,7 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(const LnBwd2 p) {
     float st = 0.f, stx = 0.f;
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
+      const int c = t.chunk(v);
       tt[v] = f32x4{0.f, 0.f, 0.f, 0.f}; w[v] = tt[v];
       if (c < nch) {
 #pragma unroll
@@ -553,9 +563,9 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(const LnBwd2 p) {
           w[v][e] = ww;
           const float q = ww * k2[v][e];                   // w gamma dy act''(n)
           const float ug = u[v][e] * gm[v][e];              // u with gamma
-          const float t = q * gm[v][e] - r * (ug * dgx + gv[v][e] * cux);
-          tt[v][e] = t;
-          st += t; stx += t * x;
+          const float tv = q * gm[v][e] - r * (ug * dgx + gv[v][e] * cux);
+          tt[v][e] = tv;
+          st += tv; stx += tv * x;
           dgm[v][e] += ww * u[v][e] + q * x;
           dbt[v][e] += q;
         }
@@ -564,7 +574,7 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(const LnBwd2 p) {
     const float mt = wave_sum(st) * inv_n, mtx = wave_sum(stx) * inv_n;
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
-      const int c = lane + 64 * v;
+      const int c = t.chunk(v);
       if (c < nch) {
         const long o = (long)row * p.ld + 4 * c;
         f32x4 ddy, da;
@@ -578,29 +588,14 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(const LnBwd2 p) {
       }
     }
   }
-  float* sm = reinterpret_cast<float*>(smem);          // [4][2][cols]
-#pragma unroll
-  for (int v = 0; v < VPL; ++v) {
-    const int c = lane + 64 * v;
-    if (c < nch) {
-      *reinterpret_cast<f32x4*>(sm + (wid * 2 + 0) * p.cols + 4 * c) = dgm[v];
-      *reinterpret_cast<f32x4*>(sm + (wid * 2 + 1) * p.cols + 4 * c) = dbt[v];
-    }
-  }
-  __syncthreads();
-  const int nw = blockDim.x >> 6;
-  for (int i = threadIdx.x; i < 2 * p.cols; i += blockDim.x) {
-    float acc = 0.f;
-    for (int ww = 0; ww < nw; ++ww) acc += sm[ww * 2 * p.cols + i];
-    p.part[(long)blockIdx.x * 2 * p.cols + i] = acc;
-  }
+  ln_partials_through_lds(t, p.cols, dgm, dbt, p.part);
 }
 
 // part: [nparts][ncols] with ncols = 2*cols ([dgamma | dbeta]).  Block = 16 columns x 16 row groups: a thread sums
 // every 16th partial row with 8 independent loads in flight (the old 64 x 4 shape ran 15 blocks of 256-deep
 // dependent chains: 33 us for a 4 MB input), LDS combines the 16 groups in a fixed order (deterministic).
-__global__ __launch_bounds__(256) void colreduce_kernel(const float* part, int nparts, int ncols, float* out0,
-                                                        float* out1, int cols, int accumulate) {
+__device__ __forceinline__ void colreduce_block(const float* part, int nparts, int ncols, float* out0, float* out1,
+                                                int cols, int accumulate) {
   __shared__ float sm[16][17];
   const int c = threadIdx.x & 15, rg = threadIdx.x >> 4;
   const int i = blockIdx.x * 16 + c;
@@ -626,41 +621,21 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* part, int n
   }
 }
 
+__global__ __launch_bounds__(256) void colreduce_kernel(const float* part, int nparts, int ncols, float* out0,
+                                                        float* out1, int cols, int accumulate) {
+  colreduce_block(part, nparts, ncols, out0, out1, cols, accumulate);
+}
+
 // Several column reduces in ONE launch (blockIdx.y = problem): the dgamma / dbeta partial rows of every LayerNorm whose
 // backward ran in this pass, reduced when the pass is over (functional.LayerNormFn defers them: one launch instead of one
 // per LayerNorm - 20 per step of the sliced notebook model, each a 4-us launch on the critical chain).  desc: 6 int64 per
-// problem {part, nparts, cols, out0 (dgamma), out1 (dbeta), accumulate}; same block shape and summation order as
-// colreduce_kernel.
+// problem {part, nparts, cols, out0 (dgamma), out1 (dbeta), accumulate}.
 __global__ __launch_bounds__(256) void colreduce_batched_kernel(const long long* desc) {
   const long long* d = desc + 6 * (long)blockIdx.y;
-  const float* part = reinterpret_cast<const float*>(d[0]);
-  const int nparts = (int)d[1], cols = (int)d[2], ncols = 2 * cols, accumulate = (int)d[5];
-  float* out0 = reinterpret_cast<float*>(d[3]);
-  float* out1 = reinterpret_cast<float*>(d[4]);
-  if ((int)blockIdx.x * 16 >= ncols) return;                 // (block-uniform)
-  __shared__ float sm[16][17];
-  const int c = threadIdx.x & 15, rg = threadIdx.x >> 4;
-  const int i = blockIdx.x * 16 + c;
-  float a = 0.f;
-  if (i < ncols) {
-    int s = rg;
-    for (; s + 7 * 16 < nparts; s += 8 * 16) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part[(long)(s + 16 * u) * ncols + i];
-      a += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-    for (; s < nparts; s += 16) a += part[(long)s * ncols + i];
-  }
-  sm[rg][c] = a;
-  __syncthreads();
-  if (rg == 0 && i < ncols) {
-    a = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a += sm[r][c];
-    float* o = (i < cols) ? (out0 ? out0 + i : nullptr) : (out1 ? out1 + (i - cols) : nullptr);
-    if (o) *o = accumulate ? (*o + a) : a;
-  }
+  const int cols = (int)d[2];
+  if ((int)blockIdx.x * 16 >= 2 * cols) return;              // (block-uniform)
+  colreduce_block(reinterpret_cast<const float*>(d[0]), (int)d[1], 2 * cols, reinterpret_cast<float*>(d[3]),
+                  reinterpret_cast<float*>(d[4]), cols, (int)d[5]);
 }
 
 // ---- L2 normalise -------------------------------------------------------------------------------
@@ -741,13 +716,46 @@ int ln_blocks_cap(int rows, int cap) {
 // second round
 int ln_blocks(int rows, int cols) { return ln_blocks_cap(rows, cols <= 512 ? 1280 : (cols <= 1024 ? 768 : 512)); }
 int ln_blocks_fwd(int rows) { return ln_blocks_cap(rows, 2048); }
+size_t ln_partials_lds(int cols) { return (size_t)4 * 2 * cols * sizeof(float); }   // ln_partials_through_lds
 
-template <int VPL, bool DYBF16, bool XBF16, bool ADD16 = false, bool POOL = false>
-void launch_ln_bwd(const LnBwd& p, int blocks, size_t lds, hipStream_t st) {
+template <class P>
+void ln_launch(void (*kernel)(const P), int blocks, size_t lds, hipStream_t st, const P& p) {
   if (lds > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ln_bwd_kernel<VPL, DYBF16, XBF16, ADD16, POOL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((ln_bwd_kernel<VPL, DYBF16, XBF16, ADD16, POOL>), dim3(blocks), dim3(256), lds, st, p);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, st, p);
+}
+
+// VPL 20 is the width of the workgroup-per-row form: five chunks in each of four waves, one block per row up to 2048
+template <int V, bool XBF16>
+void launch_ln_fwd(const LnFwd& p, hipStream_t st) {
+  constexpr int NW = ln_fwd_row_waves(V);
+  const int blocks = NW == 1 ? ln_blocks_fwd(p.rows) : (p.rows < 2048 ? p.rows : 2048);
+  ln_launch(ln_fwd_kernel<V / NW, NW, XBF16>, blocks, 0, st, p);
+}
+
+// ... and of the backward where dy and x are both f32 (with ln_blocks' grid: `blocks` partial rows either way); a bf16
+// stream or the pooled form keeps a wave per row at VPL 20
+template <int V, bool DYBF16, bool XBF16, bool ADD16 = false, bool POOL = false>
+void launch_ln_bwd(const LnBwd& p, int blocks, hipStream_t st) {
+  if constexpr (V == 20 && !DYBF16 && !XBF16 && !POOL)
+    ln_launch(ln_bwd_kernel<5, 4, false, false>, blocks, 0, st, p);
+  else
+    ln_launch(ln_bwd_kernel<V, 1, DYBF16, XBF16, ADD16, POOL>, blocks, ln_partials_lds(p.cols), st, p);
+}
+
+template <int V>
+int launch_ln_bwd2(const LnBwd2& p, int blocks, hipStream_t st) {
+  if constexpr (V > 8) return CLIPK_ERR_UNSUPPORTED;        // (eleven chunk arrays per lane: no form beyond 2048 columns)
+  else {
+    ln_launch(ln_bwd2_kernel<V>, blocks, ln_partials_lds(p.cols), st, p);
+    return CLIPK_OK;
+  }
+}
+
+int launch_colreduce(const void* part, int nparts, int cols, float* dgamma, float* dbeta, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(colreduce_kernel, dim3((2 * cols + 15) / 16), dim3(256), 0, st, (const float*)part, nparts, 2 * cols,
+                     dgamma, dbeta, cols, accumulate);
+  return clipk_check_launch();
 }
 
 }  // namespace
@@ -769,17 +777,10 @@ extern "C" int clipk_layernorm_fwd(const void* x, int x_dtype, int64_t ldx, cons
   if ((cols & 3) || (ldx & 3) || (ldy & 3)) return CLIPK_ERR_UNSUPPORTED;
   if (!aligned16(gamma) || !aligned16(beta)) return CLIPK_ERR_BAD_ARG;
   LnFwd p{x, (long)ldx, gamma, beta, eps, act, y_f32, y_bf16, (long)ldy, mean, rstd, rows, cols};
-  const int blocks = ln_blocks_fwd(rows);
   hipStream_t st = (hipStream_t)stream;
-  if (cols > 2048 && cols <= 5120) {                        // wide rows: one workgroup per row (the choice depends on the
-    const int wb = rows < 2048 ? rows : 2048;               // row WIDTH only: a row's arithmetic never depends on the batch)
-    if (x_dtype == CLIPK_BF16) hipLaunchKernelGGL((ln_fwd_wide_kernel<5, true>), dim3(wb), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((ln_fwd_wide_kernel<5, false>), dim3(wb), dim3(256), 0, st, p);
-    return clipk_check_launch();
-  }
-#define CALL(V)                                                                                   \
-  if (x_dtype == CLIPK_BF16) hipLaunchKernelGGL((ln_fwd_kernel<V, true>), dim3(blocks), dim3(256), 0, st, p); \
-  else hipLaunchKernelGGL((ln_fwd_kernel<V, false>), dim3(blocks), dim3(256), 0, st, p)
+#define CALL(V)                                                    \
+  if (x_dtype == CLIPK_BF16) launch_ln_fwd<V, true>(p, st);        \
+  else launch_ln_fwd<V, false>(p, st)
   LN_DISPATCH_VPL(cols, CALL);
 #undef CALL
   return clipk_check_launch();
@@ -802,44 +803,30 @@ extern "C" int clipk_layernorm_bwd(const void* dy, int dy_dtype, int64_t lddy, c
   if (dx_add && dx_add_dtype == CLIPK_BF16 && !(dy_dtype == CLIPK_BF16 && x_dtype == CLIPK_F32)) return CLIPK_ERR_UNSUPPORTED;
   const int blocks = ln_blocks(rows, cols);
   if (workspace_bytes < (size_t)blocks * 2 * cols * sizeof(float)) return CLIPK_ERR_BAD_ARG;
+  const DropParams drop = drop_params(drop_p);
   LnBwd p{dy, (long)lddy, x, (long)ldx, gamma, beta, mean, rstd, act, dx_add, dx_f32, dx_bf16, (long)lddx,
-          (float*)workspace, rows, cols, 0u, drop_seed, 1.0f, (dx_add && dx_add_dtype == CLIPK_BF16) ? 1 : 0,
+          (float*)workspace, rows, cols, drop.thr, drop_seed, drop.scale, (dx_add && dx_add_dtype == CLIPK_BF16) ? 1 : 0,
           nullptr, 1};
   p.drop_epoch = clipk_drop_epoch();
-  if (drop_p > 0.f && drop_p < 1.f) {
-    const double t = (double)drop_p * 4294967296.0;
-    p.drop_thr = t < 1.0 ? 1u : (t >= 4294967295.0 ? 4294967295u : (unsigned)t);
-    p.drop_scale = 1.0f / (1.0f - drop_p);
-  }
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)4 * 2 * cols * sizeof(float);
-  const bool wide = cols > 2048 && cols <= 5120 && dy_dtype == CLIPK_F32 && x_dtype == CLIPK_F32 && !p.add_bf16;
-  if (wide)                                     // one workgroup per row (ln_bwd_wide_kernel); `blocks` partial rows as below
-    hipLaunchKernelGGL((ln_bwd_wide_kernel<5>), dim3(blocks), dim3(256), 0, st, p);
 #define CALL(V)                                                                                                   \
   do {                                                                                                            \
-    if (wide) break;                                                                                              \
     if (p.add_bf16)                             /* bf16 gradient stream: bf16 dy, f32 x (checked above) */       \
-      launch_ln_bwd<V, true, false, true>(p, blocks, lds, st);                                                    \
+      launch_ln_bwd<V, true, false, true>(p, blocks, st);                                                         \
     else if (dy_dtype == CLIPK_BF16 && x_dtype == CLIPK_BF16)                                                     \
-      launch_ln_bwd<V, true, true>(p, blocks, lds, st);                                                           \
+      launch_ln_bwd<V, true, true>(p, blocks, st);                                                                \
     else if (dy_dtype == CLIPK_BF16)                                                                              \
-      launch_ln_bwd<V, true, false>(p, blocks, lds, st);                                                          \
+      launch_ln_bwd<V, true, false>(p, blocks, st);                                                               \
     else if (x_dtype == CLIPK_BF16)                                                                               \
-      launch_ln_bwd<V, false, true>(p, blocks, lds, st);                                                          \
+      launch_ln_bwd<V, false, true>(p, blocks, st);                                                               \
     else                                                                                                          \
-      launch_ln_bwd<V, false, false>(p, blocks, lds, st);                                                         \
+      launch_ln_bwd<V, false, false>(p, blocks, st);                                                              \
   } while (0)
   LN_DISPATCH_VPL(cols, CALL);
 #undef CALL
-  int rc = clipk_check_launch();
-  if (rc) return rc;
-  if (dgamma || dbeta) {
-    hipLaunchKernelGGL(colreduce_kernel, dim3((2 * cols + 15) / 16), dim3(256), 0, st, (const float*)workspace,
-                       blocks, 2 * cols, dgamma, dbeta, cols, accumulate);
-    rc = clipk_check_launch();
-  }
-  return rc;
+  const int rc = clipk_check_launch();
+  if (rc || !(dgamma || dbeta)) return rc;
+  return launch_colreduce(workspace, blocks, cols, dgamma, dbeta, accumulate, st);
 }
 
 // out[c] (+)= sum over rows of x[r][c]: the bias gradient of an exact-f32 Linear (db = dY.sum(0)), fixed summation order
@@ -876,23 +863,11 @@ extern "C" int clipk_layernorm_bwd2(const float* g, const float* dy, const float
   if (workspace_bytes < (size_t)blocks * 2 * cols * sizeof(float)) return CLIPK_ERR_BAD_ARG;
   LnBwd2 p{g, dy, a, (long)ld, gamma, beta, mean, rstd, act, d_dy, d_a, (float*)workspace, rows, cols};
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)4 * 2 * cols * sizeof(float);
-#define LN_BWD2_CALL(V)                                                                                      \
-  do {                                                                                                       \
-    if (lds > 65536)                                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ln_bwd2_kernel<V>),                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
-    hipLaunchKernelGGL((ln_bwd2_kernel<V>), dim3(blocks), dim3(256), lds, st, p);                            \
-  } while (0)
-  const int nch_ = cols >> 2;
-  if (nch_ <= 64 * 2) LN_BWD2_CALL(2);
-  else if (nch_ <= 64 * 4) LN_BWD2_CALL(4);
-  else if (nch_ <= 64 * 8) LN_BWD2_CALL(8);
-  else return CLIPK_ERR_UNSUPPORTED;
-#undef LN_BWD2_CALL
-  if (d_gamma)
-    hipLaunchKernelGGL(colreduce_kernel, dim3((2 * cols + 15) / 16), dim3(256), 0, st, (const float*)workspace,
-                       blocks, 2 * cols, d_gamma, d_beta, cols, accumulate);
+#define CALL(V) \
+  if (const int rc = launch_ln_bwd2<V>(p, blocks, st)) return rc
+  LN_DISPATCH_VPL(cols, CALL);
+#undef CALL
+  if (d_gamma) return launch_colreduce(workspace, blocks, cols, d_gamma, d_beta, accumulate, st);
   return clipk_check_launch();
 }
 
@@ -906,11 +881,9 @@ extern "C" int clipk_layernorm_meanpool_fwd(const void* x, int x_dtype, int64_t 
   const size_t lds = ((size_t)4 * cols + 4) * sizeof(float);
   if (lds > 65536) return CLIPK_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-#define CALL(V)                                                                                          \
-  do {                                                                                                   \
-    if (x_dtype == CLIPK_BF16) hipLaunchKernelGGL((ln_pool_fwd_kernel<V, true>), dim3(B), dim3(256), lds, st, p);  \
-    else hipLaunchKernelGGL((ln_pool_fwd_kernel<V, false>), dim3(B), dim3(256), lds, st, p);             \
-  } while (0)
+#define CALL(V)                                                                      \
+  if (x_dtype == CLIPK_BF16) ln_launch(ln_pool_fwd_kernel<V, true>, B, lds, st, p);  \
+  else ln_launch(ln_pool_fwd_kernel<V, false>, B, lds, st, p)
   LN_DISPATCH_VPL(cols, CALL);
 #undef CALL
   return clipk_check_launch();
@@ -933,22 +906,14 @@ extern "C" int clipk_layernorm_meanpool_bwd(const float* dpooled, const float* r
   LnBwd p{dpooled, (long)cols, x, (long)ldx, gamma, nullptr, mean, rstd, CLIPK_ACT_NONE, nullptr, dx_f32, dx_bf16,
           (long)lddx, (float*)workspace, rows, cols, 0u, 0u, 1.0f, 0, row_weight, L};
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)4 * 2 * cols * sizeof(float);
 #define CALL(V)                                                                          \
-  do {                                                                                   \
-    if (x_dtype == CLIPK_BF16) launch_ln_bwd<V, false, true, false, true>(p, blocks, lds, st);   \
-    else launch_ln_bwd<V, false, false, false, true>(p, blocks, lds, st);                \
-  } while (0)
+  if (x_dtype == CLIPK_BF16) launch_ln_bwd<V, false, true, false, true>(p, blocks, st);  \
+  else launch_ln_bwd<V, false, false, false, true>(p, blocks, st)
   LN_DISPATCH_VPL(cols, CALL);
 #undef CALL
-  int rc = clipk_check_launch();
-  if (rc) return rc;
-  if (dgamma || dbeta) {
-    hipLaunchKernelGGL(colreduce_kernel, dim3((2 * cols + 15) / 16), dim3(256), 0, st, (const float*)workspace,
-                       blocks, 2 * cols, dgamma, dbeta, cols, accumulate);
-    rc = clipk_check_launch();
-  }
-  return rc;
+  const int rc = clipk_check_launch();
+  if (rc || !(dgamma || dbeta)) return rc;
+  return launch_colreduce(workspace, blocks, cols, dgamma, dbeta, accumulate, st);
 }
 
 extern "C" int clipk_l2norm_fwd(const float* x, float* y, float* norm, int rows, int cols, float eps, void* stream) {

@@ -1,7 +1,7 @@
 """GPU: the LayerNorm family of csrc/rowwise.hip (forward with fused activation, first and second backward, LayerNorm + mean
 pooling, the deferred parameter-gradient reduce) against the plain f64 references and the tolerances of
 tests/layernorm_ref.py (pinned on the CPU by tests/test_layernorm_ref_host.py), branch by branch: every register width
-(VPL 2 / 4 / 8 / 20) and both one-workgroup-per-row kernels on either side of each dispatch boundary, every accepted
+(VPL 2 / 4 / 8 / 20) and both one-workgroup-per-row (NW = 4) instantiations on either side of each dispatch boundary, every accepted
 (dy, x, dx_add) type triple, the second trip of every grid-stride loop, the dropout multiply, strides, refusals.  Every
 input comes from a seeded CPU generator; each docstring names the branch the test exists for.  What the dispatch promises
 exactly (bf16 = RNE of the f32 output, outputs independent of which are asked for, rows independent of the batch, the
@@ -23,7 +23,7 @@ WIDTHS = [4, 8, 256, 260, 512, 516, 1024, 1028, 2048, 2052, 5120]   # VPL 2 | 4 
 ROWS = [1, 3, 4, 5, 9]                  # 1: three idle waves; 4 | 5: one block | two; 9: three blocks, the last with one row
 BAD_ARG, UNSUPPORTED = -1, -2           # include/clipk.h
 GUARD = 16
-# accepted (dy, x, dx_add) types -> the kernel instantiation at cols <= 2048 (beyond: ln_bwd_wide_kernel for f32 / f32, VPL 20 else)
+# accepted (dy, x, dx_add) types -> the kernel instantiation at cols <= 2048 (beyond: ln_bwd_kernel<5, 4> for f32 / f32, VPL 20 else)
 TRIPLES = [("f32", "f32", None), ("f32", "f32", "f32"),          # launch_ln_bwd<V, false, false>
            ("f32", "bf16", "f32"),                               # <V, false, true>
            ("bf16", "bf16", None), ("bf16", "bf16", "f32"),      # <V, true, true>
@@ -94,7 +94,7 @@ def _check_fwd(dev, fam, rows, cols, xbf16, act, eps0, seed=50):
 @pytest.mark.parametrize("fam,xbf16", [(f, False) for f in R.FAMILIES] + [(f, True) for f in "abc"])
 @pytest.mark.parametrize("cols", WIDTHS)
 def test_forward_every_width_and_family(dev, cols, fam, xbf16):
-    """ln_fwd_kernel<2 | 4 | 8> and ln_fwd_wide_kernel<5> (cols 2052, 5120), f32 and bf16 x, on both sides of every dispatch
+    """ln_fwd_kernel<2 | 4 | 8, 1> and ln_fwd_kernel<5, 4> (cols 2052, 5120), f32 and bf16 x, on both sides of every dispatch
     boundary, rows 1 .. 9 (a lone row leaves three waves of its block idle), None / gelu (+ celu / softplus on f32), eps 1e-12
     and 1e-5: y32, mean, rstd within layernorm_ref.bounds of f64 on N(0, 4), offset 100 (|mean| >> std: the two-pass
     variance), std 1e-3 against eps 1e-5, and one constant row (finite outputs, mean within 2 ulp of the constant);
@@ -111,8 +111,8 @@ def test_forward_every_width_and_family(dev, cols, fam, xbf16):
 @pytest.mark.parametrize("xbf16", [False, True])
 @pytest.mark.parametrize("rows,cols", [(8197, 8), (2053, 2052)])
 def test_forward_second_grid_stride_trip(dev, rows, cols, xbf16):
-    """The forward grids are capped at 2048 blocks: rows > 8192 send the first waves of ln_fwd_kernel round `row += nwaves`
-    again (rows 8192 .. 8196), rows > 2048 the first blocks of ln_fwd_wide_kernel round `row += gridDim.x`.  Against f64, and
+    """The forward grids are capped at 2048 blocks: rows > 8192 send the first waves of ln_fwd_kernel<V, 1> round `row += row_step`
+    again (rows 8192 .. 8196), rows > 2048 the first blocks of ln_fwd_kernel<5, 4> round it (row_step = gridDim.x).  Against f64, and
     the last row bit for bit against a 1-row call."""
     ops = _ops()
     _check_fwd(dev, "a", rows, cols, xbf16, None, 1e-5, seed=60)
@@ -182,7 +182,7 @@ def _check_bwd(dev, fam, rows, cols, triple, act, seed=80):
 @pytest.mark.parametrize("triple", TRIPLES, ids=lambda t: "-".join(str(k) for k in t))
 @pytest.mark.parametrize("cols", WIDTHS)
 def test_backward_every_type_triple_at_every_width(dev, cols, triple):
-    """The four launch_ln_bwd type instantiations and ADD16 at VPL 2 / 4 / 8, ln_bwd_wide_kernel<5> for the f32 triples at
+    """The four launch_ln_bwd type instantiations and ADD16 at VPL 2 / 4 / 8, ln_bwd_kernel<5, 4> for the f32 triples at
     cols 2052 / 5120 and VPL 20 (160 KiB of dynamic LDS at 5120) for the others; rows 1 .. 9; families (a) - (d) without an
     activation, gelu on (a) and (c) (layernorm_ref.ACT_BWD_FAMILIES).  dx32, dgamma, dbeta within layernorm_ref.bounds of
     the f64 closed form on the values the kernel sees, mean / rstd from the kernel's own forward; dx16 == RNE(dx32)."""
@@ -229,7 +229,7 @@ GRID_STRIDE_BWD = [(5125, 8, TRIPLES[1]),        # cols <= 512: 1280 blocks
                    (5125, 8, TRIPLES[6]),
                    (3077, 516, TRIPLES[6]),      # cols <= 1024: 768 blocks
                    (2053, 1028, TRIPLES[4]),     # beyond: 512 blocks
-                   (2053, 2052, TRIPLES[1])]     # ln_bwd_wide_kernel: `row += gridDim.x`
+                   (2053, 2052, TRIPLES[1])]     # ln_bwd_kernel<5, 4>: row_step = gridDim.x
 
 
 @pytest.mark.parametrize("rows,cols,triple", GRID_STRIDE_BWD, ids=lambda v: "-".join(map(str, v)) if isinstance(v, tuple) else str(v))
@@ -272,8 +272,8 @@ def _check_dropout(d, dx32, dg, db, rows, cols, act=None):
                                               (9, 2052, TRIPLES[1]), (5, 5120, TRIPLES[0])],
                          ids=lambda v: "-".join(map(str, v)) if isinstance(v, tuple) else str(v))
 def test_backward_dropout_mask_is_the_emulators_hash(dev, rows, cols, triple):
-    """The dropout multiply on the bf16 output of ln_bwd_kernel (ADD16 path of encoders._post_layer_bwd among the cases) and
-    of ln_bwd_wide_kernel: dx16 == RNE(dx32 * m) bit for bit, m = ops_emulator.drop_mult(0.1, 99) at row * cols + col scaled
+    """The dropout multiply on the bf16 output of ln_bwd_kernel<V, 1> (ADD16 path of encoders._post_layer_bwd among the cases) and
+    of ln_bwd_kernel<5, 4>: dx16 == RNE(dx32 * m) bit for bit, m = ops_emulator.drop_mult(0.1, 99) at row * cols + col scaled
     by f32 1 / (1 - p); dx32, dgamma, dbeta unmasked; a bf16-only call gives the same bits; p = 0 is the no-dropout result."""
     d, c, (dx32, dx16, dg, db), _ = _check_bwd(dev, "a", rows, cols, triple, "gelu", seed=110)
     _check_dropout(d, dx32, dg, db, rows, cols, act="gelu")

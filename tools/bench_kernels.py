@@ -169,6 +169,22 @@ def bench_ln():
         fb = T * cols * (4 + 2)
         bb = T * cols * (2 + 4 + 4 + 4 + 2)
         print(f"layernorm d={cols}: fwd {f * 1e3:7.1f} us {fb / f / 1e9:6.2f} TB/s | bwd {bw * 1e3:7.1f} us {bb / bw / 1e9:6.2f} TB/s")
+    # LayerNorm + mean pool over L = 256 rows per sample (bf16 rows in, as the ESM tower's last LayerNorm), and the second-order
+    # backward (f32 only), one model width each
+    B, L, cols = T // 256, 256, 480
+    x = rnd((T, cols))
+    g, b = torch.ones(cols, device=DEV), torch.zeros(cols, device=DEV)
+    f, _ = timeit(lambda: ops.layernorm_meanpool_fwd(x, g, b, 1e-5, B, L))
+    _, mean, rstd, wrow = ops.layernorm_meanpool_fwd(x, g, b, 1e-5, B, L)
+    dp = torch.randn(B, cols, device=DEV)
+    bw, _ = timeit(lambda: ops.layernorm_meanpool_bwd(dp, wrow, x, g, mean, rstd, B, L, want_f32=False, want_bf16=True))
+    print(f"layernorm+meanpool d={cols}: fwd {f * 1e3:7.1f} us | bwd {bw * 1e3:7.1f} us")
+    rows, cols = T // 8, 768
+    a, dy, gc = (torch.randn(rows, cols, device=DEV) for _ in range(3))
+    g, b = torch.ones(cols, device=DEV), torch.zeros(cols, device=DEV)
+    _, _, mean, rstd = ops.layernorm_fwd(a, g, b, 1e-5, act="softplus")
+    bw2, _ = timeit(lambda: ops.layernorm_bwd2(gc, dy, a, g, b, mean, rstd, act="softplus"))
+    print(f"layernorm bwd2 d={cols} rows={rows}: {bw2 * 1e3:7.1f} us")
 
 
 if __name__ == "__main__":
