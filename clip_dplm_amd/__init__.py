@@ -36,6 +36,8 @@ from .distribution import evaluate_distributions, frechet_distance, mmd2
 from . import distribution
 from .cluster import (KMeansResult, adjusted_rand_index, cluster_agreement, contingency, kmeans,
                       normalized_mutual_info)
+from .cluster import (calinski_harabasz_score, choose_n_clusters, davies_bouldin_score, label_separation,
+                      silhouette_by_label, silhouette_samples, silhouette_score)
 from . import cluster
 
 __all__ = [
@@ -57,5 +59,6 @@ __all__ = [
     "ExactOptimalTransportConditionalFlowMatcher", "linear_conditional_flow",
     "distribution", "mmd2", "frechet_distance", "evaluate_distributions",
     "cluster", "kmeans", "KMeansResult", "contingency", "adjusted_rand_index", "normalized_mutual_info",
-    "cluster_agreement",
+    "cluster_agreement", "silhouette_samples", "silhouette_score", "silhouette_by_label", "davies_bouldin_score",
+    "calinski_harabasz_score", "label_separation", "choose_n_clusters",
 ]

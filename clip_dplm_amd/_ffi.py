@@ -154,6 +154,8 @@ SIGNATURES = {
     "clipk_kernel_sums": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "clipk_kmeans_step_workspace": (_sz, [_i, _i, _i]),
     "clipk_kmeans_step": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_label_dist_sums_workspace": (_sz, [_i, _i, _i, _i]),
+    "clipk_label_dist_sums": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "clipk_sim_top2_bias_plan": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "clipk_sim_top2_bias_workspace": (_sz, [_i, _i, _i]),
     "clipk_sim_top2_bias": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -14,6 +14,11 @@ One Lloyd iteration on x [N, P] with centroids c [K, P] (f32, device):
 K <= 64: one ops.kmeans_step call (include/clipk.h: clipk_kmeans_step) - assignment and update read each tile of x once,
 the N x K scores never leave the workgroup.  K > 64: ops.sim_top2_bias assigns, ops.kmeans_step sums under those labels.
 What is left to ATen is O((N + K) P) glue: the division by the counts, the centroid norms, the seeding.
+
+Whether a labeling - a k-means result, or an annotation such as the cell types - is any good: the silhouette width per
+point, per label and overall on ops.label_dist_sums (include/clipk.h: clipk_label_dist_sums; the N x N distances never
+leave the workgroups), the Davies-Bouldin and Calinski-Harabasz scores as f64 glue on cluster sums, and
+choose_n_clusters, which makes the reference's hard-coded 10 checkable.
 """
 from __future__ import annotations
 
@@ -25,7 +30,8 @@ import torch
 from . import ops
 
 __all__ = ["kmeans", "KMeansResult", "init_centroids", "contingency", "adjusted_rand_index", "normalized_mutual_info",
-           "cluster_agreement"]
+           "cluster_agreement", "silhouette_samples", "silhouette_score", "silhouette_by_label", "davies_bouldin_score",
+           "calinski_harabasz_score", "label_separation", "choose_n_clusters"]
 
 METRICS = ("euclidean", "cosine")
 INITS = ("k-means++", "random")
@@ -283,11 +289,13 @@ def normalized_mutual_info(labels_a, labels_b) -> float:
 
 
 @torch.no_grad()
-def cluster_agreement(a, b, n_clusters: int = 10, labels=None, **kmeans_kw) -> dict:
+def cluster_agreement(a, b, n_clusters: int = 10, labels=None, silhouette: bool = False, **kmeans_kw) -> dict:
     """The reference's analyze_embedding_alignment: k-means with n_clusters on each of the paired clouds a [N, Pa] and
     b [N, Pb] (row i of both is one sample), then {"ari", "nmi"} between the two labelings, Python floats.  labels (an
     integer annotation [N], e.g. the cell types): also "ari_a_vs_labels", "nmi_a_vs_labels", "ari_b_vs_labels",
-    "nmi_b_vs_labels".  Keyword arguments go to kmeans()."""
+    "nmi_b_vs_labels".  silhouette=True: also "silhouette_a", "silhouette_b" - silhouette_score of each cloud under its own
+    k-means labels, in the k-means metric - and with labels "silhouette_a_vs_labels", "silhouette_b_vs_labels", each cloud
+    under the annotation.  Keyword arguments go to kmeans()."""
     for name, t in (("a", a), ("b", b)):
         if not isinstance(t, torch.Tensor) or t.dim() != 2:
             raise TypeError(f"{name} must be a 2-D tensor")
@@ -299,9 +307,216 @@ def cluster_agreement(a, b, n_clusters: int = 10, labels=None, **kmeans_kw) -> d
             raise ValueError(f"labels has {labels.shape[0]} entries for {a.shape[0]} rows")
     la, lb = kmeans(a, n_clusters, **kmeans_kw).labels, kmeans(b, n_clusters, **kmeans_kw).labels
     out = {"ari": adjusted_rand_index(la, lb), "nmi": normalized_mutual_info(la, lb)}
+    metric = kmeans_kw.get("metric", "euclidean")
+    if silhouette:
+        out["silhouette_a"], out["silhouette_b"] = silhouette_score(a, la, metric), silhouette_score(b, lb, metric)
     if labels is not None:
         labels = labels.to(la.device)
-        for name, l in (("a", la), ("b", lb)):
+        for name, l, cloud in (("a", la, a), ("b", lb, b)):
             out[f"ari_{name}_vs_labels"] = adjusted_rand_index(l, labels)
             out[f"nmi_{name}_vs_labels"] = normalized_mutual_info(l, labels)
+            if silhouette:
+                out[f"silhouette_{name}_vs_labels"] = silhouette_score(cloud, labels, metric)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ quality of one labeling
+SILHOUETTE_METRICS = ops.LABEL_DIST_METRICS
+SILHOUETTE_BLOCK_BYTES = 256 << 20                  # the [rows, G] sums of one row block (default row_block)
+CRITERIA = ("silhouette", "calinski_harabasz", "davies_bouldin")
+
+
+def _relabel(x, labels):
+    """(label values [G] ascending, positions int64 [N] in 0..G-1, counts int64 [G]) of an annotation of x's rows; the
+    ValueError of every score here unless 2 <= G <= N - 1.  torch.unique: the one host read (G is a shape)."""
+    labels = _labels_arg("labels", labels)
+    N = x.shape[0]
+    if labels.shape[0] != N:
+        raise ValueError(f"labels has {labels.shape[0]} entries for {N} rows")
+    values, inv, counts = torch.unique(labels, return_inverse=True, return_counts=True)
+    G = values.shape[0]
+    if not 2 <= G <= N - 1:
+        raise ValueError(f"the number of distinct labels must be in [2, N - 1], got {G} for N = {N}")
+    return values, inv, counts
+
+
+def _silhouette(x, labels, metric, row_block):
+    """(s f32 [N], values, inv, counts): every argument error first, then the row-block walks."""
+    _check_cloud(x)
+    if metric not in SILHOUETTE_METRICS:
+        raise ValueError(f"metric must be one of {SILHOUETTE_METRICS}, got {metric!r}")
+    if row_block is not None and (isinstance(row_block, bool) or not isinstance(row_block, int) or row_block < 1):
+        raise ValueError(f"row_block must be None or a positive int, got {row_block!r}")
+    values, inv, counts = _relabel(x, labels)
+    if not x.is_cuda:
+        raise ValueError("the silhouette needs device tensors (there is no CPU fallback)")
+    G, N = values.shape[0], x.shape[0]
+    if G > ops.LABEL_DIST_MAX_LABELS:
+        raise ValueError(f"at most {ops.LABEL_DIST_MAX_LABELS} distinct labels, got {G}")
+    x = _prepare(x, metric)
+    inv, counts = inv.to(x.device), counts.to(x.device)
+    lab32 = inv.int()
+    nx = None if metric == "cosine" else (x * x).sum(1)
+    n = counts.float()
+    if row_block is None:
+        row_block = max(64, SILHOUETTE_BLOCK_BYTES // (4 * ((G + 3) // 4 * 4)) // 64 * 64)
+    s = torch.empty(N, dtype=torch.float32, device=x.device)
+    for r0 in range(0, N, row_block):
+        r1 = min(N, r0 + row_block)
+        d = ops.label_dist_sums(x[r0:r1], x, lab32, G, metric, None if nx is None else nx[r0:r1], nx, diag_offset=r0)
+        own = inv[r0:r1, None]
+        n_own = n[inv[r0:r1]]
+        a = d.gather(1, own)[:, 0] / (n_own - 1).clamp_min(1.0)
+        b = (d / n[None, :]).scatter_(1, own, float("inf")).min(1).values
+        sil = torch.nan_to_num((b - a) / torch.maximum(a, b))             # a = b = 0 (coincident points): 0, as sklearn
+        s[r0:r1] = torch.where(n_own > 1, sil, torch.zeros_like(sil))     # alone in its cluster: 0
+    return s, values, inv, counts
+
+
+@torch.no_grad()
+def silhouette_samples(x, labels, metric: str = "euclidean", row_block: Optional[int] = None):
+    """The silhouette width of every row of the cloud x [N, P] (f32, device; P % 4 == 0, P <= 512) under the integer
+    annotation labels [N] (any values, device or host; 2 <= distinct labels <= N - 1): f32 [N] on the device, sklearn's
+    definition.  With D[i, g] = the sum of d(x_i, x_j) over the other points j of label g (ops.label_dist_sums - the
+    N x N distances never leave the workgroups):
+
+        a_i = D[i, own] / (n_own - 1),  b_i = min over the other labels of D[i, g] / n_g,  s_i = (b_i - a_i) / max(a_i, b_i)
+
+    and 0 for a point alone in its cluster.  metric: "euclidean", "sqeuclidean" or "cosine" (1 - cos: the rows are
+    L2-normalised first).  Queries go through in blocks of row_block rows against the whole cloud, so the [rows, G]
+    sums stay bounded (default: about 256 MiB of them).  More than 512 distinct labels cost one walk per 512."""
+    return _silhouette(x, labels, metric, row_block)[0]
+
+
+def _subset(x, labels, sample_size, generator):
+    if sample_size is None:
+        return x, labels
+    _check_cloud(x)
+    N = x.shape[0]
+    if isinstance(sample_size, bool) or not isinstance(sample_size, int) or not 1 <= sample_size <= N:
+        raise ValueError(f"sample_size must be None or an int in [1, N], got {sample_size!r}")
+    labels = _labels_arg("labels", labels)
+    if labels.shape[0] != N:
+        raise ValueError(f"labels has {labels.shape[0]} entries for {N} rows")
+    gdev = generator.device if generator is not None else "cpu"
+    idx = torch.randperm(N, generator=generator, device=gdev)[:sample_size]
+    return x[idx.to(x.device)], labels[idx.to(labels.device)]
+
+
+@torch.no_grad()
+def silhouette_score(x, labels, metric: str = "euclidean", sample_size: Optional[int] = None, generator=None,
+                     row_block: Optional[int] = None) -> float:
+    """The mean of silhouette_samples, a Python float in [-1, 1].  sample_size: the score of one random subset of the rows,
+    queries and keys alike, as sklearn does - torch.randperm(N, generator=generator)[:sample_size], drawn on the
+    generator's device (the host without one)."""
+    x, labels = _subset(x, labels, sample_size, generator)
+    return float(_silhouette(x, labels, metric, row_block)[0].double().mean())
+
+
+def _label_means(v, inv, counts):
+    return torch.zeros(counts.shape[0], dtype=torch.float64, device=v.device).index_add_(0, inv, v.double()) / counts.double()
+
+
+@torch.no_grad()
+def silhouette_by_label(x, labels, metric: str = "euclidean", row_block: Optional[int] = None):
+    """(label values [G] ascending, mean silhouette width per label f64 [G], counts int64 [G]), on x's device: how well
+    each annotation value - a cell type, an RBP, a perturbation - is separated from the others in the embedding space.
+    A label whose points sit inside another label's cloud comes out near or below 0: the collapse the reference's
+    analyze_embedding_collapse looks for with mean cosine similarities inside hand-picked groups."""
+    s, values, inv, counts = _silhouette(x, labels, metric, row_block)
+    return values.to(s.device), _label_means(s, inv, counts), counts
+
+
+def _centroid_stats(x, labels):
+    """(centroids f64 [G, P], counts f64 [G], mean distance to the own centroid f64 [G], sum of squared distances to the
+    own centroid (0-d f64), N): on the device the cluster sums come from ops.kmeans_step with the labels given and the
+    N x P differences are f32; host tensors go through index_add_ in f64."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or not x.is_floating_point():
+        raise TypeError("x must be a 2-D floating-point tensor")
+    values, inv, counts = _relabel(x, labels)
+    G, P = values.shape[0], x.shape[1]
+    inv = inv.to(x.device)
+    cnt = counts.to(x.device).double()
+    if x.is_cuda:
+        _check_cloud(x)
+        if G > ops.KMEANS_MAX_K:
+            raise ValueError(f"at most {ops.KMEANS_MAX_K} distinct labels, got {G}")
+        x = x.detach().contiguous()
+        sums = ops.kmeans_step(x, torch.zeros((G, P), dtype=torch.float32, device=x.device), labels=inv.int())[2].double()
+        work = x
+    else:
+        work = x.detach().double()
+        sums = torch.zeros((G, P), dtype=torch.float64).index_add_(0, inv, work)
+    c = sums / cnt[:, None]
+    d2 = (work - c.to(work.dtype)[inv]).square().sum(1).double()
+    intra = torch.zeros(G, dtype=torch.float64, device=x.device).index_add_(0, inv, d2.sqrt()) / cnt
+    return c, cnt, intra, d2.sum(), x.shape[0]
+
+
+@torch.no_grad()
+def davies_bouldin_score(x, labels) -> float:
+    """The Davies-Bouldin index (1979) of the labeling, sklearn's conventions: with s_g the mean distance of label g's
+    points to their centroid and m_gh the distance between centroids, the mean over g of max_{h != g} (s_g + s_h) / m_gh -
+    lower is better, 0 the best.  Centroid pairs at distance 0 are left out of the maximum; all s_g or all m_gh zero
+    gives 0.0.  x [N, P], device (f32, the limits of kmeans) or host (any float dtype); f64 glue on cluster sums."""
+    c, _, intra, _, _ = _centroid_stats(x, labels)
+    m = torch.cdist(c, c, compute_mode="donot_use_mm_for_euclid_dist")          # from the differences: an exact 0 diagonal
+    if bool((intra.abs() <= 1e-8).all()) or bool((m.abs() <= 1e-8).all()):       # numpy.allclose(., 0) defaults
+        return 0.0
+    m = torch.where(m == 0, torch.full_like(m, float("inf")), m)
+    return float(((intra[:, None] + intra[None, :]) / m).max(1).values.mean())
+
+
+@torch.no_grad()
+def calinski_harabasz_score(x, labels) -> float:
+    """The Calinski-Harabasz index (1974), sklearn's conventions: (between-cluster dispersion / (G - 1)) / (within-cluster
+    dispersion / (N - G)) - higher is better; 1.0 when the within-cluster dispersion is 0.  Inputs as
+    davies_bouldin_score."""
+    c, cnt, _, within, N = _centroid_stats(x, labels)
+    G = c.shape[0]
+    mean = (c * cnt[:, None]).sum(0) / cnt.sum()
+    between = float((cnt * (c - mean).square().sum(1)).sum())
+    within = float(within)
+    return 1.0 if within == 0.0 else between * (N - G) / (within * (G - 1))
+
+
+@torch.no_grad()
+def label_separation(x, labels, metric: str = "euclidean") -> dict:
+    """How well an annotation (cell type, RBP, perturbation) is separated in the embedding space x [N, P] (f32, device):
+    {"silhouette": the mean width, "davies_bouldin", "calinski_harabasz": the two centroid-based scores (Euclidean
+    whatever the metric), "silhouette_by_label": (label values, mean width per label, counts)}.  What the reference's
+    config asks of a BiologicalMetrics it never defines (tong/configs/default.yaml: compute_biological_metrics)."""
+    s, values, inv, counts = _silhouette(x, labels, metric, None)
+    return {"silhouette": float(s.double().mean()),
+            "davies_bouldin": davies_bouldin_score(x, labels),
+            "calinski_harabasz": calinski_harabasz_score(x, labels),
+            "silhouette_by_label": (values.to(s.device), _label_means(s, inv, counts), counts)}
+
+
+@torch.no_grad()
+def choose_n_clusters(x, candidates=range(2, 17), criterion: str = "silhouette", **kmeans_kw):
+    """k-means for every k in candidates, scored: (best k, {k: score}, the KMeansResult of the best k).  criterion:
+    "silhouette" (in the k-means metric) or "calinski_harabasz" - the highest wins - or "davies_bouldin" - the lowest;
+    equal scores go to the smaller k.  A fit that leaves fewer than two clusters with points scores nan and cannot win.
+    This is the check the reference's hard-coded KMeans(n_clusters=10) never had.  Keyword arguments go to kmeans()."""
+    if criterion not in CRITERIA:
+        raise ValueError(f"criterion must be one of {CRITERIA}, got {criterion!r}")
+    candidates = sorted(set(int(k) for k in candidates))
+    if not candidates or candidates[0] < 2:
+        raise ValueError("candidates must be cluster counts of at least 2")
+    sign = -1.0 if criterion == "davies_bouldin" else 1.0
+    scores, best = {}, None
+    for k in candidates:
+        res = kmeans(x, k, **kmeans_kw)
+        if int((res.counts > 0).sum()) < 2:
+            scores[k] = float("nan")
+            continue
+        if criterion == "silhouette":
+            scores[k] = silhouette_score(x, res.labels, kmeans_kw.get("metric", "euclidean"))
+        else:
+            scores[k] = (davies_bouldin_score if criterion == "davies_bouldin" else calinski_harabasz_score)(x, res.labels)
+        if best is None or sign * scores[k] > sign * scores[best[0]]:
+            best = (k, res)
+    if best is None:
+        raise ValueError("no candidate gave two clusters with points")
+    return best[0], scores, best[1]

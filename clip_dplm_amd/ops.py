@@ -1263,6 +1263,69 @@ def kmeans_step(x, c, nc=None, labels=None):
     return labels, best, sums, counts
 
 
+LABEL_DIST_MAX_P = 512         # clipk_label_dist_sums
+LABEL_DIST_MAX_G = 512         # ... labels per launch
+LABEL_DIST_MAX_LABELS = 65536  # ops.label_dist_sums: in 512-label blocks, one walk each
+LABEL_DIST_METRICS = ("euclidean", "sqeuclidean", "cosine")
+
+
+def label_dist_sums_plan(Mx: int, Ny: int):
+    """(64-query blocks, key-range splits) of the grid clipk_label_dist_sums launches: that of clipk_sim_lse_bias."""
+    return sim_lse_bias_plan(Mx, Ny)
+
+
+def label_dist_sums(x, y, labels, n_labels, metric="euclidean", nx=None, ny=None, diag_offset=-1):
+    """Per-label distance sums (include/clipk.h: clipk_label_dist_sums): out f32 [Mx, n_labels] with out[i, g] = the sum
+    of d(x_i, y_j) over the keys j with labels[j] == g.  x [Mx, P], y [Ny, P] f32, labels int32 [Ny]; a label outside
+    [0, n_labels) belongs to no column.  metric: "euclidean" (sqrt(max(nx_i + ny_j - 2 <x_i, y_j>, 0))), "sqeuclidean"
+    (without the root) or "cosine" (max(1 - <x_i, y_j>, 0): the caller passes unit rows, the norms are not read).  nx, ny:
+    the squared norms, computed here when not given.  diag_offset >= 0: row i skips key i + diag_offset (0 for a cloud
+    with itself, r0 for its rows [r0, r1) against the whole cloud); -1: nothing is skipped.
+    n_labels > 512 (up to 65536) runs in 512-label blocks, and EACH BLOCK IS A FULL WALK over the Mx x Ny tiles."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    if P > LABEL_DIST_MAX_P:
+        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {LABEL_DIST_MAX_P})")
+    if metric not in LABEL_DIST_METRICS:
+        raise ValueError(f"metric must be one of {LABEL_DIST_METRICS}, got {metric!r}")
+    if isinstance(n_labels, bool) or not isinstance(n_labels, int):
+        raise TypeError(f"n_labels must be an int, got {n_labels!r}")
+    if not 1 <= n_labels <= LABEL_DIST_MAX_LABELS:
+        raise ValueError(f"n_labels must be in [1, {LABEL_DIST_MAX_LABELS}], got {n_labels}")
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError("labels must be an int32 tensor")
+    _int32_vector("labels", labels, Ny, x.device)
+    _f32_vectors((("nx", nx, Mx), ("ny", ny, Ny)))
+    diag_offset = int(diag_offset)
+    if diag_offset < -1:
+        raise ValueError(f"diag_offset must be -1 (nothing skipped) or >= 0, got {diag_offset}")
+    for t in (x, y, labels, nx, ny):
+        if t is not None and not t.is_cuda:
+            raise ValueError("the label-distance kernel needs device tensors (there is no CPU fallback)")
+    _need_cuda(x, y, labels, nx, ny)
+    mode = LABEL_DIST_METRICS.index(metric)
+    if metric != "cosine":
+        if nx is None:
+            nx = (x * x).sum(1)
+        if ny is None:
+            ny = nx if y is x else (y * y).sum(1)
+    dev = x.device
+    lib = _lib()
+    stream = _stream()
+    blocks = []
+    for g0 in range(0, n_labels, LABEL_DIST_MAX_G):
+        G = min(LABEL_DIST_MAX_G, n_labels - g0)
+        Gp = (G + 3) // 4 * 4
+        lab = labels if g0 == 0 else labels - g0                 # the block's labels as its columns 0 .. G - 1
+        out = torch.empty((Mx, Gp), dtype=torch.float32, device=dev)
+        ws = workspace(lib.clipk_label_dist_sums_workspace(Mx, Ny, P, G), dev, "label_dist", stream)
+        check(_timed("label_dist_sums", 2.0 * Mx * Ny * (P + Gp),
+                     lambda: lib.clipk_label_dist_sums(x.data_ptr(), Mx, y.data_ptr(), Ny, P, lab.data_ptr(), G, mode,
+                                                       ptr(nx), ptr(ny), diag_offset, out.data_ptr(), ws.data_ptr(),
+                                                       ws.numel(), stream)), "clipk_label_dist_sums")
+        blocks.append(out if Gp == G else out[:, :G])
+    return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
+
+
 def ce_logits_lse(S, S2=None, columns=False, label_offset=0):
     """LSE over the rows (optionally of [S | S2]) or the columns of materialised f32 logits + the diagonal logit."""
     _need_cuda(S, S2)

@@ -1002,6 +1002,39 @@ int clipk_kmeans_step(const float* X, int N, const float* C /*[K,P] (fused)*/, i
                       int* labels /*[N] (fused)*/, float* best /*[N] (fused)*/, float* sums /*[K,P]*/,
                       float* counts /*[K]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-label sums of point-to-point distances between two f32 clouds X [Mx,P], Y [Ny,P] without the Mx x Ny matrix: what
+ * the silhouette width of a labeling is made of (clip_dplm_amd.cluster.silhouette_samples) - the quality score the
+ * reference's hard-coded KMeans(n_clusters=10) lacks, and per label the separation its analyze_embedding_collapse is after.
+ *
+ * clipk_label_dist_sums:
+ *     out[i, g] = sum over { j < Ny : labels[j] == g, j != i + diag_offset } of d_ij        i < Mx, 0 <= g < G
+ *     mode 0 (euclidean):    d_ij = sqrt(max(nx[i] + ny[j] - 2 <X_i, Y_j>, 0))
+ *     mode 1 (sqeuclidean):  d_ij = max(nx[i] + ny[j] - 2 <X_i, Y_j>, 0)
+ *     mode 2 (cosine):       d_ij = max(1 - <X_i, Y_j>, 0)       (the caller passes unit rows; nx, ny are not read, may be NULL)
+ *   labels [Ny] int32: an entry outside [0, G) belongs to no column - that is how a caller leaves points out.
+ *   nx [Mx] = |x_i|^2, ny [Ny] = |y_j|^2.
+ *   Diagonal rule: diag_offset = -1 skips nothing; diag_offset >= 0: row i skips key j = i + diag_offset - the term is
+ *   dropped, never formed and subtracted: a computed d2_ii of rounding size would enter the Euclidean sum as its square
+ *   root, about 3e-4 |x|.  A row whose skipped key lies at or beyond Ny skips nothing.  Rows [r0, r1) of a cloud against
+ *   the whole cloud: diag_offset = r0.
+ *   out [Mx, Gp] with the row stride Gp = G rounded up to a multiple of 4; the padding columns are zeros.
+ *   Kernel: the structure of clipk_kernel_sums with kbary (64 queries per workgroup, 64-key tiles on
+ *   v_mfma_f32_32x32x2_f32, the distance tile into LDS) with the one-hot of the tile's labels in place of the staged key
+ *   rows: out^T[g, q] += H^T[g, key] D[key, q] as the second MFMA product; the one-hot is staged in LDS from the labels
+ *   and never exists in memory.  G <= 64: the four waves split the 64 keys of the tile and merge in wave order; beyond,
+ *   they split the label rows.  The square root is v_sqrt_f32 (1 ulp).  Key-split slabs are summed in split order by a
+ *   finalize launch.  The grid is that of clipk_sim_lse_bias (clipk_sim_lse_bias_plan).
+ *   Supported: Mx, Ny >= 1, P % 4 == 0, P <= 512, 1 <= G <= 512, X / Y / out / workspace 16-byte aligned.
+ * Anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED before any launch and the workspace helper returns 0.
+ * Never allocates, never synchronises, capturable, no float atomics: results depend on the shapes and inputs alone. */
+size_t clipk_label_dist_sums_workspace(int Mx, int Ny, int P, int G);
+int clipk_label_dist_sums(const float* X, int Mx, const float* Y, int Ny, int P, const int* labels /*[Ny]*/, int G,
+                          int mode /* 0 euclidean, 1 sqeuclidean, 2 cosine */,
+                          const float* nx /*[Mx] = |x_i|^2*/, const float* ny /*[Ny] = |y_j|^2*/,
+                          long long diag_offset /* -1: none; else row i skips key j == i + diag_offset */,
+                          float* out /*[Mx, (G + 3) / 4 * 4]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
