@@ -82,6 +82,18 @@ __device__ __forceinline__ float live_lse2(float lse) { return fmaxf(lse * LOG2E
 // v_exp_f32 directly: every argument here is <= 0 (or -inf), so the denormal-range fix-up of exp2f() is dead weight
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// acc + the dot of one 16-byte chunk (8 bf16) of O with the same chunk of dO, element by element in memory order: the
+// summation order of delta = rowsum(dO * O) in the whole-head backward kernels.  (The dQ kernel spells the same lines
+// out: through this helper four of its instances compile to other instructions.)
+__device__ __forceinline__ float chunk_dot(float acc, const u32x4& o, const u32x4& d) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    acc += bf16_to_f32(o[e] & 0xffffu) * bf16_to_f32(d[e] & 0xffffu);
+    acc += bf16_to_f32(o[e] >> 16) * bf16_to_f32(d[e] >> 16);
+  }
+  return acc;
+}
+
 // Work-item order: the G = (blocks per sequence) x H workgroups of one batch element read the same token rows
 // (each head only D*2 bytes of a 3*H*D*2-byte row), so keep them on ONE XCD's L2: blocks b and b+8 share an XCD
 // (round-robin dispatch), hence XCD x gets batch elements x, x+8, ...  Falls back to the plain order when B % 8 != 0.
@@ -1125,12 +1137,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
       const int row = ps * (NT / 4) + r0;
       *reinterpret_cast<u32x4*>(qtile + swz64(row, ci)) = R.k[ps];
       *reinterpret_cast<u32x4*>(dotile + swz64(row, ci)) = R.v[ps];
-      float acc = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc += bf16_to_f32(R.o[ps][e] & 0xffffu) * bf16_to_f32(R.d[ps][e] & 0xffffu);
-        acc += bf16_to_f32(R.o[ps][e] >> 16) * bf16_to_f32(R.d[ps][e] >> 16);
-      }
+      float acc = chunk_dot(0.f, R.o[ps], R.d[ps]);
       acc += __shfl_xor(acc, 1, 64);
       acc += __shfl_xor(acc, 2, 64);
       if (ci == 0) {
@@ -1321,37 +1328,67 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_fused32_ker
 //
 // The dQ + dK/dV kernel pair reads q, k, v, dO twice (3.6 GB per layer at B = 1024 against 2.0 GB read once) and runs
 // 7 products and the exponentials twice; its dK/dV half gives every 64-key workgroup a prologue and an epilogue as long
-// as its sweep.  Here one workgroup (4 waves, ONE per SIMD: 512 VGPRs) owns a (batch, head): wave w holds the K / V
-// fragments of keys [64w, 64w + 64) (loaded straight from HBM in fragment layout: 16-byte chunk g + 4 ks of row li),
-// their K^T fragments (transposed LDS reads of the staged K rows) and the dK^T / dV^T accumulators in registers - 336
-// of them - and all four waves sweep the eight 32-query blocks TOGETHER: Q / dO blocks are double-buffered in LDS
-// (chunk per lane through registers, the next block requested before the sweep of the current one), delta =
-// rowsum(dO * O) is formed from the staged chunks (shares in LDS, summed in chunk order), dS goes back to LDS transposed
-// (private 4 KiB per wave) to become the B operand of dQ^T += K^T dS^T, and the four waves' dQ shares (their own keys)
-// meet in LDS once per block: written side by side, summed in wave order by all 256 threads, scaled, rounded and
-// stored.  5 products, one softmax pass, every operand read once, no atomics: bitwise reproducible.
+// as its sweep.  Here one workgroup of NW waves owns a (batch, head): wave w holds the V fragments of keys
+// [KW w, KW w + KW) (loaded straight from HBM in fragment layout: 16-byte chunk g + 4 ks of row li) and the dK^T / dV^T
+// accumulators in registers, the K rows are staged in LDS for the K^T fragments (transposed reads), and all waves sweep
+// the eight 32-query blocks TOGETHER: Q / dO blocks are double-buffered in LDS (chunk per lane through registers, the
+// next block requested before the sweep of the current one), delta = rowsum(dO * O) is formed from the staged chunks
+// (shares in LDS, summed in chunk order), dS goes back to LDS transposed (a private tile per wave) to become the B
+// operand of dQ^T += K^T dS^T.  5 products, one softmax pass, every operand read once, no atomics: bitwise reproducible.
+//
+// What NW changes.  4 (option attn_fused_waves = 4): ONE wave per SIMD with 512 VGPRs owns 64 keys; its K fragments
+// sit in registers next to the V fragments (336 resident registers with the accumulators), which leaves none for the
+// K rows of the next head: they are requested at the top of the head, in two instalments.  The four waves' dQ shares
+// (their own keys) meet in LDS once per block: written side by side, summed in wave order by all 256 threads, scaled,
+// rounded and stored ("dQ from per-wave shares" in the sweep).  The SIMD is 0.41 busy: one wave, every LDS / MFMA latency exposed.
+// 8 (the default): two waves per SIMD with 256 registers each; a wave owns 32 keys - half the fragments and accumulators
+// (144 resident registers instead of 288) - so that the second wave of a SIMD fills the first one's dependency stalls.
+// The K row fragments come from the staged rows as well, and the rows are requested with the rest of the head, under
+// the previous head's write-out.  Every wave reads the Q / dO fragments of the whole 32-query block for its 32 keys
+// (twice the LDS reads per key), so dQ is NOT summed from per-wave shares: after a barrier the waves compute complete
+// (d tile, query tile) outputs over all keys from the eight dS^T tiles ("dQ as complete tiles"); the shares' region holds
+// one 32-row bf16 image, three barriers per step.  948 against 1132 us per layer at B = 1024 - with per-wave dQ shares
+// added pairwise it was 1173 (profiles/r03/attn96_eight_waves_ab_v1.txt).
 // =================================================================================================
-constexpr int F96_QB = 32;                                 // queries per step
-__host__ __device__ constexpr size_t lds_fused96() {
-  // K rows (then the dK / dV images) | the four dQ shares (4 x 32 x 100 f32) | 2 x (Q, dO) blocks | 4 x dS^T |
-  // lse, -delta | delta shares
-  return (size_t)FUSED_LMAX * Geo<96>::RS + 4 * F96_QB * 100 * 4 + 4 * F96_QB * Geo<96>::RS + 4 * 4096 +
-         2 * FUSED_LMAX * 4 + F96_QB * 12 * 4;
-}
+template <int NW>
+struct Fused96 {
+  static constexpr int D = 96, RS = Geo<96>::RS, KS = Geo<96>::KS, DT = Geo<96>::DT, NCH = Geo<96>::NCH;
+  static constexpr int LQ = FUSED_LMAX, ILD = D + 4;
+  static constexpr int QB = 32;                            // queries per step
+  static constexpr int NT = 64 * NW;
+  static constexpr int KTW = 16 / NW, KW = 16 * KTW, NCK = KW / 32;   // per wave: 16-key tiles, keys, 32-key chunks
+  static constexpr int NPS = (QB * NCH + NT - 1) / NT;     // Q / dO / O block staging passes
+  static constexpr int NKP = LQ * NCH / NT;                // K-row chunk tasks per thread (12 / 6) ...
+  static constexpr int NKB = NW == 4 ? 2 : 1;              // ... which pass through registers in this many instalments
+  // LDS, byte offsets
+  static constexpr int KTILE = 0;                          // [256][RS] K rows (transposed fragments); later dK / dV images
+  static constexpr int DQ = KTILE + LQ * RS;               // 4: [4 waves][32 q][ILD] f32 dQ shares; 8: [32 q][RS] bf16 dQ rows of the step
+  static constexpr int QD = DQ + 4 * QB * ILD * 4;         // [2 buffers][Q block | dO block][32][RS]
+  static constexpr int DST = QD + 4 * QB * RS;             // [NW waves][KW keys][64 B] dS^T
+  static constexpr int LSE = DST + NW * KW * 64;           // [256] f32 lse * log2(e); +inf past the end
+  static constexpr int DL = LSE + LQ * 4;                  // [256] f32 -delta
+  static constexpr int PART = DL + LQ * 4;                 // [32][12] f32 delta shares of the block being staged
+  static constexpr int BYTES = PART + QB * NCH * 4;
+};
+static_assert(Fused96<4>::BYTES == Fused96<8>::BYTES, "one LDS layout for both wave counts");
+__host__ __device__ constexpr size_t lds_fused96() { return Fused96<8>::BYTES; }
 
-__global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
-  constexpr int D = 96, RS = Geo<96>::RS, KS = 3, DT = 6, NCH = 12, LQ = FUSED_LMAX, QB = F96_QB, ILD = D + 4;
-  constexpr int KTW = 4, KW = 64, NCK = 2;                 // per wave: four 16-key tiles = two 32-key chunks
-  constexpr int NKP = LQ * NCH / 256;                      // K-row chunk tasks per thread (12)
+template <int NW>
+__global__ __launch_bounds__(64 * NW, 1) void attn_bwd_fused96_kernel(const AP p) {
+  typedef Fused96<NW> G;
+  constexpr int D = G::D, RS = G::RS, KS = G::KS, DT = G::DT, NCH = G::NCH, LQ = G::LQ, QB = G::QB, ILD = G::ILD;
+  constexpr int NT = G::NT, KTW = G::KTW, KW = G::KW, NCK = G::NCK, NPS = G::NPS, NKP = G::NKP, NKB = G::NKB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ktile = smem;                                      // [256][RS] K rows (transposed fragments); later dK / dV images
-  float* share = reinterpret_cast<float*>(smem + LQ * RS); // [4 waves][32 q][ILD] f32
-  char* qd = smem + LQ * RS + 4 * QB * ILD * 4;            // [2 buffers][Q block | dO block][32][RS]
-  char* dst_all = qd + 4 * QB * RS;                        // [4 waves][2 chunks][32 keys][64 B]
-  float* lse_l = reinterpret_cast<float*>(dst_all + 4 * 4096);   // [256] lse * log2(e); +inf past the end
-  float* dl_l = lse_l + LQ;                                // [256] -delta
-  float* part = dl_l + LQ;                                 // [32][12] delta shares of the block being staged
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  char* ktile = smem + G::KTILE;
+  float* share = reinterpret_cast<float*>(smem + G::DQ);
+  char* dqimg = smem + G::DQ;
+  char* qd = smem + G::QD;
+  char* dst_all = smem + G::DST;
+  float* lse_l = reinterpret_cast<float*>(smem + G::LSE);
+  float* dl_l = reinterpret_cast<float*>(smem + G::DL);
+  float* part = reinterpret_cast<float*>(smem + G::PART);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = NW == 8 ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;   // (eight waves: held in an SGPR)
   const int g = lane >> 4, li = lane & 15;
   const int H = p.H;
   const long tokstride = 3L * H * D, ostride = (long)H * D;
@@ -1368,14 +1405,14 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
     L_ = p.L;
     row0_ = seq_rows(p, b_, L_);
   };
-  // Q / dO / O block staging: 32 rows x 12 chunks = 384 (row, chunk) tasks per tensor, two passes of 256 threads (the
-  // second pass of threads >= 128 repeats a task of the first; its store is skipped)
-  u32x4 cq[2], cd[2], co[2];
+  // Q / dO / O block staging: 32 rows x 12 chunks = 384 (row, chunk) tasks per tensor in NPS passes of NT threads (a
+  // task past 384 repeats task - 256; its store is skipped)
+  u32x4 cq[NPS], cd[NPS], co[NPS];
   auto issue_block = [&](int j) {
     const int t = tid + opaque_zero();
 #pragma unroll
-    for (int ps = 0; ps < 2; ++ps) {
-      int idl = ps * 256 + t; idl = idl < QB * NCH ? idl : idl - 256;
+    for (int ps = 0; ps < NPS; ++ps) {
+      int idl = ps * NT + t; idl = idl < QB * NCH ? idl : idl - 256;
       const int r = idl / NCH, ch = idl - r * NCH;
       int row = j * QB + r; row = row < lL ? row : lL - 1;
       cq[ps] = *reinterpret_cast<const u32x4*>(lq + ((unsigned int)row * 3u * HD + 8u * ch));
@@ -1387,24 +1424,36 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
     const int t = tid + opaque_zero();
     char* qt = qd + (j & 1) * (2 * QB * RS);
 #pragma unroll
-    for (int ps = 0; ps < 2; ++ps) {
-      const int idl = ps * 256 + t;
+    for (int ps = 0; ps < NPS; ++ps) {
+      const int idl = ps * NT + t;
       if (idl < QB * NCH) {
         const int r = idl / NCH, ch = idl - r * NCH;
         *reinterpret_cast<u32x4*>(qt + r * RS + ch * 16) = cq[ps];
         *reinterpret_cast<u32x4*>(qt + QB * RS + r * RS + ch * 16) = cd[ps];
-        float acc = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          acc += bf16_to_f32(co[ps][e] & 0xffffu) * bf16_to_f32(cd[ps][e] & 0xffffu);
-          acc += bf16_to_f32(co[ps][e] >> 16) * bf16_to_f32(cd[ps][e] >> 16);
-        }
-        part[idl] = acc;
+        part[idl] = chunk_dot(0.f, co[ps], cd[ps]);
       }
     }
   };
-  // K / V fragments of this wave's keys straight from HBM in fragment layout (16-byte chunk g + 4 ks of row li), the
-  // K rows for the transposed fragments (chunk per lane, through registers), lse of row tid, the key-mask bias
+  // The head's K rows on their way to LDS, chunk per lane through registers, NKP / NKB tasks per thread at a time
+  u32x4 kr[NKP / NKB];
+  auto request_krows = [&](int t, int i, const unsigned short* kb, int L_) {
+#pragma unroll
+    for (int ps = 0; ps < NKP / NKB; ++ps) {
+      const int idl = (i * (NKP / NKB) + ps) * NT + t;
+      const int r = idl / NCH, ch = idl - r * NCH;
+      kr[ps] = *reinterpret_cast<const u32x4*>(kb + ((unsigned int)(r < L_ ? r : L_ - 1) * 3u * HD + 8u * ch));
+    }
+  };
+  auto stage_krows = [&](int t, int i) {
+#pragma unroll
+    for (int ps = 0; ps < NKP / NKB; ++ps) {
+      const int idl = (i * (NKP / NKB) + ps) * NT + t;
+      const int r = idl / NCH, ch = idl - r * NCH;
+      *reinterpret_cast<u32x4*>(ktile + r * RS + ch * 16) = kr[ps];
+    }
+  };
+  // V (four waves: and K) fragments of this wave's keys straight from HBM in fragment layout (16-byte chunk g + 4 ks
+  // of row li), lse of row tid, the key-mask bias
   bf16x8 kf[KTW][KS], vf[KTW][KS];
   float kbias[KTW], lse_r;
   auto issue_head = [&](int w) {                           // sets lq / ldo / lo / lL to head w and requests its rows
@@ -1424,16 +1473,20 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const unsigned int off = (unsigned int)row * 3u * HD + (unsigned int)(ks * 32 + g * 8);
-        kf[kt][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lq + (off + HD)));
+        if constexpr (NW == 4) kf[kt][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lq + (off + HD)));
         vf[kt][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lq + (off + 2u * HD)));
       }
     }
-    lse_r = p.lse[stat_at(p, b_, h_, H, L_, row0_, tid < L_ ? tid : L_ - 1)];
+    const int lr = (NT > LQ && tid >= LQ) ? LQ - 1 : tid;
+    lse_r = p.lse[stat_at(p, b_, h_, H, L_, row0_, lr < L_ ? lr : L_ - 1)];
+    // Eight waves: the K rows are requested HERE, with the rest of the head, so that they land under the previous head's
+    // write-out instead of at the top of this one
+    if constexpr (NW == 8) request_krows(tid + opaque_zero(), 0, lq + HD, L_);
     issue_block(0);
   };
 
   const int trow = 4 * g + (li >> 2), tcolb = 8 * (li & 3);
-  char* dst = dst_all + wid * 4096;
+  char* dst = dst_all + wid * (KW * 64);
   int off_dw[2];                                           // dS^T write: key row li of a 16-key tile, queries qq*16 + 4g ..
 #pragma unroll
   for (int qq = 0; qq < 2; ++qq) off_dw[qq] = swz64(li, qq * 2 + (g >> 1)) + 8 * (g & 1);
@@ -1464,29 +1517,22 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
         if (ok) p.delta[stat_at(p, b, h, H, L, row0, q)] = acc;
       }
     };
-    // ---- K rows -> LDS for the transposed fragments (chunk per lane through registers; L2-hot: the same rows came
-    // through as fragments while the previous head was written out), block 0 -> buffer 0, lse
+    // ---- K rows -> LDS for the transposed fragments, block 0 -> buffer 0, lse.  (Four waves: the rows are asked for
+    // only now; L2-hot: the same rows came through as fragments while the previous head was written out)
     {
       const int t = tid + opaque_zero();
-      const unsigned short* kb_ = p.qkv + row0 * tokstride + (long)h * D + HD;
+      if constexpr (NW == 4) {
+        const unsigned short* kb_ = p.qkv + row0 * tokstride + (long)h * D + HD;
 #pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        u32x4 kr[NKP / 2];
-#pragma unroll
-        for (int ps = 0; ps < NKP / 2; ++ps) {
-          const int idl = (half * (NKP / 2) + ps) * 256 + t;
-          const int r = idl / NCH, ch = idl - r * NCH;
-          kr[ps] = *reinterpret_cast<const u32x4*>(kb_ + ((unsigned int)(r < L ? r : L - 1) * 3u * HD + 8u * ch));
+        for (int i = 0; i < NKB; ++i) {
+          request_krows(t, i, kb_, L);
+          stage_krows(t, i);
         }
-#pragma unroll
-        for (int ps = 0; ps < NKP / 2; ++ps) {
-          const int idl = (half * (NKP / 2) + ps) * 256 + t;
-          const int r = idl / NCH, ch = idl - r * NCH;
-          *reinterpret_cast<u32x4*>(ktile + r * RS + ch * 16) = kr[ps];
-        }
+      } else {
+        stage_krows(t, 0);
       }
     }
-    lse_l[tid] = tid < L ? live_lse2(lse_r) : INFINITY;    // p = 2^-inf = 0 past the end
+    if (NT == LQ || tid < LQ) lse_l[tid] = tid < L ? live_lse2(lse_r) : INFINITY;    // p = 2^-inf = 0 past the end
     store_block(0);
     __syncthreads();
     finish_delta(0);
@@ -1500,13 +1546,19 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
     const bool wave_live = wid * KW < L;                   // this wave owns at least one real key
     unsigned short* dqb = p.dqkv + row0 * tokstride + (long)h * D;
 
+
 #pragma unroll 1
     for (int j = 0; j < nblk; ++j) {
-      if (j + 1 < nblk) issue_block(j + 1);                // (workgroup-uniform branch; the last step requests nothing)
+      // The next block's request.  Eight waves: UNCONDITIONAL (the last step re-requests its own block and stages it into
+      // the idle buffer): with `if (j + 1 < nblk)` around the request and around the staging hipcc cannot pair the two
+      // branches, assumes the loads may still be in flight at the next request and waits vmcnt(0) there - for the block
+      // it has just asked for.  Four waves: a workgroup-uniform branch; the last step requests nothing.
+      if constexpr (NW == 8) issue_block(j + 1 < nblk ? j + 1 : j);
+      else if (j + 1 < nblk) issue_block(j + 1);
       const char* qt_ = qd + (j & 1) * (2 * QB * RS);
       const char* dt_ = qt_ + QB * RS;
-      if (wave_live) {
-        u32x2 pk[2][KTW], dsk[2][KTW];
+      u32x2 pk[2][KTW], dsk[2][KTW];
+      const auto p_ds = [&]() {
 #pragma unroll
         for (int qq = 0; qq < 2; ++qq) {
           // rows of the accumulators are queries (4g + r), columns are this lane's key; dP starts at -delta of its row,
@@ -1521,9 +1573,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
             const bf16x8 da = row_frag(dt_, RS, qq * 16 + li, ks, lane);
 #pragma unroll
             for (int kt = 0; kt < KTW; ++kt) {
-              s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf[kt][ks], s[kt], 0, 0, 0);
+              if constexpr (NW == 4) s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf[kt][ks], s[kt], 0, 0, 0);
+              else s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, row_frag(ktile, RS, wid * KW + kt * 16 + li, ks, lane), s[kt], 0, 0, 0);
               dp[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf[kt][ks], dp[kt], 0, 0, 0);
             }
+            // (eight waves: fragments of one k-step at a time: the SIMD's other wave hides the reads)
+            if constexpr (NW == 8) __builtin_amdgcn_sched_barrier(0);
           }
           const f32x4 ls = *reinterpret_cast<const f32x4*>(lse_l + j * QB + qq * 16 + 4 * g);
 #pragma unroll
@@ -1537,15 +1592,21 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
             pk[qq][kt] = u32x2{pack_bf16x2(s[kt][0], s[kt][1]), pack_bf16x2(s[kt][2], s[kt][3])};
             dsk[qq][kt] = u32x2{pack_bf16x2(dp[kt][0], dp[kt][1]), pack_bf16x2(dp[kt][2], dp[kt][3])};
           }
+          // (eight waves: one 16-query tile at a time: the second one's 16 accumulator registers reuse the first one's)
+          if constexpr (NW == 8) __builtin_amdgcn_sched_barrier(0);
         }
-        // dS^T -> the wave's private [key][query] tiles first: the transposed read-back has the dV / dK block to land
+      };
+      // dS^T -> the wave's private [key][query] tiles
+      const auto write_dst = [&]() {
 #pragma unroll
         for (int kt = 0; kt < KTW; ++kt)
 #pragma unroll
           for (int qq = 0; qq < 2; ++qq)
-            *reinterpret_cast<u32x2*>(dst + (kt >> 1) * 2048 + (kt & 1) * 1024 + off_dw[qq]) = dsk[qq][kt];
-        // dV^T[d][key] += dO^T[d][32 q] P[32 q][key], dK^T += Q^T dS: ONE transposed fragment pair per d tile for all
-        // four key tiles (the fragments do not depend on the key tile)
+            *reinterpret_cast<u32x2*>(dst + kt * 1024 + off_dw[qq]) = dsk[qq][kt];
+      };
+      // dV^T[d][key] += dO^T[d][32 q] P[32 q][key], dK^T += Q^T dS: ONE transposed fragment pair per d tile for all of
+      // the wave's key tiles (the fragments do not depend on the key tile)
+      const auto dvdk = [&]() {
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
           const bf16x8 dot_f = tr_frag(dt_, RS, trow, dt * 32 + tcolb);       // dO^T[d tile][32 q]
@@ -1557,371 +1618,126 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused96_kernel(const AP p) {
             dv[dt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot_f, pbf, dv[dt][kt], 0, 0, 0);
             dk[dt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt_f, dsf, dk[dt][kt], 0, 0, 0);
           }
-        }
-      }
-      // dQ^T[d][q] += K^T[d][32 keys of chunk c] dS^T[32 keys][q], one 16-query tile at a time (24 accumulator registers
-      // instead of 48; the wave's own dS^T writes: no barrier needed), then this wave's share of dQ (its keys only) for
-      // block j as [q][d] f32 rows (zeros from a wave without keys)
-      float* sh = share + wid * (QB * ILD);
-#pragma unroll
-      for (int qq = 0; qq < 2; ++qq) {
-        f32x4 dq[DT];
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (wave_live) {
-#pragma unroll
-          for (int c = 0; c < NCK; ++c) {
-            const bf16x8 dsb = tr_frag_off(dst + c * 2048, swz64(trow, qq * 2 + ((li & 3) >> 1)) + 8 * (li & 1));
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-              // K^T[d tile][32 keys of chunk c]: re-read from the staged K rows (12 resident fragments would cost 48
-              // registers the sweep does not have)
-              const bf16x8 ktf = tr_frag(ktile, RS, wid * KW + c * 32 + trow, dt * 32 + tcolb);
-              dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsb, dq[dt], 0, 0, 0);
-            }
-          }
-        }
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-          *reinterpret_cast<f32x4*>(sh + (qq * 16 + li) * ILD + dt * 16 + 4 * g) = dq[dt];
-      }
-      if (j + 1 < nblk) store_block(j + 1);                // the other buffer
-      __syncthreads();
-      // ---- sum the four shares in wave order, scale, round, store: thread t -> query t / 8, 12 head dims
-      {
-        const int r = tid >> 3, c0 = (tid & 7) * 12;
-        f32x4 a[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) a[i] = *reinterpret_cast<const f32x4*>(share + r * ILD + c0 + 4 * i);
-#pragma unroll
-        for (int ww = 1; ww < 4; ++ww)
-#pragma unroll
-          for (int i = 0; i < 3; ++i) a[i] += *reinterpret_cast<const f32x4*>(share + ww * (QB * ILD) + r * ILD + c0 + 4 * i);
-        const int q = j * QB + r;
-        if (q < L) {
-          unsigned short* dqrow = dqb + (unsigned int)q * 3u * HD + c0;
-#pragma unroll
-          for (int i = 0; i < 3; ++i) {
-            u32x2 w2;
-            w2[0] = pack_bf16x2(a[i][0] * p.scale, a[i][1] * p.scale);
-            w2[1] = pack_bf16x2(a[i][2] * p.scale, a[i][3] * p.scale);
-            *reinterpret_cast<u32x2*>(dqrow + 4 * i) = w2;
-          }
-        }
-      }
-      if (j + 1 < nblk) finish_delta(j + 1);
-      __syncthreads();
-    }
-
-    // ---- the next head's rows: K / V fragment registers are free now; they land under the write-out below
-    issue_head(wnext);
-
-    // ---- dK^T (x scale) and dV^T accumulators -> bf16 [key][d] images (one after the other, over the shares) -> rows
-#pragma unroll 1
-    for (int which = 0; which < 2; ++which) {
-#pragma unroll
-      for (int kt = 0; kt < KTW; ++kt)
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          const f32x4 v = which == 0 ? dk[dt][kt] * p.scale : dv[dt][kt];
-          u32x2 wv;
-          wv[0] = pack_bf16x2(v[0], v[1]);
-          wv[1] = pack_bf16x2(v[2], v[3]);
-          *reinterpret_cast<u32x2*>(ktile + (wid * KW + kt * 16 + li) * RS + (dt * 16 + 4 * g) * 2) = wv;
-        }
-      __syncthreads();
-      {
-        const int t = tid + opaque_zero();
-#pragma unroll
-        for (int ps = 0; ps < NKP; ++ps) {
-          const int idl = ps * 256 + t;
-          const int r = idl / NCH, ch = idl - r * NCH;
-          if (r < L)
-            *reinterpret_cast<u32x4*>(dqb + ((unsigned int)r * 3u * HD + (unsigned int)(which + 1) * HD + 8u * ch)) =
-                *reinterpret_cast<const u32x4*>(ktile + r * RS + ch * 16);
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// =================================================================================================
-// The same backward with EIGHT waves (two per SIMD, 256 registers each): a wave owns 32 keys - half the fragments and
-// accumulators (144 resident registers instead of 288) - so that the second wave of a SIMD fills the first one's
-// dependency stalls (the 4-wave kernel keeps a SIMD 0.41 busy: one wave, every LDS / MFMA latency exposed).  Every wave
-// reads the Q / dO fragments of the whole 32-query block for its 32 keys (twice the LDS reads per key of the 4-wave
-// kernel), so dQ is NOT summed from per-wave shares here: after a barrier the waves compute complete (d tile, query tile)
-// outputs over all keys from the eight dS^T tiles (12 tiles: two each for waves 0-3, one each for waves 4-7 = three per
-// SIMD).  Same LDS layout as the 4-wave kernel (the shares' region holds one 32-row bf16 image), three barriers per
-// step, bitwise reproducible.  Everything else (staging, prefetch of the next head, write-out) as above.
-// The default for hd 96 (option attn_fused_waves = 4 keeps the 4-wave kernel): 948 against 1132 us per layer at B = 1024 -
-// with per-wave dQ shares added pairwise it was 1173 (profiles/r03/attn96_eight_waves_ab_v1.txt).
-// =================================================================================================
-__global__ __launch_bounds__(512, 1) void attn_bwd_fused96w8_kernel(const AP p) {
-  constexpr int D = 96, RS = Geo<96>::RS, KS = 3, DT = 6, NCH = 12, LQ = FUSED_LMAX, QB = F96_QB, ILD = D + 4;
-  constexpr int NT = 512, KTW = 2, KW = 32;                // per wave: two 16-key tiles = one 32-key chunk
-  constexpr int NKP = LQ * NCH / NT;                       // K-row chunk tasks per thread (6)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ktile = smem;                                      // [256][RS] K rows (transposed fragments); later dK / dV images
-  char* dqimg = smem + LQ * RS;                            // [32 q][RS] bf16 dQ rows of the step (where the 4-wave kernel keeps its shares)
-  char* qd = smem + LQ * RS + 4 * QB * ILD * 4;            // [2 buffers][Q block | dO block][32][RS]
-  char* dst_all = qd + 4 * QB * RS;                        // [8 waves][32 keys][64 B]
-  float* lse_l = reinterpret_cast<float*>(dst_all + 4 * 4096);   // [256] lse * log2(e); +inf past the end
-  float* dl_l = lse_l + LQ;                                // [256] -delta
-  float* part = dl_l + LQ;                                 // [32][12] delta shares of the block being staged
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, li = lane & 15;
-  const int H = p.H;
-  const long tokstride = 3L * H * D, ostride = (long)H * D;
-  const unsigned int HD = (unsigned int)(H * D);
-  const float c2 = p.scale * LOG2E;
-  const int nheads = p.B * H;
-
-  const unsigned short *lq = nullptr, *ldo = nullptr, *lo = nullptr;
-  int lL = 1;
-  auto point_at = [&](int w, int& L_, long& row0_, int& b_, int& h_) {
-    int blk_;
-    work_item_at(w, 1, H, p.B, blk_, h_, b_);
-    L_ = p.L;
-    row0_ = seq_rows(p, b_, L_);
-  };
-  // Q / dO / O block staging: 32 rows x 12 chunks = 384 (row, chunk) tasks per tensor, one per thread (threads >= 384
-  // repeat a task; their stores are skipped)
-  u32x4 cq, cd, co;
-  auto issue_block = [&](int j) {
-    const int t = tid + opaque_zero();
-    const int idl = t < QB * NCH ? t : t - 256;
-    const int r = idl / NCH, ch = idl - r * NCH;
-    int row = j * QB + r; row = row < lL ? row : lL - 1;
-    cq = *reinterpret_cast<const u32x4*>(lq + ((unsigned int)row * 3u * HD + 8u * ch));
-    cd = *reinterpret_cast<const u32x4*>(ldo + ((unsigned int)row * HD + 8u * ch));
-    co = *reinterpret_cast<const u32x4*>(lo + ((unsigned int)row * HD + 8u * ch));
-  };
-  auto store_block = [&](int j) {                          // -> buffer j & 1, delta shares -> part
-    const int t = tid + opaque_zero();
-    char* qt = qd + (j & 1) * (2 * QB * RS);
-    if (t < QB * NCH) {
-      const int r = t / NCH, ch = t - r * NCH;
-      *reinterpret_cast<u32x4*>(qt + r * RS + ch * 16) = cq;
-      *reinterpret_cast<u32x4*>(qt + QB * RS + r * RS + ch * 16) = cd;
-      float acc = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc += bf16_to_f32(co[e] & 0xffffu) * bf16_to_f32(cd[e] & 0xffffu);
-        acc += bf16_to_f32(co[e] >> 16) * bf16_to_f32(cd[e] >> 16);
-      }
-      part[t] = acc;
-    }
-  };
-  bf16x8 vf[KTW][KS];
-  u32x4 kr[NKP];                                           // the head's K rows, chunk per lane, on their way to LDS
-  float kbias[KTW], lse_r;
-  auto issue_head = [&](int w) {                           // sets lq / ldo / lo / lL to head w and requests its rows
-    int L_, b_, h_;
-    long row0_;
-    point_at(w, L_, row0_, b_, h_);
-    if (L_ <= 0) { L_ = 1; row0_ = row0_ > 0 ? row0_ - 1 : 0; }   // empty sequence: an in-range dummy row, never used
-    lL = L_;
-    lq = p.qkv + row0_ * tokstride + (long)h_ * D;
-    ldo = p.dout + row0_ * ostride + (long)h_ * D;
-    lo = p.out + row0_ * ostride + (long)h_ * D;
-#pragma unroll
-    for (int kt = 0; kt < KTW; ++kt) {
-      const int key = wid * KW + kt * 16 + li;
-      const int row = key < L_ ? key : L_ - 1;
-      kbias[kt] = (key < L_ && (!p.key_mask || p.key_mask[row0_ + row])) ? 0.f : -INFINITY;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const unsigned int off = (unsigned int)row * 3u * HD + (unsigned int)(ks * 32 + g * 8);
-        vf[kt][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lq + (off + 2u * HD)));
-      }
-    }
-    const int lr = tid < LQ ? tid : LQ - 1;
-    lse_r = p.lse[stat_at(p, b_, h_, H, L_, row0_, lr < L_ ? lr : L_ - 1)];
-    // the K rows for the transposed (and, in this kernel, the row) fragments: requested HERE, with the rest of the head,
-    // so that they land under the previous head's write-out instead of at the top of this one
-    {
-      const int t = tid + opaque_zero();
-#pragma unroll
-      for (int ps = 0; ps < NKP; ++ps) {
-        const int idl = ps * NT + t;
-        const int r = idl / NCH, ch = idl - r * NCH;
-        kr[ps] = *reinterpret_cast<const u32x4*>(lq + HD + ((unsigned int)(r < L_ ? r : L_ - 1) * 3u * HD + 8u * ch));
-      }
-    }
-    issue_block(0);
-  };
-
-  const int trow = 4 * g + (li >> 2), tcolb = 8 * (li & 3);
-  char* dst = dst_all + wid * 2048;
-  int off_dw[2];                                           // dS^T write: key row li of a 16-key tile, queries qq*16 + 4g ..
-#pragma unroll
-  for (int qq = 0; qq < 2; ++qq) off_dw[qq] = swz64(li, qq * 2 + (g >> 1)) + 8 * (g & 1);
-
-  int w = blockIdx.x;
-  if (w < nheads) issue_head(w);
-  for (; w < nheads; w += gridDim.x) {
-    int L, b, h;
-    long row0;
-    point_at(w, L, row0, b, h);
-    const int wnext = w + (int)gridDim.x < nheads ? w + (int)gridDim.x : w;   // last head: re-request its own rows
-    if (L <= 0) {                                          // (workgroup-uniform) empty sequence of a packed batch
-      issue_head(wnext);
-      continue;
-    }
-    const int nblk = (L + QB - 1) / QB;
-    const auto finish_delta = [&](int j) {                 // after the barrier that follows store_block(j)
-      if (tid < QB) {
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) acc += part[tid * NCH + c];
-        const int q = j * QB + tid;
-        const bool ok = q < L;
-        dl_l[q] = ok ? -acc : 0.f;                         // NEGATED: the dP accumulators start from it
-        if (ok) p.delta[stat_at(p, b, h, H, L, row0, q)] = acc;
-      }
-    };
-    // ---- K rows -> LDS for the transposed fragments, block 0 -> buffer 0, lse
-    {
-      const int t = tid + opaque_zero();
-#pragma unroll
-      for (int ps = 0; ps < NKP; ++ps) {
-        const int idl = ps * NT + t;
-        const int r = idl / NCH, ch = idl - r * NCH;
-        *reinterpret_cast<u32x4*>(ktile + r * RS + ch * 16) = kr[ps];
-      }
-    }
-    if (tid < LQ) lse_l[tid] = tid < L ? live_lse2(lse_r) : INFINITY;    // p = 2^-inf = 0 past the end
-    store_block(0);
-    __syncthreads();
-    finish_delta(0);
-    __syncthreads();
-
-    f32x4 dk[DT][KTW], dv[DT][KTW];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int kt = 0; kt < KTW; ++kt) { dk[dt][kt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt][kt] = dk[dt][kt]; }
-    const bool wave_live = wid * KW < L;                   // this wave owns at least one real key
-    unsigned short* dqb = p.dqkv + row0 * tokstride + (long)h * D;
-
-#pragma unroll 1
-    for (int j = 0; j < nblk; ++j) {
-      // UNCONDITIONAL (the last step re-requests its own block and stages it into the idle buffer): with `if (j + 1 <
-      // nblk)` around the request and around the staging hipcc cannot pair the two branches, assumes the loads may
-      // still be in flight at the next request and waits vmcnt(0) there - for the block it has just asked for
-      issue_block(j + 1 < nblk ? j + 1 : j);
-      const char* qt_ = qd + (j & 1) * (2 * QB * RS);
-      const char* dt_ = qt_ + QB * RS;
-      u32x2 pk[2][KTW], dsk[2][KTW];
-#pragma unroll
-      for (int qq = 0; qq < 2; ++qq)
-#pragma unroll
-        for (int kt = 0; kt < KTW; ++kt) { pk[qq][kt] = u32x2{0u, 0u}; dsk[qq][kt] = pk[qq][kt]; }
-      if (wave_live) {
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq) {
-          const f32x4 nd = *reinterpret_cast<const f32x4*>(dl_l + j * QB + qq * 16 + 4 * g);
-          f32x4 s[KTW], dp[KTW];
-#pragma unroll
-          for (int kt = 0; kt < KTW; ++kt) { s[kt] = f32x4{kbias[kt], kbias[kt], kbias[kt], kbias[kt]}; dp[kt] = nd; }
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) {
-            const bf16x8 qa = row_frag(qt_, RS, qq * 16 + li, ks, lane);
-            const bf16x8 da = row_frag(dt_, RS, qq * 16 + li, ks, lane);
-#pragma unroll
-            for (int kt = 0; kt < KTW; ++kt) {
-              s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, row_frag(ktile, RS, wid * KW + kt * 16 + li, ks, lane), s[kt], 0, 0, 0);
-              dp[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf[kt][ks], dp[kt], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);             // (fragments of one k-step at a time: the SIMD's other wave hides the reads)
-          }
-          const f32x4 ls = *reinterpret_cast<const f32x4*>(lse_l + j * QB + qq * 16 + 4 * g);
-#pragma unroll
-          for (int kt = 0; kt < KTW; ++kt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float pv = fast_exp2(s[kt][r] * c2 - ls[r]);
-              s[kt][r] = pv;                               // P
-              dp[kt][r] = pv * dp[kt][r];                  // dS = P (dP - delta)
-            }
-            pk[qq][kt] = u32x2{pack_bf16x2(s[kt][0], s[kt][1]), pack_bf16x2(s[kt][2], s[kt][3])};
-            dsk[qq][kt] = u32x2{pack_bf16x2(dp[kt][0], dp[kt][1]), pack_bf16x2(dp[kt][2], dp[kt][3])};
-          }
-          __builtin_amdgcn_sched_barrier(0);               // one 16-query tile at a time: the second one's 16 accumulator
-        }                                                  // registers reuse the first one's
-      }
-      // dS^T -> the wave's private [32 keys][32 queries] tile (zeros from a wave without keys: the dQ tiles below read
-      // all eight tiles)
-#pragma unroll
-      for (int kt = 0; kt < KTW; ++kt)
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq)
-          *reinterpret_cast<u32x2*>(dst + kt * 1024 + off_dw[qq]) = dsk[qq][kt];
-      // dV^T[d][key] += dO^T[d][32 q] P[32 q][key], dK^T += Q^T dS
-      const auto dvdk = [&]() {
-        if (wave_live) {
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) {
-            const bf16x8 dot_f = tr_frag(dt_, RS, trow, dt * 32 + tcolb);     // dO^T[d tile][32 q]
-            const bf16x8 qt_f = tr_frag(qt_, RS, trow, dt * 32 + tcolb);      // Q^T
-#pragma unroll
-            for (int kt = 0; kt < KTW; ++kt) {
-              const bf16x8 pbf = __builtin_bit_cast(bf16x8, u32x4{pk[0][kt][0], pk[0][kt][1], pk[1][kt][0], pk[1][kt][1]});
-              const bf16x8 dsf = __builtin_bit_cast(bf16x8, u32x4{dsk[0][kt][0], dsk[0][kt][1], dsk[1][kt][0], dsk[1][kt][1]});
-              dv[dt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot_f, pbf, dv[dt][kt], 0, 0, 0);
-              dk[dt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt_f, dsf, dk[dt][kt], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
+          if constexpr (NW == 8) __builtin_amdgcn_sched_barrier(0);
         }
       };
-      __builtin_amdgcn_sched_barrier(0);
-      dvdk();
-      __builtin_amdgcn_sched_barrier(0);
-      store_block(j + 1);                                  // the other buffer
-      __syncthreads();                                     // every wave's dS^T tile is written
-      // dQ^T = K^T dS^T as COMPLETE (d tile, 16-query tile) outputs over all keys: waves 0-3 take d tiles 0-3 (both query
-      // tiles), waves 4-7 d tiles 4 / 5 (one query tile each) - three tiles per SIMD - reading the K^T fragments of the
-      // staged K rows and the dS^T tile of the wave that owns each 32-key chunk.  No shares, no sums over waves: the
-      // accumulator IS the gradient; it goes (scaled, bf16) into a [32 q][RS] image and leaves as whole rows.
-      {
-        const int dt0 = wid < 4 ? wid : 4 + ((wid - 4) >> 1);
-        const int nq = wid < 4 ? 2 : 1, q0t = wid < 4 ? 0 : (wid & 1);
-        f32x4 dq[2];
-        dq[0] = f32x4{0.f, 0.f, 0.f, 0.f}; dq[1] = dq[0];
-        // all eight 32-key chunks, unrolled (a chunk past the end multiplies clamped K rows by a zero dS^T tile): as a
-        // run-time loop over the live chunks every fragment read waited out its own LDS latency - 3160 cycles per step
+      if constexpr (NW == 4) {
+        // a wave without keys skips the products; the dS^T tile goes first: the transposed read-back has the dV / dK
+        // block to land
+        if (wave_live) {
+          p_ds();
+          write_dst();
+          dvdk();
+        }
+        // ---- dQ FROM PER-WAVE SHARES (four waves).  dQ^T[d][q] += K^T[d][32 keys of chunk c] dS^T[32 keys][q], one
+        // 16-query tile at a time (24 accumulator registers instead of 48; the wave's own dS^T writes: no barrier needed),
+        // then this wave's share of dQ (its keys only) for block j as [q][d] f32 rows (zeros from a wave without keys)
+        // (Both dQ forms stand in place, not in lambdas like the pieces above: with this one in a lambda the kernel takes
+        // 224 B of scratch instead of 24.)
+        float* sh = share + wid * (QB * ILD);
 #pragma unroll
-        for (int c = 0; c < LQ / 32; ++c) {
-          const bf16x8 ktf = tr_frag(ktile, RS, c * 32 + trow, dt0 * 32 + tcolb);
-          const char* dsc = dst_all + c * 2048;
-          const bf16x8 dsb0 = tr_frag_off(dsc, swz64(trow, q0t * 2 + ((li & 3) >> 1)) + 8 * (li & 1));
-          dq[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsb0, dq[0], 0, 0, 0);
-          if (nq == 2) {                                   // (wave-uniform)
-            const bf16x8 dsb1 = tr_frag_off(dsc, swz64(trow, 2 + ((li & 3) >> 1)) + 8 * (li & 1));
-            dq[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsb1, dq[1], 0, 0, 0);
+        for (int qq = 0; qq < 2; ++qq) {
+          f32x4 dq[DT];
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (wave_live) {
+#pragma unroll
+            for (int c = 0; c < NCK; ++c) {
+              const bf16x8 dsb = tr_frag_off(dst + c * 2048, swz64(trow, qq * 2 + ((li & 3) >> 1)) + 8 * (li & 1));
+#pragma unroll
+              for (int dt = 0; dt < DT; ++dt) {
+                // K^T[d tile][32 keys of chunk c]: re-read from the staged K rows (12 resident fragments would cost 48
+                // registers the sweep does not have)
+                const bf16x8 ktf = tr_frag(ktile, RS, wid * KW + c * 32 + trow, dt * 32 + tcolb);
+                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsb, dq[dt], 0, 0, 0);
+              }
+            }
+          }
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt)
+            *reinterpret_cast<f32x4*>(sh + (qq * 16 + li) * ILD + dt * 16 + 4 * g) = dq[dt];
+        }
+        if (j + 1 < nblk) store_block(j + 1);              // the other buffer
+        __syncthreads();
+        // ... sum the four shares in wave order, scale, round, store: thread t -> query t / 8, 12 head dims
+        {
+          const int r = tid >> 3, c0 = (tid & 7) * 12;
+          f32x4 a[3];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) a[i] = *reinterpret_cast<const f32x4*>(share + r * ILD + c0 + 4 * i);
+#pragma unroll
+          for (int ww = 1; ww < 4; ++ww)
+#pragma unroll
+            for (int i = 0; i < 3; ++i) a[i] += *reinterpret_cast<const f32x4*>(share + ww * (QB * ILD) + r * ILD + c0 + 4 * i);
+          const int q = j * QB + r;
+          if (q < L) {
+            unsigned short* dqrow = dqb + (unsigned int)q * 3u * HD + c0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+              u32x2 w2;
+              w2[0] = pack_bf16x2(a[i][0] * p.scale, a[i][1] * p.scale);
+              w2[1] = pack_bf16x2(a[i][2] * p.scale, a[i][3] * p.scale);
+              *reinterpret_cast<u32x2*>(dqrow + 4 * i) = w2;
+            }
           }
         }
+      } else {
+        // a wave without keys writes a zero dS^T tile: the dQ tiles read all eight
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-          if (t < nq) {
-            const f32x4 v = dq[t] * p.scale;
-            u32x2 wv;
-            wv[0] = pack_bf16x2(v[0], v[1]);
-            wv[1] = pack_bf16x2(v[2], v[3]);
-            *reinterpret_cast<u32x2*>(dqimg + ((q0t + t) * 16 + li) * RS + (dt0 * 16 + 4 * g) * 2) = wv;
+        for (int qq = 0; qq < 2; ++qq)
+#pragma unroll
+          for (int kt = 0; kt < KTW; ++kt) { pk[qq][kt] = u32x2{0u, 0u}; dsk[qq][kt] = pk[qq][kt]; }
+        if (wave_live) p_ds();
+        write_dst();
+        __builtin_amdgcn_sched_barrier(0);
+        if (wave_live) dvdk();
+        __builtin_amdgcn_sched_barrier(0);
+        store_block(j + 1);                                // the other buffer
+        __syncthreads();
+        // ---- dQ AS COMPLETE TILES (eight waves; every wave's dS^T tile is written).  dQ^T = K^T dS^T as COMPLETE (d tile,
+        // 16-query tile) outputs over all keys: waves 0-3 take d tiles 0-3 (both query tiles), waves 4-7 d tiles 4 / 5
+        // (one query tile each) - three tiles per SIMD - reading the K^T fragments of the staged K rows and the dS^T tile
+        // of the wave that owns each 32-key chunk.  No shares, no sums over waves: the accumulator IS the gradient; it
+        // goes (scaled, bf16) into a [32 q][RS] image and leaves as whole rows.
+        // (In a lambda this one gets another schedule, 236 registers, and measured 1 % slower.)
+        {
+          {
+            const int dt0 = wid < 4 ? wid : 4 + ((wid - 4) >> 1);
+            const int nq = wid < 4 ? 2 : 1, q0t = wid < 4 ? 0 : (wid & 1);
+            f32x4 dq[2];
+            dq[0] = f32x4{0.f, 0.f, 0.f, 0.f}; dq[1] = dq[0];
+            // all eight 32-key chunks, unrolled (a chunk past the end multiplies clamped K rows by a zero dS^T tile): as a
+            // run-time loop over the live chunks every fragment read waited out its own LDS latency - 3160 cycles per step
+#pragma unroll
+            for (int c = 0; c < LQ / 32; ++c) {
+              const bf16x8 ktf = tr_frag(ktile, RS, c * 32 + trow, dt0 * 32 + tcolb);
+              const char* dsc = dst_all + c * 2048;
+              const bf16x8 dsb0 = tr_frag_off(dsc, swz64(trow, q0t * 2 + ((li & 3) >> 1)) + 8 * (li & 1));
+              dq[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsb0, dq[0], 0, 0, 0);
+              if (nq == 2) {                                   // (wave-uniform)
+                const bf16x8 dsb1 = tr_frag_off(dsc, swz64(trow, 2 + ((li & 3) >> 1)) + 8 * (li & 1));
+                dq[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsb1, dq[1], 0, 0, 0);
+              }
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+              if (t < nq) {
+                const f32x4 v = dq[t] * p.scale;
+                u32x2 wv;
+                wv[0] = pack_bf16x2(v[0], v[1]);
+                wv[1] = pack_bf16x2(v[2], v[3]);
+                *reinterpret_cast<u32x2*>(dqimg + ((q0t + t) * 16 + li) * RS + (dt0 * 16 + 4 * g) * 2) = wv;
+              }
           }
-      }
-      __syncthreads();
-      // ---- dQ rows: thread t < 384 -> query t / 12, one 16-byte chunk
-      if (tid < QB * NCH) {
-        const int r = tid / NCH, ch = tid - r * NCH;
-        const int q = j * QB + r;
-        if (q < L)
-          *reinterpret_cast<u32x4*>(dqb + (unsigned int)q * 3u * HD + 8 * ch) = *reinterpret_cast<const u32x4*>(dqimg + r * RS + ch * 16);
+          __syncthreads();
+          // dQ rows: thread t < 384 -> query t / 12, one 16-byte chunk
+          if (tid < QB * NCH) {
+            const int r = tid / NCH, ch = tid - r * NCH;
+            const int q = j * QB + r;
+            if (q < L)
+              *reinterpret_cast<u32x4*>(dqb + (unsigned int)q * 3u * HD + 8 * ch) = *reinterpret_cast<const u32x4*>(dqimg + r * RS + ch * 16);
+          }
+        }
       }
       if (j + 1 < nblk) finish_delta(j + 1);
       __syncthreads();
@@ -2260,19 +2076,22 @@ void launch_fused(const AP& p, hipStream_t st) {
   else launch_fused_nw<ROPE, D, 4>(p, st);
 }
 
-inline void launch_fused96(const AP& p, hipStream_t st) {
+template <int NW>
+void launch_fused96_nw(const AP& p, hipStream_t st) {
   constexpr size_t lds = lds_fused96();
   static_assert(lds <= 160 * 1024, "fused96 LDS budget");
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused96_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int nheads = p.B * p.H, cus = attn_cu_count();
-  if (clipk_opt_get(OPT_ATTN_FUSED_WAVES) != 4) {             // default: eight waves of 32 keys (948 vs 1132 us per layer at B = 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused96w8_kernel),
+  static std::atomic<uint64_t> attr_set{0};
+  clipk_once_per_device(attr_set, [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused96_kernel<NW>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attn_bwd_fused96w8_kernel, dim3(nheads < cus ? nheads : cus), dim3(512), lds, st, p);
-    return;
-  }
-  hipLaunchKernelGGL(attn_bwd_fused96_kernel, dim3(nheads < cus ? nheads : cus), dim3(256), lds, st, p);
+  });
+  const int nheads = p.B * p.H, cus = attn_cu_count();   // persistent: the resident workgroups walk the heads
+  hipLaunchKernelGGL((attn_bwd_fused96_kernel<NW>), dim3(nheads < cus ? nheads : cus), dim3(64 * NW), lds, st, p);
+}
+inline void launch_fused96(const AP& p, hipStream_t st) {
+  // default: eight waves of 32 keys (948 vs 1132 us per layer at B = 1024)
+  if (clipk_opt_get(OPT_ATTN_FUSED_WAVES) != 4) launch_fused96_nw<8>(p, st);
+  else launch_fused96_nw<4>(p, st);
 }
 
 template <int DP, int DR, int DX>

@@ -553,6 +553,43 @@ def test_attention_bwd_whole_head_hd96_vs_two_kernel(dev, B, L, H, waves, kopt):
         assert (g1 - gref).abs().max().item() / gref.abs().max().item() < 4e-2
 
 
+@pytest.mark.parametrize("waves", [4, 8])
+def test_attention_bwd_whole_head_hd96_persistent_loop(dev, waves, kopt):
+    """More heads than twice the CUs, so that workgroups of the hd-96 whole-head backward walk three heads - a first, a
+    middle and a last one: the next head's rows requested under the write-out, K rows staged over the previous head's
+    dK / dV images, the last head asking for its own rows again.  Lengths cycle along the batch, so consecutive heads of
+    a workgroup differ in length and in live waves.  Against the dQ + dK/dV pair; reproducible; exact zeros on padded rows."""
+    ops = _ops()
+    kopt("attn_fused_waves", waves)
+    D, H, L = 96, 8, 130                     # 130: the shortest length class with a second, partial 128-row half
+    cycle = (130, 129, 97, 64, 33, 1)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    B = (2 * cus + 8 + H - 1) // H
+    while cycle[(B - 1) % len(cycle)] == L:  # the last batch entry has padded rows
+        B += 1
+    qkv = _rand((B * L, 3 * H * D), dev, 270, 1.0, dtype=torch.bfloat16)
+    dout = _rand((B * L, H * D), dev, 271, 1.0, dtype=torch.bfloat16)
+    scale = D ** -0.5
+    lens = torch.tensor([cycle[i % len(cycle)] for i in range(B)])
+    mask = (torch.arange(L)[None] < lens[:, None]).to(torch.uint8).contiguous().to(dev)
+    dout = (dout.view(B, L, -1) * mask[..., None].to(dout.dtype)).view(B * L, -1).contiguous()
+    out, lse = ops.attn_fwd(qkv, B, L, H, D, key_mask=mask, rope=None, q_scale=scale)
+    kw = dict(key_mask=mask, rope=None, q_scale=scale)
+    kopt("attn_fused_bwd", 0)
+    g2 = ops.attn_bwd(qkv, out, dout, lse, B, L, H, D, **kw).float()
+    kopt("attn_fused_bwd", 1)
+    g1 = ops.attn_bwd(qkv, out, dout, lse, B, L, H, D, **kw)
+    assert torch.equal(g1, ops.attn_bwd(qkv, out, dout, lse, B, L, H, D, **kw))      # reproducible
+    g1 = g1.float()
+    assert torch.isfinite(g1).all()
+    pad = mask[B - 1] == 0
+    assert pad.any() and (g1.view(B, L, -1)[B - 1][pad] == 0).all()
+    m3 = mask.view(B * L, 1).float()
+    g1, g2 = g1 * m3, g2 * m3
+    denom = g2.abs().max().item()
+    assert (g1 - g2).abs().max().item() / denom < 8e-3, (g1 - g2).abs().max().item() / denom
+
+
 @pytest.mark.parametrize("B,L,H,D", [(8, 256, 20, 24), (3, 190, 4, 32), (2, 129, 3, 16), (5, 255, 2, 24)])
 def test_attention_fwd_whole_head_equals_general(dev, B, L, H, D, kopt):
     """Short heads whose rows need no rotation take the whole-head forward (K / V staged once per head); it keeps the

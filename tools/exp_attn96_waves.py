@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A/B of the hd-96 whole-head attention backward with four waves of 64 keys (attn_bwd_fused96_kernel) against eight waves of
-32 keys (attn_bwd_fused96w8_kernel, option attn_fused_waves = 8) and the dQ + dK/dV pair: the RNA encoder's shape (8 heads
+"""A/B of the hd-96 whole-head attention backward with four waves of 64 keys (attn_bwd_fused96_kernel<4>) against eight waves of
+32 keys (attn_bwd_fused96_kernel<8>, option attn_fused_waves = 8) and the dQ + dK/dV pair: the RNA encoder's shape (8 heads
 of 96, L = 256) at the metric batch, interleaved rounds on a warm GPU, HIP events.
 
     python3 tools/exp_attn96_waves.py [B] [rounds]"""
