@@ -1,10 +1,13 @@
-// cloud_tile.h — what the point-cloud kernels (sinkhorn.hip, sinkhorn_sample.hip, auction.hip, kernel_sums.hip) share
-// on top of sim_tile.h's exact-f32 64 x 64 block (keys on the MFMA rows, queries on the lanes):
+// cloud_tile.h — what the point-cloud kernels (sinkhorn.hip, sinkhorn_sample.hip, auction.hip, kernel_sums.hip, kmeans.hip,
+// label_dist_sums.hip) and the tiled InfoNCE kernels (simce_tiled.hip, simce_hard.hip) share on top of sim_tile.h's
+// exact-f32 64 x 64 block (keys on the MFMA rows, queries on the lanes):
 //   * KeyWalk: one workgroup's walk over the 64-key tiles of its key split - coordinates, staging rows, the S^T product;
-//   * key_split_plan: the (query block, key split) grid on the host; cloud_shape_ok: the shapes the passes accept;
+//     with CACHE the key list is two segments, batch keys and cache keys (the InfoNCE kernels);
+//   * key_split_plan: the (query block, key split) grid on the host (simce.hip, linear_ce_tiled.hip take it from here
+//     too); cloud_shape_ok: the shapes the passes accept;
 //   * NO_KEY, better_key, take_better: the (value, key) order of the sampler's and the top-two pass's merges.
-// Each kernel keeps what it does with the products, its merge rule and its own partial format.  What only the two
-// kernels with a weighted key sum share is in cloud_keysum.h; sinkhorn_apply_kernel has the walk in its own body.
+// Each kernel keeps what it does with the products, its merge rule and its own partial format.  The weighted key sum
+// behind the walk is in key_sum_tile.h; sinkhorn_apply_kernel has the walk in its own body.
 #pragma once
 #include "common.h"
 #include "sim_tile.h"
@@ -27,12 +30,15 @@ __device__ __forceinline__ void take_better(float& z, int& k, float zo, int ko) 
 // ------------------------------------------------------------------------------------------------ key-split plan
 struct KeySplitPlan { int nqb, ksplit, tiles_per_split, ntiles; };
 
-// one workgroup per (query_block-query block, key split); splits so that the grid holds >= 2 workgroups per CU
-inline KeySplitPlan key_split_plan(int M, int N, int query_block) {
+// one workgroup per (query_block-query block, key split); splits so that the grid holds >= 2 workgroups per CU.
+// problems > 1: that many same-shape problems in one grid (blockIdx.z = problem); the splits are chosen for the WHOLE
+// grid nqb x ksplit x problems, not as if each problem had the chip to itself
+inline KeySplitPlan key_split_plan(int M, int N, int query_block, int problems = 1) {
   KeySplitPlan k;
   k.nqb = (M + query_block - 1) / query_block;
   k.ntiles = (N + TK - 1) / TK;
-  int ks = (512 + k.nqb - 1) / k.nqb;
+  const int wgs = k.nqb * (problems > 0 ? problems : 1);
+  int ks = (512 + wgs - 1) / wgs;
   if (ks > k.ntiles) ks = k.ntiles;
   if (ks < 1) ks = 1;
   k.tiles_per_split = (k.ntiles + ks - 1) / ks;
@@ -44,9 +50,11 @@ inline KeySplitPlan key_split_plan(int M, int N, int query_block) {
 // Workgroup (blockIdx.x, blockIdx.y) = (query block, key split), 256 threads.  Wave (wm, wn) holds keys [32 wm, +32) x
 // queries [32 wn, +32) of each tile; lane li of half h holds query position qg and the 16 keys key(j0, r).  BKT is the
 // K-step of s_tile: 32 (16 MFMAs per wave between barriers) or 16 (half the LDS, for kernels that need the rest).
-template <int BKT>
+// CACHE: keys [Ny, Nk) are the rows of a second segment Yc (the InfoNCE cache); without it Nk = Ny and Yc is unused.
+template <int BKT, bool CACHE = false>
 struct KeyWalk {
   const float* Y; int Ny, P;
+  const float* Yc; int Nk;                        // CACHE: the second key segment, the length of the whole key list
   float* smem;                                    // 2 buffers x (keys | queries) x 64 x (BKT + 4) floats
   int tid, wid, wm, wn, li, h;
   int q0, ks, qg;
@@ -56,8 +64,8 @@ struct KeyWalk {
   // Query position q < nrows stands for row rows[q] of X [Mx][P], or for row q without a list (then nrows <= Mx).
   // Positions beyond nrows are clamped: computed and dropped by the caller.
   __device__ __forceinline__ KeyWalk(const float* X, int Mx, const int* rows, int nrows, const float* Y_, int Ny_, int P_,
-                                     int tiles_per_split, int ntiles, float* smem_)
-      : Y(Y_), Ny(Ny_), P(P_), smem(smem_) {
+                                     int tiles_per_split, int ntiles, float* smem_, const float* Yc_ = nullptr, int Nc = 0)
+      : Y(Y_), Ny(Ny_), P(P_), Yc(Yc_), Nk(Ny_ + Nc), smem(smem_) {
     tid = threadIdx.x; wid = tid >> 6;
     const int lane = tid & 63;
     wm = wid >> 1; wn = wid & 1;                                          // key half, query half
@@ -78,8 +86,13 @@ struct KeyWalk {
   }
 
   __device__ __forceinline__ const float* key_row(int j) const {
-    j = j < Ny ? j : Ny - 1;                                              // clamped: masked in the caller's epilogue
-    return Y + (long)j * P;
+    if constexpr (CACHE) {
+      j = j < Nk ? j : Nk - 1;                                            // clamped: masked in the caller's epilogue
+      return (j < Ny) ? Y + (long)j * P : Yc + (long)(j - Ny) * P;
+    } else {
+      j = j < Ny ? j : Ny - 1;                                            // clamped: masked in the caller's epilogue
+      return Y + (long)j * P;
+    }
   }
 
   // the key of accumulator row r of the tile at j0

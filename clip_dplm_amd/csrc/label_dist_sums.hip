@@ -10,7 +10,7 @@
 // gl[key][query]; (3) out^T[g, q] += H^T[g, key] D[key, q] as the second MFMA product, H the one-hot of the tile's
 // labels, staged in LDS from the labels (16 label loads per 16-key block) - no N x G one-hot matrix exists in memory.  Key-split slabs
 // are summed in split order by split_sum_finalize.
-// Two forms of step (3).  G > 64: the contraction of cloud_keysum.h's key_sum_tile, wave w owning label rows
+// Two forms of step (3).  G > 64: the contraction of key_sum_tile.h's key_sum_tile, wave w owning label rows
 // [w G/4, (w+1) G/4) - for G <= 128 that is 32 rows per wave, so few labels leave waves idle at the barriers of the four
 // key blocks.  G <= 64: one or two 32-row blocks hold every label, so the four waves split the tile's 64 KEYS instead
 // (16 each, one staging of the whole one-hot, two barriers in place of eight) and their partial accumulators are merged
@@ -66,7 +66,7 @@ __device__ __forceinline__ void label_stage(const int* labels, int Ny, int G, in
 }
 
 // dx += yh^T[g, 16 keys] gl[16 keys of block kb, q]: wave wid's label rows, all 64 queries.  The contraction half of
-// cloud_keysum.h's key_sum_tile, kept here: split out of that function it changes what its three callers compile to.
+// key_sum_tile.h's key_sum_tile, kept here: split out of that function it changes what its three callers compile to.
 __device__ __forceinline__ void label_contract(f32x16 (&dx)[4][2], int Gp, int kb, const float* gl, const float* yh, int wid,
                                                int li, int h) {
   const int npt = (Gp + 127) / 128;                                       // 32-row label tiles per wave

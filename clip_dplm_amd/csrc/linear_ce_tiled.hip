@@ -7,7 +7,7 @@
 //                             64 x 64 tile of sim_tile.h (classes on the MFMA rows, X rows on the lanes; the two sources
 //                             are two s_tile calls into one accumulator).  Each lane keeps (m, l, best value, best class,
 //                             target logit) of its row; lane halves and the two class-waves merge at the end.  Class-range
-//                             splits (the plan of clipk_simce_tiled_plan) fill the chip when M is small.
+//                             splits (cloud_tile.h's key_split_plan) fill the chip when M is small.
 //   lcet_finalize_kernel      the splits' partials [split][M][5] merged in split order -> lse, tgt, pred
 //   lcet_rows_kernel<true>    backward, step 1: the same Z (same code, same bits), G = g/M (softmax - onehot) -> workspace,
 //                             pitch C rounded up to 4 with zeros in the padding

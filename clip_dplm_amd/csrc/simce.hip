@@ -18,6 +18,7 @@
 //   * key-range splits write f32 partials (online-softmax pairs / dX slabs) that a tiny finalize
 //     kernel merges in a fixed order: deterministic, no float atomics.
 #include "common.h"
+#include "cloud_tile.h"                    // key_split_plan: the grid of the tiled passes (simce_tiled.hip, simce_hard.hip)
 #include <math.h>
 
 namespace {
@@ -397,11 +398,9 @@ int launch(const SP& sp, const Plan& pl, hipStream_t st) {
 }  // namespace
 
 // simce_tiled.hip: second-generation LSE pass (64 x 64 tiles, gemm_f32-style K-loop)
-extern "C" void clipk_simce_tiled_plan(int Mx, int Nkeys, int* nqb, int* ksplit, int* tps, int* ntiles);
 extern "C" int clipk_simce_lse_tiled_launch(const float* X, int Mx, const float* Y, int Ny, const float* Yc, int Nc, int P,
                                             const float* scale, int label_offset, float* part_ml, float* pos,
                                             void* stream);
-extern "C" void clipk_simce_grad_tiled_plan(int Mx, int Nkeys, int* nqb, int* ksplit, int* tps, int* ntiles);
 static bool use_tiled_grad(int Mx, int Nkeys, int P, int Pw) {
   const int mode = clipk_opt_get(OPT_SIMCE_KERNEL);
   if (P > 512) return false;
@@ -421,12 +420,10 @@ static bool use_tiled_lse(int Mx, int Nkeys) {
 extern "C" size_t clipk_simce_workspace(int Mx, int Nkeys, int P) {
   Plan pl;
   if (!make_plan(Mx, Nkeys, P, &pl)) return 0;
-  int nqb, ks2, tps, nt;
-  clipk_simce_tiled_plan(Mx, Nkeys, &nqb, &ks2, &tps, &nt);
+  const int ks2 = key_split_plan(Mx, Nkeys, TQ).ksplit;
   const size_t a = (size_t)pl.ksplit * Mx * ((size_t)P + 2) * sizeof(float);
   const size_t b = (size_t)ks2 * Mx * 2 * sizeof(float);          // (m, l) partials of the tiled LSE pass
-  int ks3;
-  clipk_simce_grad_tiled_plan(Mx, Nkeys, &nqb, &ks3, &tps, &nt);
+  const int ks3 = key_split_plan(Mx, Nkeys, TQ).ksplit;
   const size_t c = (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float);   // dX slabs + dscale partials of the tiled grad pass
   const size_t ab = a > b ? a : b;
   return ab > c ? ab : c;
@@ -440,8 +437,7 @@ extern "C" int clipk_simce_lse(const float* X, int Mx, const float* Y, int Ny, c
   if (!make_plan(Mx, Ny + Nc, P, &pl)) return CLIPK_ERR_UNSUPPORTED;
   if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc))) return CLIPK_ERR_BAD_ARG;
   if (use_tiled_lse(Mx, Ny + Nc)) {
-    int nqb, ks2, tps, nt;
-    clipk_simce_tiled_plan(Mx, Ny + Nc, &nqb, &ks2, &tps, &nt);
+    const int ks2 = key_split_plan(Mx, Ny + Nc, TQ).ksplit;
     if (workspace_bytes < (size_t)ks2 * Mx * 2 * sizeof(float)) return CLIPK_ERR_BAD_ARG;
     int rc = clipk_simce_lse_tiled_launch(X, Mx, Y, Ny, Yc, Nc, P, scale, label_offset, (float*)workspace, pos, stream);
     if (rc) return rc;
@@ -478,9 +474,8 @@ static bool cls_shape_ok(int Mx, int Nkeys, int P) { return Mx > 0 && Nkeys > 0 
 
 extern "C" size_t clipk_simce_cls_workspace(int Mx, int Nkeys, int P) {
   if (!cls_shape_ok(Mx, Nkeys, P)) return 0;
-  int nqb, ks2, ks3, tps, nt;
-  clipk_simce_tiled_plan(Mx, Nkeys, &nqb, &ks2, &tps, &nt);
-  clipk_simce_grad_tiled_plan(Mx, Nkeys, &nqb, &ks3, &tps, &nt);
+  const int ks2 = key_split_plan(Mx, Nkeys, TQ).ksplit;
+  const int ks3 = key_split_plan(Mx, Nkeys, TQ).ksplit;
   const size_t a = (size_t)ks2 * Mx * 5 * sizeof(float);                   // (m, l) + target-sum partials
   const size_t c = (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float);    // dX slabs + dscale partials
   return a > c ? a : c;
@@ -501,8 +496,7 @@ extern "C" int clipk_simce_lse_cls(const float* X, int Mx, const float* Y, int N
   if (!cls_shape_ok(Mx, Ny + Nc, P)) return CLIPK_ERR_UNSUPPORTED;
   if (label_offset < 0 || (long)label_offset + Mx > Ny) return CLIPK_ERR_BAD_ARG;   // every row has its diagonal key
   if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc))) return CLIPK_ERR_BAD_ARG;
-  int nqb, ks2, tps, nt;
-  clipk_simce_tiled_plan(Mx, Ny + Nc, &nqb, &ks2, &tps, &nt);
+  const int ks2 = key_split_plan(Mx, Ny + Nc, TQ).ksplit;
   if (workspace_bytes < (size_t)ks2 * Mx * 5 * sizeof(float)) return CLIPK_ERR_BAD_ARG;
   float* part_ml = (float*)workspace;
   float* part_t = part_ml + (size_t)ks2 * Mx * 2;
@@ -528,8 +522,7 @@ extern "C" int clipk_simce_grad_cls(const float* X, int Mx, const float* Y, int 
   if (label_offset < 0 || (long)label_offset + Mx > Ny) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc)) || !aligned16(dX) || !aligned16(workspace))
     return CLIPK_ERR_BAD_ARG;
-  int nqb, ks3, tps, nt;
-  clipk_simce_grad_tiled_plan(Mx, Ny + Nc, &nqb, &ks3, &tps, &nt);
+  const int ks3 = key_split_plan(Mx, Ny + Nc, TQ).ksplit;
   if (workspace_bytes < (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float)) return CLIPK_ERR_BAD_ARG;
   float* slab = (float*)workspace;
   float* dscp = slab + (size_t)ks3 * Mx * P;
@@ -558,9 +551,8 @@ extern "C" int clipk_simce_grad_hard_launch(const float* X, int Mx, const float*
 
 extern "C" size_t clipk_simce_hard_workspace(int Mx, int Nkeys, int P) {
   if (!cls_shape_ok(Mx, Nkeys, P)) return 0;
-  int nqb, ks2, ks3, tps, nt;
-  clipk_simce_tiled_plan(Mx, Nkeys, &nqb, &ks2, &tps, &nt);
-  clipk_simce_grad_tiled_plan(Mx, Nkeys, &nqb, &ks3, &tps, &nt);
+  const int ks2 = key_split_plan(Mx, Nkeys, TQ).ksplit;
+  const int ks3 = key_split_plan(Mx, Nkeys, TQ).ksplit;
   const size_t a = (size_t)ks2 * Mx * 4 * sizeof(float);                   // (m, a, c, n) partials
   const size_t c = (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float);    // dX slabs + dscale partials
   return a > c ? a : c;
@@ -577,8 +569,7 @@ extern "C" int clipk_simce_lse_hard(const float* X, int Mx, const float* Y, int 
   if (!cls_shape_ok(Mx, Ny + Nc, P)) return CLIPK_ERR_UNSUPPORTED;
   if (label_offset < 0 || (long)label_offset + Mx > Ny) return CLIPK_ERR_BAD_ARG;   // every row has its diagonal key
   if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc))) return CLIPK_ERR_BAD_ARG;
-  int nqb, ks2, tps, nt;
-  clipk_simce_tiled_plan(Mx, Ny + Nc, &nqb, &ks2, &tps, &nt);
+  const int ks2 = key_split_plan(Mx, Ny + Nc, TQ).ksplit;
   if (workspace_bytes < (size_t)ks2 * Mx * 4 * sizeof(float)) return CLIPK_ERR_BAD_ARG;
   return clipk_simce_lse_hard_launch(X, Mx, Y, Ny, Yc, Nc, P, scale, beta, label_offset, cls_x, cls_y, (float*)workspace,
                                      lse_h, pos, coef, stream);
@@ -595,8 +586,7 @@ extern "C" int clipk_simce_grad_hard(const float* X, int Mx, const float* Y, int
   if (label_offset < 0 || (long)label_offset + Mx > Ny) return CLIPK_ERR_BAD_ARG;
   if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc)) || !aligned16(dX) || !aligned16(workspace))
     return CLIPK_ERR_BAD_ARG;
-  int nqb, ks3, tps, nt;
-  clipk_simce_grad_tiled_plan(Mx, Ny + Nc, &nqb, &ks3, &tps, &nt);
+  const int ks3 = key_split_plan(Mx, Ny + Nc, TQ).ksplit;
   if (workspace_bytes < (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float)) return CLIPK_ERR_BAD_ARG;
   float* slab = (float*)workspace;
   float* dscp = slab + (size_t)ks3 * Mx * P;
@@ -676,8 +666,7 @@ extern "C" int clipk_simce_grad_scaled(const float* X, int Mx, const float* Y, i
   if (!aligned16(X) || !aligned16(Y) || (Yc && !aligned16(Yc)) || !aligned16(dX) || !aligned16(workspace))
     return CLIPK_ERR_BAD_ARG;
   if (use_tiled_grad(Mx, Ny + Nc, P, pl.Pw)) {
-    int nqb, ks3, tps, nt;
-    clipk_simce_grad_tiled_plan(Mx, Ny + Nc, &nqb, &ks3, &tps, &nt);
+    const int ks3 = key_split_plan(Mx, Ny + Nc, TQ).ksplit;
     if (workspace_bytes < (size_t)ks3 * Mx * ((size_t)P + 1) * sizeof(float)) return CLIPK_ERR_BAD_ARG;
     float* slab = (float*)workspace;
     float* dscp = slab + (size_t)ks3 * Mx * P;
@@ -784,8 +773,7 @@ extern "C" int clipk_simce_grad_pairs(const float* E, int nmod, int B, int P, co
 
 // ---- the batched form of the class-aware and the hard-negative pair (clipk_simce_{lse,grad}_pairs_{cls,hard}): the
 // tiled kernels with a problem index (simce_tiled.hip, simce_hard.hip), one launch per pass plus one finalize, the key
-// splits of clipk_simce_pairs_tiled_plan (chosen for the whole grid)
-extern "C" void clipk_simce_pairs_tiled_plan(int npairs, int B, int* nqb, int* ksplit, int* tps, int* ntiles);
+// splits of key_split_plan(B, B, 64, npairs) (chosen for the whole grid)
 extern "C" int clipk_simce_lse_tiled_pairs_cls_launch(const PairZ* zt, int B, int P, const float* scale, int same_positive,
                                                       float* part_ml, float* part_t, float* pos, void* stream);
 extern "C" int clipk_simce_grad_tiled_pairs_cls_launch(const PairZ* zt, int B, int P, const float* scale, const float* lse,
@@ -801,8 +789,7 @@ extern "C" int clipk_simce_grad_pairs_hard_launch(const PairZ* zt, int B, int P,
 // lse_floats: partial floats per (split, row) of the LSE pass (5 class-aware, 4 hard-negative)
 static size_t pairs_tiled_workspace(int npairs, int B, int P, int lse_floats) {
   if (npairs <= 0 || npairs > MAXZ || !cls_shape_ok(B, B, P)) return 0;
-  int nqb, ks, tps, nt;
-  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  const int ks = key_split_plan(B, B, TQ, npairs).ksplit;
   const size_t a = (size_t)npairs * ks * B * lse_floats * sizeof(float);
   const size_t c = (size_t)npairs * ks * B * ((size_t)P + 1) * sizeof(float);      // dX slabs + dscale partials
   return a > c ? a : c;
@@ -850,8 +837,7 @@ extern "C" int clipk_simce_lse_pairs_cls(const float* E, int nmod, int B, int P,
   PairZ zt;
   int rc = pairs_table(E, nmod, B, P, pairs, nullptr, npairs, ids, &zt);
   if (rc) return rc;
-  int nqb, ks, tps, nt;
-  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  const int ks = key_split_plan(B, B, TQ, npairs).ksplit;
   if (workspace_bytes < (size_t)npairs * ks * B * 5 * sizeof(float)) return CLIPK_ERR_BAD_ARG;
   float* part_ml = (float*)workspace;
   float* part_t = part_ml + (size_t)npairs * ks * B * 2;
@@ -874,8 +860,7 @@ extern "C" int clipk_simce_grad_pairs_cls(const float* E, int nmod, int B, int P
   int rc = pairs_table(E, nmod, B, P, pairs, reverse, npairs, ids, &zt);
   if (rc) return rc;
   if (!aligned16(dX) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
-  int nqb, ks, tps, nt;
-  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  const int ks = key_split_plan(B, B, TQ, npairs).ksplit;
   if (workspace_bytes < (size_t)npairs * ks * B * ((size_t)P + 1) * sizeof(float)) return CLIPK_ERR_BAD_ARG;
   float* slab = (float*)workspace;
   float* dscp = slab + (size_t)npairs * ks * B * P;
@@ -892,8 +877,7 @@ extern "C" int clipk_simce_lse_pairs_hard(const float* E, int nmod, int B, int P
   PairZ zt;
   int rc = pairs_table(E, nmod, B, P, pairs, nullptr, npairs, ids, &zt);
   if (rc) return rc;
-  int nqb, ks, tps, nt;
-  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  const int ks = key_split_plan(B, B, TQ, npairs).ksplit;
   if (workspace_bytes < (size_t)npairs * ks * B * 4 * sizeof(float)) return CLIPK_ERR_BAD_ARG;
   return clipk_simce_lse_pairs_hard_launch(&zt, B, P, scale, beta, (float*)workspace, lse_h, pos, coef, stream);
 }
@@ -908,8 +892,7 @@ extern "C" int clipk_simce_grad_pairs_hard(const float* E, int nmod, int B, int 
   int rc = pairs_table(E, nmod, B, P, pairs, reverse, npairs, ids, &zt);
   if (rc) return rc;
   if (!aligned16(dX) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
-  int nqb, ks, tps, nt;
-  clipk_simce_pairs_tiled_plan(npairs, B, &nqb, &ks, &tps, &nt);
+  const int ks = key_split_plan(B, B, TQ, npairs).ksplit;
   if (workspace_bytes < (size_t)npairs * ks * B * ((size_t)P + 1) * sizeof(float)) return CLIPK_ERR_BAD_ARG;
   float* slab = (float*)workspace;
   float* dscp = slab + (size_t)npairs * ks * B * P;

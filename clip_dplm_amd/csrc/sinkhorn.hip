@@ -11,7 +11,7 @@
 //     order: the error scalar is as deterministic as the potentials);
 //   * sinkhorn_lse_x3_kernel: the same pass with the product as a bf16x3 split on v_mfma_f32_32x32x16_bf16 (plane_tile.h's
 //     PlaneWalk: 128-query blocks, its own plan), feeding the same finalize and error kernels (clipk_sim_lse_bias_x3);
-//   * sinkhorn_apply_kernel: S tile -> P tile into LDS -> cloud_keysum.h's weighted key sum (bary^T = Y^T P^T), mass and
+//   * sinkhorn_apply_kernel: S tile -> P tile into LDS -> key_sum_tile.h's weighted key sum (bary^T = Y^T P^T), mass and
 //     cost from the same P values; key-split slabs are summed in split order by split_sum_finalize.
 // No float atomics, no cooperative launch: results depend on the shapes alone.
 #include "common.h"
@@ -225,7 +225,7 @@ constexpr int APMAX = KEYSUM_PMAX;                // contraction / output width 
 
 // Same 64 x 64 tiles as simce_grad_tiled_kernel: (1) S^T tile by the K-loop over P; (2) the plan's entries in the
 // accumulator layout (keys on rows, queries on lanes), mass and cost summed per lane, the tile written once to a 16 KiB
-// LDS tile; (3) bary^T[p, q] += Y^T[p, key] P^T[key, q] by cloud_keysum.h's weighted key sum.  70 KiB of LDS: two
+// LDS tile; (3) bary^T[p, q] += Y^T[p, key] P^T[key, q] by key_sum_tile.h's weighted key sum.  70 KiB of LDS: two
 // workgroups per CU.  Without bary the kernel stops after (2).
 struct SAP {
   const float* X; int Mx;
