@@ -1,5 +1,5 @@
 // gemm_nt_v3.hip — persistent 256 x 256-tile, 8-wave, phase-interleaved kernel for clipk_gemm_nt
-// (K % 32 == 0, K >= 192).  Same contract and epilogue as gemm_nt_v2.hip; selected by gemm_nt.hip (option gemm_kernel).
+// (K % 32 == 0, K >= 160: three K-tiles, the last one a half tile at K = 160).  Same contract and epilogue as gemm_nt_v2.hip; selected by gemm_nt.hip (option gemm_kernel).
 //
 // Why a second structure: the 128 x 128 kernel tops out where the CU's L2 -> LDS path saturates.
 // A 256 x 256 tile halves the operand bytes per FLOP, but only pays with ~1 workgroup per CU if the loads stay in
@@ -294,7 +294,8 @@ int cu_count() {
 
 }  // namespace
 
-// called by clipk_gemm_nt (gemm_nt.hip) after it validated the arguments (K % 32 == 0, K >= 192)
+// called by clipk_gemm_nt (gemm_nt.hip) after it validated the arguments (K % 32 == 0, K >= 160, i.e. nk >= 3: what the
+// main loop needs - K-tile 0, K-tile nk - 2 and the last one each have their own body; tests/test_gpu_gemm.py runs K = 160)
 extern "C" int clipk_gemm_nt_v3_launch(const clipk_gemm_args* a, void* stream) {
   Params p;
   p.A = (const unsigned short*)a->A; p.lda = a->lda;

@@ -1,5 +1,5 @@
 // gemm_nt_v4.hip — persistent 128 x 256-tile, 4-wave kernel for clipk_gemm_nt, TWO workgroups per CU
-// (K % 32 == 0, K >= 128).  Same contract and epilogue as gemm_nt_v2.hip / gemm_nt_v3.hip; option gemm_kernel = 4.
+// (K % 32 == 0, K >= 160: the dispatcher's one admission test for both persistent kernels; this one needs nk >= 2).  Same contract and epilogue as gemm_nt_v2.hip / gemm_nt_v3.hip; option gemm_kernel = 4.
 //
 // Why a third structure.  In gemm_nt_v3 (one 8-wave workgroup per CU, 256 x 256 tile) nothing runs on a CU while its
 // workgroup is in the epilogue: measured (DESIGN.md 3.1 / 3.2, K = 480) a 12 us main loop is followed by ~5 us of
@@ -280,7 +280,8 @@ int cu_count4() {
 
 }  // namespace
 
-// called by clipk_gemm_nt (gemm_nt.hip) after it validated the arguments (K % 32 == 0, K >= 128)
+// called by clipk_gemm_nt (gemm_nt.hip) after it validated the arguments (K % 32 == 0, K >= 160 as for gemm_nt_v3.hip; the
+// main loop itself needs nk >= 2)
 extern "C" int clipk_gemm_nt_v4_launch(const clipk_gemm_args* a, void* stream) {
   Params p;
   p.A = (const unsigned short*)a->A; p.lda = a->lda;

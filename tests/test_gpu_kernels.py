@@ -2,6 +2,11 @@
 
 Each check compares the HIP kernel with a plain PyTorch f32 computation of the same op on the same
 (bf16-rounded where the kernel takes bf16) inputs.  Tolerances are stated per test.
+
+These are the first-generation tests: workload-sized shapes, loose bf16 tolerances.  The branch-by-branch suites against plain
+f64 references with derived bounds are tests/test_gpu_gemm.py (the Linear kernels gemm_nt*.hip with gemm_epilogue.h and the
+weight-gradient kernels gemm_wgrad*.hip; references in tests/gemm_ref.py, pinned by tests/test_gemm_ref_host.py),
+tests/test_gpu_layernorm.py, tests/test_gpu_elementwise.py and tests/test_gpu_attention.py.
 """
 import math
 import os
