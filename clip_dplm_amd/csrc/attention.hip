@@ -1988,17 +1988,6 @@ __global__ __launch_bounds__(256, ROT ? 3 : 4) void attn_fwd_whole32_kernel(cons
   }
 }
 
-int attn_cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 template <int DP> constexpr size_t lds_fwd() { return (size_t)2 * Geo<DP>::KVB * Geo<DP>::RS + 256; }
 template <int DP> constexpr size_t lds_dq() {
   const size_t rows = 256 * (size_t)Geo<DP>::RS + 128 * 4 + 256 + 128 * (size_t)Geo<DP>::NCH * 4;   // + delta shares
@@ -2063,7 +2052,7 @@ void launch_fused_nw(const AP& p, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused32_kernel<ROPE, D, NW>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
-  int nwg = (NW == 4 ? 2 : 1) * attn_cu_count();          // persistent: the resident workgroups walk the heads
+  int nwg = (NW == 4 ? 2 : 1) * clipk_cu_count();          // persistent: the resident workgroups walk the heads
   if (nwg > p.H * p.B) nwg = p.H * p.B;
   hipLaunchKernelGGL((attn_bwd_fused32_kernel<ROPE, D, NW>), dim3(nwg), dim3(64 * NW), lds, st, p);
 }
@@ -2085,7 +2074,7 @@ void launch_fused96_nw(const AP& p, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused96_kernel<NW>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
-  const int nheads = p.B * p.H, cus = attn_cu_count();   // persistent: the resident workgroups walk the heads
+  const int nheads = p.B * p.H, cus = clipk_cu_count();   // persistent: the resident workgroups walk the heads
   hipLaunchKernelGGL((attn_bwd_fused96_kernel<NW>), dim3(nheads < cus ? nheads : cus), dim3(64 * NW), lds, st, p);
 }
 inline void launch_fused96(const AP& p, hipStream_t st) {

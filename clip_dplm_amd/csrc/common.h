@@ -12,11 +12,11 @@
 // Every value of every option computes the same results; they choose between kernels / schedules that tests and
 // tools/ want to compare.
 enum clipk_opt {
-  OPT_GEMM_KERNEL = 0,     // -1 auto, 1 generic kernel (gemm_nt.hip), 2 128x128 (v2), 3 persistent 256x256 (v3)
+  OPT_GEMM_KERNEL = 0,     // -1 auto, 1 generic kernel (gemm_nt.hip), 2 128x128 (v2), 3 persistent 256x256 (v3), 4 persistent 128x256 (v4)
   OPT_GEMM_EPI_GENERIC,    // 1: run-time epilogue instead of the specialised modes
   OPT_GEMM_BM,             // v2: 256 = 256-row tile variant
   OPT_GEMM_STAGES,         // v2: 2 = two-stage LDS pipeline
-  OPT_GEMM_NWG,            // v3: persistent grid size (multiple of 8), 0 = one workgroup per CU
+  OPT_GEMM_NWG,            // v3 / v4: persistent grid size (multiple of 8), 0 = one (v3) / two (v4) workgroups per CU
   OPT_GEMM_STAGGER,        // start-up stagger of workgroups (0 = off)
   OPT_EPI_NT,              // 1: non-temporal epilogue stores
   OPT_WGRAD_KERNEL,        // -1 auto, 2 128x128 kernel, 3 256x256 kernel (8-phase schedule), 4 256x256 software-pipelined
@@ -294,6 +294,18 @@ static inline void clipk_once_per_device(std::atomic<uint64_t>& mask, F&& f) {
     f();
     mask.fetch_or(bit, std::memory_order_release);
   }
+}
+// compute units of the current device, asked once per process (256, the MI355X's, if the runtime cannot say): the grid
+// of the persistent kernels
+static inline int clipk_cu_count() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
+    if (n <= 0) n = 256;
+  }
+  return n;
 }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 

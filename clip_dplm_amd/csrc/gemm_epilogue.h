@@ -509,3 +509,15 @@ static inline EpiArgs epi_args_from(const clipk_gemm_args* a) {
   e.drop_thr = d.thr; e.drop_seed = a->drop_seed; e.drop_scale = d.scale; e.drop_epoch = clipk_drop_epoch();
   return e;
 }
+
+// the head the argument structs of gemm_nt_v2.hip and gemm_nt_persistent.h start with - A, lda, B, ldb, M, N, K,
+// EpiArgs e - filled from a validated request (P: that kernel's Params; its own trailing fields are left to its launcher)
+template <class P>
+static inline P gemm_params_from(const clipk_gemm_args* a) {
+  P p;
+  p.A = (const unsigned short*)a->A; p.lda = a->lda;
+  p.B = (const unsigned short*)a->B; p.ldb = a->ldb;
+  p.M = a->M; p.N = a->N; p.K = a->K;
+  p.e = epi_args_from(a);
+  return p;
+}

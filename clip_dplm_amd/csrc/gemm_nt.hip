@@ -268,17 +268,17 @@ static int gemm_nt_one(const clipk_gemm_args* a, void* stream) {
   if (a->out_preact && (!aligned16(a->out_preact) || (a->ldp & 7))) return CLIPK_ERR_BAD_ARG;
   if (a->dact_aux && (!aligned16(a->dact_aux) || (a->ldd & 7))) return CLIPK_ERR_BAD_ARG;
   if (a->residual && (!aligned16(a->residual) || (a->ldr & 7))) return CLIPK_ERR_BAD_ARG;
-  // fast paths, both LDS-DMA staged and needing whole 32-deep K steps:
+  // fast paths, all three LDS-DMA staged and needing whole 32-deep K steps:
   //   gemm_nt_v3.hip  persistent 256 x 256 tiles, phase-interleaved: problems with at least ~3/4 of a tile per CU
+  //   gemm_nt_v4.hip  persistent 128 x 256 tiles, two 4-wave workgroups per CU: option gemm_kernel = 4 only
   //   gemm_nt_v2.hip  128 x 128 tiles, 4 workgroups per CU: everything else
-  // option gemm_kernel = 2 / 3 forces the choice (tools/bench_kernels.py, tests), 1 the generic kernel.
+  // option gemm_kernel = 2 / 3 / 4 forces the choice (tools/bench_kernels.py, tests), 1 the generic kernel.
   const int kmode = clipk_opt_get(OPT_GEMM_KERNEL);
   const bool force_v1 = kmode == 1;
   const int v3mode = kmode == 3 ? 1 : kmode == 2 ? 0 : -1;
   const long tiles256 = (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
   const bool v3_ok = (a->K & 31) == 0 && a->K >= 160 && (long)a->M * a->lda * 2 < (1L << 32) &&
                      (long)a->N * a->ldb * 2 < (1L << 32);     // 32-bit buffer offsets
-  //   gemm_nt_v4.hip  persistent 128 x 256 tiles, two 4-wave workgroups per CU (option gemm_kernel = 4 only)
   if (kmode == 4 && v3_ok && a->M >= 2048) return clipk_gemm_nt_v4_launch(a, stream);
   if (!force_v1 && v3_ok && ((v3mode == 1 && a->M >= 2048) || (v3mode < 0 && tiles256 >= 192)))
     return clipk_gemm_nt_v3_launch(a, stream);

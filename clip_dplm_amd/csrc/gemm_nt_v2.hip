@@ -163,11 +163,7 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 ? 4 : 2)) void gemm_nt_v2_kern
 
 // called by clipk_gemm_nt (gemm_nt.hip) after it validated the arguments; returns CLIPK_OK / launch error
 extern "C" int clipk_gemm_nt_v2_launch(const clipk_gemm_args* a, void* stream) {
-  Params p;
-  p.A = (const unsigned short*)a->A; p.lda = a->lda;
-  p.B = (const unsigned short*)a->B; p.ldb = a->ldb;
-  p.M = a->M; p.N = a->N; p.K = a->K;
-  p.e = epi_args_from(a);
+  Params p = gemm_params_from<Params>(a);
   const int ntn = (a->N + BN - 1) / BN;
   p.ntn = ntn;
   p.stagger = clipk_opt_get(OPT_GEMM_STAGGER);

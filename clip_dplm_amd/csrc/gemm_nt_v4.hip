@@ -27,56 +27,17 @@
 // wait is covered by the other workgroup.  The ring runs across output tiles: in a tile's last K-tile the refills
 // fetch K-tile 0 of the workgroup's next tile, whose stores then drain under the next main loop (vmcnt is in-order:
 // the three waits of a tile's first K-tile allow for the NS store instructions of the epilogue before it).
-#include "common.h"
-#include "gemm_epilogue.h"
-#include <stdlib.h>
-#include <type_traits>
+#include "gemm_nt_persistent.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 256, BK = 64;
+constexpr int BM = 128, BN = 256;
 constexpr int XH_BYTES = 64 * BK * 2;            // 8 KiB
 constexpr int WH_BYTES = 128 * BK * 2;           // 16 KiB
 constexpr int XH0 = 0, XH1 = XH_BYTES, WH0 = 2 * XH_BYTES, WH1 = 2 * XH_BYTES + WH_BYTES;
 constexpr int BUF_BYTES = 2 * XH_BYTES + 2 * WH_BYTES;     // 48 KiB
 constexpr int SLAB_BYTES = 16 * 64 * 4;          // per-wave epilogue slab (XOR-swizzled, unpadded)
 constexpr int LDS_BYTES = BUF_BYTES + 4 * SLAB_BYTES;      // 64 KiB: two workgroups per CU
-
-struct Params {
-  const unsigned short* A; long lda;
-  const unsigned short* B; long ldb;
-  int M, N, K;
-  EpiArgs e;
-  int ntn, ntiles;
-  int stagger;      // the second workgroup of every CU (blockIdx >= gridDim / 2) starts stagger x ~3.9 us late
-};
-
-// one quadrant: 2 n-tiles x 4 m-tiles x 2 k-halves = 16 MFMAs (k outer so dependent accumulations sit 8 apart);
-// KLO = 1: upper k-half only, for the last K-tile of a K % 64 == 32 problem (fetched as [K - 64, K), whose lower
-// half was already accumulated by the K-tile before)
-template <int NH, int MH, int KLO = 0>
-__device__ __forceinline__ void quad(f32x4 (&acc)[4][8], const bf16x8 (&wf)[2][2][2], const bf16x8 (&xf)[4][2]) {
-#pragma unroll
-  for (int kk = KLO; kk < 2; ++kk)
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[NH * 2 + t][MH * 4 + j] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[NH][t][kk], xf[j][kk], acc[NH * 2 + t][MH * 4 + j], 0, 0, 0);
-}
-
-#define CLIPK_BAR() __builtin_amdgcn_s_barrier()
-#define CLIPK_SB() __builtin_amdgcn_sched_barrier(0)
-#define CLIPK_STR2(x) #x
-#define CLIPK_STR(x) CLIPK_STR2(x)
-// counted wait that tolerates NS younger-than-the-loads store instructions (NS is a template constant 0 / 16 / 32)
-#define CLIPK_VMCNT_PLUS(base, ns)                                                              \
-  do {                                                                                          \
-    if ((ns) == 0) asm volatile("s_waitcnt vmcnt(" CLIPK_STR(base) ")" ::: "memory");           \
-    else if ((ns) == 16) asm volatile("s_waitcnt vmcnt(" CLIPK_STR(base) "+16)" ::: "memory");  \
-    else asm volatile("s_waitcnt vmcnt(" CLIPK_STR(base) "+32)" ::: "memory");                  \
-  } while (0)
 
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void gemm_nt_v4_kernel(const Params p) {
@@ -85,7 +46,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v4_kernel(const Params p) {
   static_assert(NS == 0 || NS == 16 || NS == 32, "vmcnt bookkeeping below knows 0 / 16 / 32 stores");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int M = p.M, N = p.N, K = p.K;
+  const int K = p.K;
 
   // ---- LDS-DMA assignment: a wave instruction fills one piece = 8 rows x 128 B.  Wave w takes pieces 2w, 2w + 1 of an
   // X half-tile and 4w .. 4w + 3 of a W half-tile.  lane -> (row in piece = lane >> 3, physical 16-B slot = lane & 7);
@@ -105,20 +66,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v4_kernel(const Params p) {
     wv[i] = (unsigned)(((long)((r >> 5) * 64 + (r & 31)) * p.ldb + kch) * 2);
   }
   int m0 = 0, n0 = 0;
-  using rsrc_t = decltype(__builtin_amdgcn_make_buffer_rsrc((void*)nullptr, 0, 0, 0));
   rsrc_t dx0, dx1, dw0, dw1;
-  auto desc = [&](const unsigned short* base, long ld, int row0, int rows) {      // rows [row0, rows) of a [rows][K] operand
-    const long left = (long)rows - row0;
-    const int bytes = left > 0 ? (int)(((left - 1) * ld + K) * 2) : 0;
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(base + (long)row0 * ld), 0, bytes, 0x00020000);
-  };
-  auto setup = [&](int bid) {                                   // tile -> origin and the four descriptors
-    const int tile = xcd_remap(bid, p.ntiles);
-    const int tm = tile / p.ntn, tn = tile - tm * p.ntn;
-    m0 = tm * BM; n0 = tn * BN;
-    dx0 = desc(p.A, p.lda, m0, M); dx1 = desc(p.A, p.lda, m0 + 64, M);
-    dw0 = desc(p.B, p.ldb, n0, N); dw1 = desc(p.B, p.ldb, n0 + 32, N);
-  };
+  auto setup = [&](int bid) { tile_source<BM, BN>(p, bid, m0, n0, dx0, dx1, dw0, dw1); };
   const int nk = (K + BK - 1) / BK;                             // >= 2 (launcher)
   const bool tail = (K & 63) != 0;                              // K % 64 == 32
   // K-tile T covers k in [64 T, 64 T + 64), except the last one of a K % 64 == 32 problem, which is fetched as
@@ -257,50 +206,11 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_v4_kernel(const Params p) {
   }
 }
 
-template <int MODE>
-void launch_v4(const Params& p, dim3 grid, hipStream_t st) {
-  static std::atomic<uint64_t> attr_set{0};
-  clipk_once_per_device(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_v4_kernel<MODE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-  });
-  hipLaunchKernelGGL((gemm_nt_v4_kernel<MODE>), grid, dim3(256), LDS_BYTES, st, p);
-}
-
-int cu_count4() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace
 
-// called by clipk_gemm_nt (gemm_nt.hip) after it validated the arguments (K % 32 == 0, K >= 160 as for gemm_nt_v3.hip; the
-// main loop itself needs nk >= 2)
+// gemm_nt_persistent.h has the launcher: two persistent workgroups per CU.  The dispatcher admits both persistent
+// kernels by one test (K % 32 == 0, K >= 160); the main loop here needs nk >= 2
 extern "C" int clipk_gemm_nt_v4_launch(const clipk_gemm_args* a, void* stream) {
-  Params p;
-  p.A = (const unsigned short*)a->A; p.lda = a->lda;
-  p.B = (const unsigned short*)a->B; p.ldb = a->ldb;
-  p.M = a->M; p.N = a->N; p.K = a->K;
-  p.e = epi_args_from(a);
-  const int ntm = (a->M + BM - 1) / BM, ntn = (a->N + BN - 1) / BN;
-  p.ntn = ntn;
-  p.ntiles = ntm * ntn;
-  // two persistent workgroups per CU; a multiple of 8 keeps "workgroup b runs on XCD b % 8" true for every tile it walks
-  int nwg = (2 * cu_count4()) & ~7;
-  { const int e = clipk_opt_get(OPT_GEMM_NWG); if (e >= 8) nwg = e & ~7; }                   // experiments only
-  if (nwg > p.ntiles) nwg = p.ntiles;
-  const dim3 grid(nwg);
-  p.stagger = clipk_opt_get(OPT_GEMM_STAGGER);
-  hipStream_t st = (hipStream_t)stream;
-  const int mode = select_epi_mode(a);
-  if (mode == EPI_UNSUPPORTED || (a->rope_cos && mode != EPI_ROPE && mode != EPI_ROPE_IL))
-    return CLIPK_ERR_UNSUPPORTED;                            // rotation: its own mode only
-  with_epi_mode(mode, [&](auto m) { launch_v4<decltype(m)::value>(p, grid, st); });
-  return clipk_check_launch();
+  return gemm_nt_persistent_launch(a, stream, BM, BN, 2, 256, LDS_BYTES,
+                                   [](auto m) { return gemm_nt_v4_kernel<decltype(m)::value>; });
 }

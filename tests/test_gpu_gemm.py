@@ -273,7 +273,7 @@ V34_CASES = [(s, f) for s in V34_SHAPES for f in ("a", "c")] + [(s, f) for s in 
 @pytest.mark.parametrize("kernel", ["v3", "v4"])
 @pytest.mark.parametrize("shape,fam", V34_CASES)
 def test_v3_v4_persistent_kernels_walk_several_tiles(dev, kopt, shape, fam, kernel, generic):
-    """gemm_nt_v3.hip / gemm_nt_v4.hip with gemm_nwg = 8 (gemm_nt_v3.hip:310, gemm_nt_v4.hip:295): every workgroup walks several
+    """gemm_nt_v3.hip / gemm_nt_v4.hip with gemm_nwg = 8 (gemm_nt_persistent.h:98-99): every workgroup walks several
     tiles at M = 2048 / 2072 - the prefetch of the next tile under the epilogue, vmcnt(8 + NS) / vmcnt(6 + NS) after a
     specialised epilogue's stores, the drain after the run-time one - for every epilogue request, with K = 160 (the
     smallest the dispatcher admits: nk = 3 with the half K-tile) upwards."""
@@ -286,9 +286,9 @@ def test_v3_v4_persistent_kernels_walk_several_tiles(dev, kopt, shape, fam, kern
 
 @pytest.mark.parametrize("kernel", ["v3", "v4"])
 def test_v3_v4_one_tile_per_workgroup_and_independence_of_nwg(dev, kopt, kernel):
-    """gemm_nwg = 0 (the default: one workgroup per CU, here exactly one tile each - the loop of gemm_nt_v3.hip:232-271 leaves at
+    """gemm_nwg = 0 (the default: one workgroup per CU, here exactly one tile each - the loop of gemm_nt_v3.hip:181-220 leaves at
     its first `if (!more) break`) against the bound, and BITWISE equal to gemm_nwg = 8 and 16: a tile's arithmetic does not
-    depend on which workgroup computes it or on what it computed before (acc is zeroed per tile, gemm_nt_v3.hip:239-242)."""
+    depend on which workgroup computes it or on what it computed before (acc is zeroed per tile, gemm_nt_v3.hip:188-191)."""
     ops = _ops()
     kopt("gemm_kernel", KERNEL[kernel])
     c = _case("a", 2072, 520, 480)
@@ -359,7 +359,7 @@ def test_rows_do_not_depend_on_the_batch(dev, kopt, kernel, shape, rows):
     """Rows 0 .. m - 1 of the M-row call == the call on the first m rows, bit for bit, with m inside another tile than M: an
     output element is one dot product over k of its own row and column in a fixed K order (MFMA lanes do not mix rows),
     tails are clamped (v1 / v2: gemm_nt.hip:64, gemm_nt_v2.hip:73) or zero-filled by the descriptor's range check
-    (gemm_nt_v3.hip:108-112), and only stores are predicated."""
+    (gemm_nt_persistent.h:60-64), and only stores are predicated."""
     ops = _ops()
     _select(kopt, kernel)
     c = _case("a", *shape)
@@ -390,7 +390,7 @@ def test_streaming_stores_change_nothing(dev, kopt, kernel, shape):
 @pytest.mark.parametrize("K", [64, 96, 480])
 @pytest.mark.parametrize("M", [1, 255, 257, 600])
 def test_v2_option_instantiations(dev, kopt, M, K, bm, stages):
-    """gemm_nt_v2_kernel<256, 1>, <256, 2>, <128, 2> (options gemm_bm = 256, gemm_stages = 2; gemm_nt_v2.hip:185-197): the
+    """gemm_nt_v2_kernel<256, 1>, <256, 2>, <128, 2> (options gemm_bm = 256, gemm_stages = 2; gemm_nt_v2.hip:181-193): the
     8-wave tile and the two-stage pipeline with its counted vmcnt(8) / vmcnt(6) waits (143-144), one K-step (K = 64), a
     last step with ksub = 1 (96), many (480); run-time epilogue with bias + relu + f32 residual + pre-activation.  Within the
     f64 bound, exact on family (c), and bitwise equal to the default <128, 1> instantiation: all four walk K in the same
@@ -467,7 +467,7 @@ LD_REQUESTS = [("generic_all", "relu", torch.float32, torch.float32, BF, BF, "re
 def test_leading_dimensions(dev, kopt, kernel, shape):
     """Every operand a column slice of a wider buffer: lda = K + 8, ldb = K + 16, ldc / ldp / ldd / ldr = N + 8 / 16 / 24 / 32,
     the inputs' padding NaN, the outputs' padding and GUARD rows below M a sentinel.  v3 / v4 build per-lane buffer offsets
-    and descriptor extents from lda / ldb (gemm_nt_v3.hip:102-111), the specialised epilogues their store offsets and
+    and descriptor extents from lda / ldb (gemm_nt_v3.hip:63-64, gemm_nt_persistent.h:60-64), the specialised epilogues their store offsets and
     extents from ldc / ldp (gemm_epilogue.h:193-197), the operand fetches from ldr / ldd (243-253).  Bitwise equal to the
     dense call, sentinels untouched, nothing non-finite."""
     ops = _ops()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel microbenchmarks at the BASELINE-config-2 shapes (run on the GPU box).
 
-    python tools/bench_kernels.py gemm        # gemm_nt v1 vs v2, interleaved rounds in one process
+    python tools/bench_kernels.py gemm        # gemm_nt v2 / v3 / v4 arms interleaved in one process, then the generic-K rows
     python tools/bench_kernels.py wgrad | attn | ln | all
 
 Random data (cdna_hip_programming.md §5.4 rule 25), HIP events on the launch stream, median of rounds.
@@ -50,6 +50,24 @@ GEMM_SHAPES = [  # (name, M, N, K, epilogue)
     ("esm fc1", T, 1920, 480, "gelu+d8"), ("esm d_fc2", T, 1920, 480, "dact8"),
     ("rna fc1", T, 2048, 768, "gelu+d8"), ("rna d_fc2", T, 2048, 768, "dact8"),
 ]
+# the generic-K kernel (gemm_nt.hip) at the notebook model's width 120 / FFN 200 (tests/test_gpu_models.py; K % 32 != 0): a
+# Linear and the FFN pair, through natural dispatch
+GENERIC_K_SHAPES = [("w120 lin", T, 120, 120, "bias"), ("w120 fc1", T, 200, 120, "gelu+pre"), ("w120 fc2", T, 120, 200, "res32")]
+
+
+def epilogue_kwargs(epi, M, N):
+    kw = {"bias": torch.randn(N, device=DEV)}
+    if epi == "res32":
+        kw.update(residual=torch.randn(M, N, device=DEV), out_dtype=torch.float32)
+    elif epi == "gelu+pre":
+        kw.update(act="gelu", out_preact=True)
+    elif epi == "dact":
+        kw = {"dact_aux": rnd((M, N)), "dact": "gelu"}
+    elif epi == "gelu+d8":
+        kw.update(act="gelu", out_preact=True, aux_u8=True)
+    elif epi == "dact8":
+        kw = {"dact_aux": torch.randint(0, 256, (M, N), device=DEV, dtype=torch.uint8), "dact": "gelu"}
+    return kw
 
 
 def bench_gemm():
@@ -77,18 +95,7 @@ def bench_gemm():
     tot = {n: 0.0 for n, _ in arms}
     for name, M, N, K, epi in GEMM_SHAPES:
         a, b = rnd((M, K)), rnd((N, K), scale=0.05)
-        bias = torch.randn(N, device=DEV)
-        kw = {"bias": bias}
-        if epi == "res32":
-            kw.update(residual=torch.randn(M, N, device=DEV), out_dtype=torch.float32)
-        elif epi == "gelu+pre":
-            kw.update(act="gelu", out_preact=True)
-        elif epi == "dact":
-            kw = {"dact_aux": rnd((M, N)), "dact": "gelu"}
-        elif epi == "gelu+d8":
-            kw.update(act="gelu", out_preact=True, aux_u8=True)
-        elif epi == "dact8":
-            kw = {"dact_aux": torch.randint(0, 256, (M, N), device=DEV, dtype=torch.uint8), "dact": "gelu"}
+        kw = epilogue_kwargs(epi, M, N)
         out = {}
         for n, opts in arms:
             ops.reset_options()
@@ -105,6 +112,11 @@ def bench_gemm():
         del a, b, kw
     ops.reset_options()
     print("sum: " + ", ".join(f"{n} {tot[n]:.2f} ms" for n, _ in arms))
+    for name, M, N, K, epi in GENERIC_K_SHAPES:
+        a, b = rnd((M, K)), rnd((N, K), scale=0.05)
+        kw = epilogue_kwargs(epi, M, N)
+        med, mn = timeit(lambda: ops.gemm_nt(a, b, **kw))
+        print(f"{name:12s} {M:7d} {N:5d} {K:5d} {epi:9s} | generic-K {med * 1e3:7.1f} us {2.0 * M * N * K / med / 1e9:5.0f} TF/s", flush=True)
 
 
 def bench_wgrad():
