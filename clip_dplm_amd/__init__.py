@@ -39,6 +39,8 @@ from .cluster import (KMeansResult, adjusted_rand_index, cluster_agreement, cont
 from .cluster import (calinski_harabasz_score, choose_n_clusters, davies_bouldin_score, label_separation,
                       silhouette_by_label, silhouette_samples, silhouette_score)
 from . import cluster
+from .manifold import TSNEResult, embed_spaces, knn_preservation, perplexity_bandwidths, tsne
+from . import manifold
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -61,4 +63,5 @@ __all__ = [
     "cluster", "kmeans", "KMeansResult", "contingency", "adjusted_rand_index", "normalized_mutual_info",
     "cluster_agreement", "silhouette_samples", "silhouette_score", "silhouette_by_label", "davies_bouldin_score",
     "calinski_harabasz_score", "label_separation", "choose_n_clusters",
+    "manifold", "tsne", "TSNEResult", "perplexity_bandwidths", "embed_spaces", "knn_preservation",
 ]

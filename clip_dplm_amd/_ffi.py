@@ -156,6 +156,11 @@ SIGNATURES = {
     "clipk_kmeans_step": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_label_dist_sums_workspace": (_sz, [_i, _i, _i, _i]),
     "clipk_label_dist_sums": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "clipk_cond_entropy_sums_workspace": (_sz, [_i, _i, _i]),
+    "clipk_cond_entropy_sums": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_tsne_grad_workspace": (_sz, [_i, _i, _i]),
+    "clipk_tsne_grad": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _sz, _vp]),
+    "clipk_tsne_update": (_i, [_vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clipk_sim_top2_bias_plan": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "clipk_sim_top2_bias_workspace": (_sz, [_i, _i, _i]),
     "clipk_sim_top2_bias": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1326,6 +1326,151 @@ def label_dist_sums(x, y, labels, n_labels, metric="euclidean", nx=None, ny=None
     return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
 
 
+TSNE_MAX_P = 512               # clipk_cond_entropy_sums, clipk_tsne_grad
+TSNE_MAX_B = 8                 # ... candidate bandwidths per row and walk
+TSNE_MIN_N = 3
+
+
+def cond_entropy_sums_plan(N: int):
+    """(64-query blocks, key-range splits) of the grid clipk_cond_entropy_sums launches: that of clipk_sim_lse_bias."""
+    return sim_lse_bias_plan(N, N)
+
+
+def tsne_grad_plan(N: int):
+    """(64-query blocks, key-range splits) of the grid clipk_tsne_grad launches: that of clipk_sim_lse_bias."""
+    return sim_lse_bias_plan(N, N)
+
+
+def _tsne_cloud(x, vectors, others=()):
+    """Operand checks of the t-SNE walks, before any launch.  vectors: (name, tensor or None, length)."""
+    N, _, P = _retrieval_args(x, x)
+    if P > TSNE_MAX_P:
+        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {TSNE_MAX_P})")
+    if N < TSNE_MIN_N:
+        raise ValueError(f"N = {N} is outside the kernel's limit (N >= {TSNE_MIN_N})")
+    _f32_vectors(vectors)
+    ts = (x, *(v[1] for v in vectors), *others)
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise ValueError("the t-SNE kernels need device tensors (there is no CPU fallback)")
+    _need_cuda(*ts)
+    return N, P
+
+
+def _f32_matrix(name, t, shape):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError(f"{name} must be a float32 device tensor")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor of shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _diag_offset(diag_offset) -> int:
+    diag_offset = int(diag_offset)
+    if diag_offset < -1:
+        raise ValueError(f"diag_offset must be -1 (nothing skipped) or >= 0, got {diag_offset}")
+    return diag_offset
+
+
+def cond_entropy_sums(x, betas=None, shift=None, nx=None, diag_offset=0, want_min=False, want_s0=True, want_s1=True):
+    """One walk of the cloud x [N, P] against itself (include/clipk.h: clipk_cond_entropy_sums): (dmin [N], s0 [N, B],
+    s1 [N, B]), None for an output not wanted.  betas f32 [N, B], B <= 8: per-row candidate bandwidths; betas=None asks
+    for the row minimum dmin of d_ij alone.  s0 = sum_j exp(-betas t_ij), s1 = sum_j t_ij exp(-betas t_ij) with t_ij =
+    d_ij - shift[i] (shift=None: zeros).  nx: the squared norms, computed here when not given.  diag_offset = 0 drops
+    the pair (i, i) as a term; -1 keeps it."""
+    if betas is None:
+        B, want_min, want_s0, want_s1 = 0, True, False, False
+    else:
+        if not isinstance(betas, torch.Tensor) or betas.dtype != torch.float32:
+            raise TypeError("betas must be a float32 device tensor")
+        if betas.dim() != 2 or betas.shape[0] != x.shape[0] or not betas.is_contiguous():
+            raise ValueError(f"betas must be a contiguous [N, B] tensor, got shape {tuple(betas.shape)}")
+        B = betas.shape[1]
+        if not 1 <= B <= TSNE_MAX_B:
+            raise ValueError(f"betas must hold 1..{TSNE_MAX_B} candidates per row, got {B}")
+        if not (want_s0 or want_s1):
+            raise ValueError("betas given but neither s0 nor s1 wanted")
+    N, P = _tsne_cloud(x, (("shift", shift, x.shape[0]), ("nx", nx, x.shape[0])), (betas,))
+    diag_offset = _diag_offset(diag_offset)
+    if nx is None:
+        nx = (x * x).sum(1)
+    dev = x.device
+    dmin = torch.empty(N, dtype=torch.float32, device=dev) if want_min else None
+    s0 = torch.empty((N, B), dtype=torch.float32, device=dev) if want_s0 else None
+    s1 = torch.empty((N, B), dtype=torch.float32, device=dev) if want_s1 else None
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_cond_entropy_sums_workspace(N, P, B), dev, "tsne", stream)
+    check(_timed("cond_entropy_sums", 2.0 * N * N * P,
+                 lambda: lib.clipk_cond_entropy_sums(x.data_ptr(), N, P, nx.data_ptr(), ptr(betas), B, ptr(shift),
+                                                     diag_offset, ptr(dmin), ptr(s0), ptr(s1), ws.data_ptr(), ws.numel(),
+                                                     stream)), "clipk_cond_entropy_sums")
+    return dmin, s0, s1
+
+
+def tsne_grad(x, y, beta, dmin, log_s0, nx=None, diag_offset=0, want_kl=False, out=None):
+    """The row sums of one t-SNE gradient step (include/clipk.h: clipk_tsne_grad): rows f32 [N, 6] with want_kl, [N, 5]
+    without - per row the attractive sum (2), the repulsive sum (2), sum_j w_ij and sum_j P_ij (log P_ij - log w_ij).
+    x [N, P], y [N, 2] f32; beta, dmin, log_s0 [N] from the perplexity calibration."""
+    N, P = _tsne_cloud(x, (("beta", beta, x.shape[0]), ("dmin", dmin, x.shape[0]), ("log_s0", log_s0, x.shape[0]),
+                           ("nx", nx, x.shape[0])), (y, out))
+    for name, t in (("beta", beta), ("dmin", dmin), ("log_s0", log_s0)):
+        if t is None:
+            raise TypeError(f"{name} must be a float32 device tensor")
+    _f32_matrix("y", y, (N, 2))
+    nc = 6 if want_kl else 5
+    if out is not None:
+        _f32_matrix("out", out, (N, nc))
+    diag_offset = _diag_offset(diag_offset)
+    if nx is None:
+        nx = (x * x).sum(1)
+    rows = torch.empty((N, nc), dtype=torch.float32, device=x.device) if out is None else out
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_tsne_grad_workspace(N, P, int(want_kl)), x.device, "tsne", stream)
+    check(_timed("tsne_grad", 2.0 * N * N * P,
+                 lambda: lib.clipk_tsne_grad(x.data_ptr(), N, P, nx.data_ptr(), beta.data_ptr(), dmin.data_ptr(),
+                                             log_s0.data_ptr(), y.data_ptr(), diag_offset, int(want_kl), rows.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), stream)), "clipk_tsne_grad")
+    return rows
+
+
+def tsne_update(rows, y=None, update=None, gains=None, alpha=1.0, momentum=0.8, lr=200.0, want_kl=False, want_gnorm=False,
+                z=None):
+    """The fixed-order reductions of tsne_grad's rows and, with y / update / gains [N, 2] (changed in place), the
+    delta-bar-delta step (include/clipk.h: clipk_tsne_update).  Returns (z, kl, gnorm): device scalars Z = sum_i rows[i,
+    4], the KL value (rows [N, 6] only) and the gradient's 2-norm, None where not wanted."""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32:
+        raise TypeError("rows must be a float32 device tensor")
+    if rows.dim() != 2 or rows.shape[1] not in (5, 6) or not rows.is_contiguous():
+        raise ValueError(f"rows must be a contiguous [N, 5] or [N, 6] tensor, got shape {tuple(rows.shape)}")
+    N, nc = rows.shape
+    if N < TSNE_MIN_N:
+        raise ValueError(f"N = {N} is outside the kernel's limit (N >= {TSNE_MIN_N})")
+    if want_kl and nc != 6:
+        raise ValueError("the KL value needs rows [N, 6] (tsne_grad with want_kl=True)")
+    state = (y, update, gains)
+    if any(t is not None for t in state):
+        for name, t in zip(("y", "update", "gains"), state):
+            _f32_matrix(name, t, (N, 2))
+    for t in (rows, *state, z):
+        if t is not None and not t.is_cuda:
+            raise ValueError("the t-SNE kernels need device tensors (there is no CPU fallback)")
+    _need_cuda(rows, *state, z)
+    dev = rows.device
+    if z is None:
+        z = torch.empty((), dtype=torch.float32, device=dev)
+    elif z.dtype != torch.float32 or z.numel() != 1:
+        raise TypeError("z must be a one-element float32 device tensor")
+    kl = torch.empty((), dtype=torch.float32, device=dev) if want_kl else None
+    gnorm = torch.empty((), dtype=torch.float32, device=dev) if want_gnorm else None
+    lib = _lib()
+    check(_timed("tsne_update", 0.0,
+                 lambda: lib.clipk_tsne_update(rows.data_ptr(), N, nc, float(alpha), float(momentum), float(lr), ptr(y),
+                                               ptr(update), ptr(gains), z.data_ptr(), ptr(kl), ptr(gnorm), _stream())),
+          "clipk_tsne_update")
+    return z, kl, gnorm
+
+
 def ce_logits_lse(S, S2=None, columns=False, label_offset=0):
     """LSE over the rows (optionally of [S | S2]) or the columns of materialised f32 logits + the diagonal logit."""
     _need_cuda(S, S2)

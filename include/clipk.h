@@ -1035,6 +1035,73 @@ int clipk_label_dist_sums(const float* X, int Mx, const float* Y, int Ny, int P,
                           long long diag_offset /* -1: none; else row i skips key j == i + diag_offset */,
                           float* out /*[Mx, (G + 3) / 4 * 4]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Exact t-SNE of an f32 cloud X [N,P] into a map Y [N,2] without the N x N matrix (clip_dplm_amd.manifold.tsne): what
+ * the reference's Visualizer.plot_embeddings (tong/utils/visualization.py) takes from a host library.
+ *
+ * Definitions (3 <= N, P % 4 == 0, P <= 512):
+ *     d_ij    = max(nx[i] + nx[j] - 2 <X_i, X_j>, 0)                       as in clipk_kernel_sums
+ *     m_i     = min_{j != i} d_ij
+ *     p_{j|i} = exp(-beta_i (d_ij - m_i)) / s0_i,   s0_i = sum_{j != i} exp(-beta_i (d_ij - m_i))
+ *               (subtracting m_i changes nothing mathematically; it keeps the nearest neighbour's term at exactly 1,
+ *               so no row underflows to an empty sum)
+ *     H_i(beta) = log s0_i + beta s1_i / s0_i,  s1_i = sum_{j != i} (d_ij - m_i) exp(-beta (d_ij - m_i))      (nats)
+ *     beta_i solves H_i(beta_i) = log(perplexity)
+ *     P_ij    = (p_{j|i} + p_{i|j}) / (2N)
+ *     w_ij    = 1 / (1 + |y_i - y_j|^2) for i != j,   Z = sum_{i != j} w_ij
+ *     grad_i  = 4 (alpha sum_j P_ij w_ij (y_i - y_j) - (1/Z) sum_j w_ij^2 (y_i - y_j))      alpha: the exaggeration
+ *     KL      = sum_{i != j} P_ij (log P_ij - log w_ij) + log Z,   0 log 0 = 0   (no clamp of P or Q at machine epsilon)
+ *   Diagonal rule (that of clipk_kernel_sums): the pair (i, i) is dropped as a term, never formed and subtracted.
+ *   diag_offset = -1 skips nothing; diag_offset >= 0: row i skips key j = i + diag_offset; a cloud with itself passes 0.
+ *
+ * clipk_cond_entropy_sums - one walk of X against itself, each output optional (not all NULL):
+ *     dmin[i]  = min over the kept keys of d_ij
+ *     s0[i,b]  = sum over the kept keys of exp(-betas[i,b] t_ij),   s1[i,b] = sum of t_ij exp(-betas[i,b] t_ij),
+ *     t_ij = d_ij - shift[i]       (shift NULL: zeros)
+ *   betas [N,B] are PER-ROW candidate bandwidths, 1 <= B <= 8, held in the registers of the row's lane; d is formed once
+ *   per element and the B exponentials applied to it.  B = 0 (betas, s0, s1 NULL) asks for dmin alone: the first pass.
+ *   With shift = dmin of an earlier call every t_ij >= 0 and the nearest neighbour's term is exactly 1: the same walk
+ *   forms the same d bit for bit.  exp(-beta t) = 2^(c t) with c = -beta log2 e held in two parts, as clipk_kernel_sums.
+ *   Kernel: the grid, key split and split-order finalize of clipk_kernel_sums without kbary (clipk_sim_lse_bias_plan
+ *   reports the grid for Mx = Ny = N).
+ *
+ * clipk_tsne_grad - one walk per gradient step: rows [N,6] (want_kl) or [N,5], per row i the sums over the kept keys j
+ *     rows[i,0:2] = sum_j P_ij w_ij (y_i - y_j)        rows[i,2:4] = sum_j w_ij^2 (y_i - y_j)
+ *     rows[i,4]   = sum_j w_ij                          rows[i,5]   = sum_j P_ij (log P_ij - log w_ij)
+ *   beta, dmin (= m), log_s0 [N] come from clipk_cond_entropy_sums (log_s0 = log s0 at beta with shift = dmin); Y [N,2].
+ *   The entry packs one 32-byte record per point (norm, c in two parts, m, log2 s0, y0, y1) into the workspace; the walk
+ *   stages the tile's 64 key records in LDS.  The exponent is -beta (d - m) - log s0 computed from (d - m), never as
+ *   a d + b with beta m folded into b.  Per element: two v_exp_f32, one v_rcp_f32, no division; one v_log_f32 more with
+ *   want_kl.  The other five sums are bit-identical with and without want_kl.
+ *
+ * clipk_tsne_update - the reductions of rows in a fixed order (one workgroup) and the delta-bar-delta step:
+ *     z[0] = Z = sum_i rows[i,4];  kl[0] = sum_i rows[i,5] + log Z (ncomp = 6 only);  gnorm[0] = |grad|_2
+ *     grad = 4 (alpha rows[:,0:2] - rows[:,2:4] / Z)
+ *     inc = update * grad < 0;  gains = max(inc ? gains + 0.2 : gains * 0.8, 0.01)
+ *     update = momentum * update - lr * gains * grad;   Y += update
+ *   z is required and is read back from device memory by the step; kl, gnorm may be NULL.  Y, update, gains [N,2]: all
+ *   three, or all NULL for the reductions alone.
+ *
+ *   Supported: 3 <= N, P % 4 == 0, P <= 512, 0 <= B <= 8, X / workspace 16-byte aligned.
+ * Anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED before any launch and the workspace helpers return 0.
+ * Never allocates, never synchronises, no host read, capturable, no float atomics, no cooperative launch: results depend
+ * on the shapes and inputs alone. */
+size_t clipk_cond_entropy_sums_workspace(int N, int P, int B);
+int clipk_cond_entropy_sums(const float* X, int N, int P, const float* nx /*[N] = |x_i|^2*/,
+                            const float* betas /*[N,B] or NULL (B = 0)*/, int B, const float* shift /*[N] or NULL*/,
+                            long long diag_offset /* -1: none; else row i skips key j == i + diag_offset */,
+                            float* dmin /*[N] or NULL*/, float* s0 /*[N,B] or NULL*/, float* s1 /*[N,B] or NULL*/,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t clipk_tsne_grad_workspace(int N, int P, int want_kl);
+int clipk_tsne_grad(const float* X, int N, int P, const float* nx /*[N]*/, const float* beta /*[N]*/,
+                    const float* dmin /*[N]*/, const float* log_s0 /*[N]*/, const float* Y /*[N,2]*/,
+                    long long diag_offset, int want_kl, float* rows /*[N, want_kl ? 6 : 5]*/, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int clipk_tsne_update(const float* rows /*[N,ncomp]*/, int N, int ncomp /* 5 or 6 */, float alpha, float momentum,
+                      float lr, float* Y /*[N,2] or NULL*/, float* update /*[N,2]*/, float* gains /*[N,2]*/,
+                      float* z /* device scalar */, float* kl /* device scalar or NULL */,
+                      float* gnorm /* device scalar or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
