@@ -41,6 +41,8 @@ from .cluster import (calinski_harabasz_score, choose_n_clusters, davies_bouldin
 from . import cluster
 from .manifold import TSNEResult, embed_spaces, knn_preservation, perplexity_bandwidths, tsne
 from . import manifold
+from .mixing import LabelMasses, integration_scores, label_masses, label_transfer, label_transfer_accuracy, lisi
+from . import mixing
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -64,4 +66,5 @@ __all__ = [
     "cluster_agreement", "silhouette_samples", "silhouette_score", "silhouette_by_label", "davies_bouldin_score",
     "calinski_harabasz_score", "label_separation", "choose_n_clusters",
     "manifold", "tsne", "TSNEResult", "perplexity_bandwidths", "embed_spaces", "knn_preservation",
+    "mixing", "lisi", "label_masses", "LabelMasses", "label_transfer", "label_transfer_accuracy", "integration_scores",
 ]

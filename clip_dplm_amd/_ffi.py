@@ -156,6 +156,9 @@ SIGNATURES = {
     "clipk_kmeans_step": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_label_dist_sums_workspace": (_sz, [_i, _i, _i, _i]),
     "clipk_label_dist_sums": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "clipk_label_kernel_sums_workspace": (_sz, [_i, _i, _i, _i]),
+    "clipk_label_kernel_sums": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                     _vp]),
     "clipk_cond_entropy_sums_workspace": (_sz, [_i, _i, _i]),
     "clipk_cond_entropy_sums": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipk_tsne_grad_workspace": (_sz, [_i, _i, _i]),

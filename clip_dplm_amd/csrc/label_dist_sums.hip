@@ -17,6 +17,10 @@
 // through LDS in wave order after the walk (measured: profiles/silhouette).
 // The skipped key of a row (diag_offset) is dropped as a term - never formed and subtracted: a computed d2_ii of
 // rounding size would enter as its square root.
+// clipk_label_kernel_sums is the same walk with one more element function (MODE_KERNEL): the per-row Gaussian of
+// tsne.hip's cond_entropy_walk, w = exp(-beta_i (d2 - shift_i)), on the d2 of the sqeuclidean mode - the label masses LISI
+// is made of (clip_dplm_amd.mixing).  beta_i, c in two parts and shift_i sit in the row's lane next to nx_i.  Its finalize
+// (label_kernel_finalize) also forms the row statistics, so the Mx x G result need not be written at all.
 // No float atomics, no cooperative launch: results depend on the shapes and inputs alone.
 #include "common.h"
 #include "cloud_keysum.h"
@@ -27,7 +31,8 @@ namespace {
 constexpr int LD_PMAX = KEYSUM_PMAX;              // contraction limit
 constexpr int LD_GMAX = KEYSUM_PMAX;              // labels per launch: the second product's output width
 constexpr int LD_GSMALL = 64;                     // at most this many labels: the key-split form of the second product
-enum { MODE_EUCLIDEAN = 0, MODE_SQEUCLIDEAN = 1, MODE_COSINE = 2 };
+enum { MODE_EUCLIDEAN = 0, MODE_SQEUCLIDEAN = 1, MODE_COSINE = 2, MODE_KERNEL = 3 };  // 3: clipk_label_kernel_sums' own
+constexpr float L_HI = 1.44269502162933349609375f, L_LO = 1.92596299112661746e-8f;   // log2(e) = L_HI + L_LO
 
 struct LDP {
   const float* X; int Mx;
@@ -38,6 +43,7 @@ struct LDP {
   long long diag_offset;                          // -1: none; row i skips key i + diag_offset
   float* slab;                                    // [ksplit][Mx][Gp]
   int tiles_per_split, ntiles;
+  const float* beta; const float* shift;          // MODE_KERNEL: [Mx] per-row bandwidths, [Mx] shifts or null (zeros)
 };
 
 constexpr int LD_LDS_FLOATS = KLOOP_LDS_FLOATS + KEYSUM_LDS_FLOATS;       // K-loop buffers + distance tile + staged block
@@ -100,6 +106,16 @@ __global__ __launch_bounds__(256, 2) void label_dist_sums_kernel(const LDP p) {
   const int tid = w.tid, wid = w.wid, Ny = p.Ny, G = p.G, Gp = p.Gp;
   float nx_i = 0.f;
   if constexpr (MODE != MODE_COSINE) nx_i = p.nx[qg < p.Mx ? qg : p.Mx - 1];
+  // MODE_KERNEL: exp(-beta t) = 2^(c t) with c = -beta log2(e) held as cg + cl, the row's own (the lane is the query), and
+  // t = d - shift_i: d, t and the exponent exactly as tsne.hip's cond_entropy_walk forms them
+  float cg = 0.f, cl = 0.f, sh_i = 0.f;
+  if constexpr (MODE == MODE_KERNEL) {
+    const int qc = qg < p.Mx ? qg : p.Mx - 1;
+    const float gm = -p.beta[qc];
+    cg = gm * L_HI;
+    cl = fmaf(gm, L_HI, -cg) + gm * L_LO;
+    sh_i = p.shift ? p.shift[qc] : 0.f;
+  }
   // this query's skipped key, -1 where there is none (or it lies beyond Ny: nothing to skip)
   int skip = -1;
   if (p.diag_offset >= 0) {
@@ -128,6 +144,10 @@ __global__ __launch_bounds__(256, 2) void label_dist_sums_kernel(const LDP p) {
         const float ny_j = p.ny[key < Ny ? key : Ny - 1];
         d = fmaxf(fmaf(-2.f, acc[r], nx_i + ny_j), 0.f);
         if constexpr (MODE == MODE_EUCLIDEAN) d = __builtin_amdgcn_sqrtf(d);          // v_sqrt_f32: 1 ulp
+        if constexpr (MODE == MODE_KERNEL) {
+          const float t = d - sh_i;
+          d = __builtin_amdgcn_exp2f(fmaf(cg, t, cl * t));                            // one v_exp_f32, no division
+        }
       }
       if (key >= Ny || qg >= p.Mx || key == skip) d = 0.f;                // the term is dropped, not subtracted
       gl[kl * TQ + wn * 32 + li] = d;
@@ -239,6 +259,48 @@ void launch_mode(const LDP& p, dim3 grid, hipStream_t stream) {
   else launch_walk<MODE, 0>(p, grid, stream);
 }
 
+// the walk of either entry on the grid of the LSE pass: p without its plan and slab
+void launch_label_walk(LDP& p, int mode, const KeySplitPlan& k, void* workspace, hipStream_t stream) {
+  p.Gp = (p.G + 3) & ~3;
+  p.slab = (float*)workspace;
+  p.tiles_per_split = k.tiles_per_split; p.ntiles = k.ntiles;
+  const dim3 grid(k.nqb, k.ksplit);
+  if (mode == MODE_EUCLIDEAN) launch_mode<MODE_EUCLIDEAN>(p, grid, stream);
+  else if (mode == MODE_SQEUCLIDEAN) launch_mode<MODE_SQEUCLIDEAN>(p, grid, stream);
+  else if (mode == MODE_COSINE) launch_mode<MODE_COSINE>(p, grid, stream);
+  else launch_mode<MODE_KERNEL>(p, grid, stream);
+}
+
+// clipk_label_kernel_sums' finalize, one row per thread: the key-split slabs in split order, label by label in ascending
+// order; out (null: never written), and from the same summed values mass = sum_g, sumsq = sum_g ^2, the arg max (equal
+// values: the lower label) and its value.  The values are sums of non-negative terms: -1 loses to every one of them.
+__global__ __launch_bounds__(256) void label_kernel_finalize(const float* slab, int ksplit, int Mx, int G, int Gp, float* out,
+                                                             float* mass, float* sumsq, int* top, float* best) {
+  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+  const long slab_n = (long)Mx * Gp;
+  for (long i = tid; i < Mx; i += nth) {
+    float m = 0.f, q = 0.f, bv = -1.f;
+    int bg = 0;
+    for (int g4 = 0; g4 < Gp; g4 += 4) {
+      const long at = i * Gp + g4;
+      f32x4 a = *reinterpret_cast<const f32x4*>(slab + at);
+      for (int s = 1; s < ksplit; ++s) a += *reinterpret_cast<const f32x4*>(slab + (long)s * slab_n + at);
+      if (out) *reinterpret_cast<f32x4*>(out + at) = a;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (g4 + e < G) {
+          m += a[e];
+          q = fmaf(a[e], a[e], q);
+          if (a[e] > bv) { bv = a[e]; bg = g4 + e; }
+        }
+    }
+    if (mass) mass[i] = m;
+    if (sumsq) sumsq[i] = q;
+    if (top) top[i] = bg;
+    if (best) best[i] = bv;
+  }
+}
+
 }  // namespace
 
 extern "C" size_t clipk_label_dist_sums_workspace(int Mx, int Ny, int P, int G) {
@@ -257,16 +319,39 @@ extern "C" int clipk_label_dist_sums(const float* X, int Mx, const float* Y, int
   if (workspace_bytes < clipk_label_dist_sums_workspace(Mx, Ny, P, G)) return CLIPK_ERR_BAD_ARG;
   const KeySplitPlan k = key_split_plan(Mx, Ny, TQ);                      // the grid of the LSE pass
   LDP p{};
-  p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.G = G; p.Gp = (G + 3) & ~3; p.labels = labels; p.nx = nx; p.ny = ny;
+  p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.G = G; p.labels = labels; p.nx = nx; p.ny = ny;
   p.diag_offset = diag_offset;
-  p.slab = (float*)workspace;
-  p.tiles_per_split = k.tiles_per_split; p.ntiles = k.ntiles;
-  const dim3 grid(k.nqb, k.ksplit);
-  if (mode == MODE_EUCLIDEAN) launch_mode<MODE_EUCLIDEAN>(p, grid, (hipStream_t)stream);
-  else if (mode == MODE_SQEUCLIDEAN) launch_mode<MODE_SQEUCLIDEAN>(p, grid, (hipStream_t)stream);
-  else launch_mode<MODE_COSINE>(p, grid, (hipStream_t)stream);
+  launch_label_walk(p, mode, k, workspace, (hipStream_t)stream);
   int rc = clipk_check_launch();
   if (rc) return rc;
   launch_split_sum_finalize(p.slab, nullptr, nullptr, k.ksplit, Mx, p.Gp, out, nullptr, nullptr, (hipStream_t)stream);
+  return clipk_check_launch();
+}
+
+extern "C" size_t clipk_label_kernel_sums_workspace(int Mx, int Ny, int P, int G) {
+  return clipk_label_dist_sums_workspace(Mx, Ny, P, G);                   // the same slabs
+}
+
+extern "C" int clipk_label_kernel_sums(const float* X, int Mx, const float* Y, int Ny, int P, const int* labels, int G,
+                                       const float* beta, const float* shift, const float* nx, const float* ny,
+                                       long long diag_offset, float* out, float* mass, float* sumsq, int* top, float* best,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (Mx <= 0 || Ny <= 0 || P <= 0 || G <= 0 || diag_offset < -1) return CLIPK_ERR_BAD_ARG;
+  if (!shape_ok(Mx, Ny, P, G)) return CLIPK_ERR_UNSUPPORTED;
+  if (!X || !Y || !labels || !beta || !nx || !ny || !workspace) return CLIPK_ERR_BAD_ARG;
+  if (!out && !mass && !sumsq && !top && !best) return CLIPK_ERR_BAD_ARG;
+  if (!aligned16(X) || !aligned16(Y) || (out && !aligned16(out)) || !aligned16(workspace)) return CLIPK_ERR_BAD_ARG;
+  if (workspace_bytes < clipk_label_kernel_sums_workspace(Mx, Ny, P, G)) return CLIPK_ERR_BAD_ARG;
+  const KeySplitPlan k = key_split_plan(Mx, Ny, TQ);                      // the grid of the LSE pass
+  LDP p{};
+  p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.G = G; p.labels = labels; p.nx = nx; p.ny = ny;
+  p.diag_offset = diag_offset; p.beta = beta; p.shift = shift;
+  launch_label_walk(p, MODE_KERNEL, k, workspace, (hipStream_t)stream);
+  int rc = clipk_check_launch();
+  if (rc) return rc;
+  int blocks = (Mx + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(label_kernel_finalize, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p.slab, k.ksplit, Mx, G, p.Gp, out,
+                     mass, sumsq, top, best);
   return clipk_check_launch();
 }

@@ -1326,7 +1326,59 @@ def label_dist_sums(x, y, labels, n_labels, metric="euclidean", nx=None, ny=None
     return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
 
 
-TSNE_MAX_P = 512               # clipk_cond_entropy_sums, clipk_tsne_grad
+def label_kernel_sums(x, y, labels, n_labels, beta, shift=None, nx=None, ny=None, diag_offset=-1, want_out=True,
+                      want_stats=True):
+    """Per-label Gaussian masses (include/clipk.h: clipk_label_kernel_sums): (out, mass, sumsq, top, best) with
+    out f32 [Mx, n_labels], out[i, g] = the sum of exp(-beta[i] (d_ij - shift[i])) over the keys j with labels[j] == g,
+    d_ij = max(nx_i + ny_j - 2 <x_i, y_j>, 0); mass = sum_g out, sumsq = sum_g out^2, top int32 = arg max_g out (equal
+    values: the lower g) and best = that value, [Mx] each.  want_out=False: out is None and the Mx x n_labels result is never
+    written; want_stats=False: the four row statistics are None.  x [Mx, P], y [Ny, P] f32, labels int32 [Ny] (a label
+    outside [0, n_labels) belongs to no column), n_labels <= 512: ONE walk - a caller with more labels walks once per
+    512 and merges.  beta f32 [Mx] > 0 per row, shift f32 [Mx] or None (zeros); nx, ny: the squared norms, computed here
+    when not given.  diag_offset as in label_dist_sums.  ops.cond_entropy_sums_plan reports the grid for Mx = Ny."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    if P > LABEL_DIST_MAX_P:
+        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {LABEL_DIST_MAX_P})")
+    if isinstance(n_labels, bool) or not isinstance(n_labels, int):
+        raise TypeError(f"n_labels must be an int, got {n_labels!r}")
+    if not 1 <= n_labels <= LABEL_DIST_MAX_G:
+        raise ValueError(f"n_labels must be in [1, {LABEL_DIST_MAX_G}], got {n_labels}")
+    if not (want_out or want_stats):
+        raise ValueError("neither out nor the row statistics wanted")
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError("labels must be an int32 tensor")
+    _int32_vector("labels", labels, Ny, x.device)
+    if beta is None:
+        raise TypeError("beta must be a float32 device tensor")
+    _f32_vectors((("beta", beta, Mx), ("shift", shift, Mx), ("nx", nx, Mx), ("ny", ny, Ny)))
+    diag_offset = _diag_offset(diag_offset)
+    for t in (x, y, labels, beta, shift, nx, ny):
+        if t is not None and not t.is_cuda:
+            raise ValueError("the label-kernel walk needs device tensors (there is no CPU fallback)")
+    _need_cuda(x, y, labels, beta, shift, nx, ny)
+    if nx is None:
+        nx = (x * x).sum(1)
+    if ny is None:
+        ny = nx if y is x else (y * y).sum(1)
+    dev = x.device
+    G, Gp = n_labels, (n_labels + 3) // 4 * 4
+    out = torch.empty((Mx, Gp), dtype=torch.float32, device=dev) if want_out else None
+    mass, sumsq, best = (torch.empty(Mx, dtype=torch.float32, device=dev) if want_stats else None for _ in range(3))
+    top = torch.empty(Mx, dtype=torch.int32, device=dev) if want_stats else None
+    lib = _lib()
+    stream = _stream()
+    ws = workspace(lib.clipk_label_kernel_sums_workspace(Mx, Ny, P, G), dev, "label_dist", stream)
+    check(_timed("label_kernel_sums", 2.0 * Mx * Ny * (P + Gp),
+                 lambda: lib.clipk_label_kernel_sums(x.data_ptr(), Mx, y.data_ptr(), Ny, P, labels.data_ptr(), G,
+                                                     beta.data_ptr(), ptr(shift), nx.data_ptr(), ny.data_ptr(), diag_offset,
+                                                     ptr(out), ptr(mass), ptr(sumsq), ptr(top), ptr(best), ws.data_ptr(),
+                                                     ws.numel(), stream)), "clipk_label_kernel_sums")
+    if want_out and Gp != G:
+        out = out[:, :G]
+    return out, mass, sumsq, top, best
+
+
+TSNE_MAX_P = 512              # clipk_cond_entropy_sums, clipk_tsne_grad
 TSNE_MAX_B = 8                 # ... candidate bandwidths per row and walk
 TSNE_MIN_N = 3
 

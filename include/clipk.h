@@ -1036,6 +1036,45 @@ int clipk_label_dist_sums(const float* X, int Mx, const float* Y, int Ny, int P,
                           float* out /*[Mx, (G + 3) / 4 * 4]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-label Gaussian masses of each point's perplexity-calibrated neighbourhood, without the Mx x Ny affinities or an
+ * N x G one-hot: what LISI (local inverse Simpson's index) and the leave-one-out kernel vote are made of
+ * (clip_dplm_amd.mixing).  f32 clouds X [Mx,P], Y [Ny,P].
+ *
+ * clipk_label_kernel_sums:
+ *     d_ij  = max(nx[i] + ny[j] - 2 <X_i, Y_j>, 0)      (cosine: the caller passes unit rows scaled by sqrt(1/2): d = 1 - cos)
+ *     t_ij  = d_ij - shift[i]                            (shift NULL: zeros)
+ *     w_ij  = exp(-beta[i] t_ij)                         beta [Mx] > 0, PER ROW, read by the kernel from device memory
+ *     out[i,g]  = sum over { j < Ny : labels[j] == g, j != i + diag_offset } of w_ij       i < Mx, 0 <= g < G
+ *     mass[i]   = sum_g out[i,g]      sumsq[i] = sum_g out[i,g]^2      (g ascending: a fixed order)
+ *     top[i]    = arg max_g out[i,g]  (equal values: the lower g),      best[i] = that value
+ *   Every output is optional, not all NULL.  out [Mx, Gp] with the row stride Gp = G rounded up to a multiple of 4; the
+ *   padding columns are zeros.  Without out the Mx x G result is never written: the finalize launch that sums the
+ *   key-split slabs in split order also forms mass, sumsq, top and best, one row per thread, from the same summed values -
+ *   the four are bit-identical with and without out.
+ *   labels [Ny] int32: an entry outside [0, G) belongs to no column, as in clipk_label_dist_sums - that is how a caller
+ *   handles more than 512 labels (one walk per 512) or leaves points out.
+ *   Diagonal rule (that of clipk_kernel_sums): diag_offset = -1 skips nothing; diag_offset >= 0: row i skips key
+ *   j = i + diag_offset - the term is dropped, never formed and subtracted.  Rows [r0, r1) of a cloud against the whole
+ *   cloud: diag_offset = r0.
+ *   d is formed exactly as clipk_cond_entropy_sums forms it (the same K-loop, the same norm expansion): with shift = dmin
+ *   from that entry the nearest neighbour's term is exactly 1 and every t_ij >= 0.  exp(-beta t) = 2^(c t) with
+ *   c = -beta log2 e held in two parts, as clipk_kernel_sums: one v_exp_f32 per element, no division.
+ *   Kernel: the walk of clipk_label_dist_sums (both forms of the second product) with one more element function; beta_i,
+ *   c and shift_i sit in the row's lane registers.  The grid is that of clipk_sim_lse_bias (clipk_sim_lse_bias_plan).
+ *   Supported: Mx, Ny >= 1, P % 4 == 0, P <= 512, 1 <= G <= 512, X / Y / out / workspace 16-byte aligned.
+ * Anything else returns CLIPK_ERR_BAD_ARG or CLIPK_ERR_UNSUPPORTED before any launch and the workspace helper returns 0.
+ * Never allocates, never synchronises, capturable, no float atomics, no cooperative launch: results depend on the shapes
+ * and inputs alone. */
+size_t clipk_label_kernel_sums_workspace(int Mx, int Ny, int P, int G);
+int clipk_label_kernel_sums(const float* X, int Mx, const float* Y, int Ny, int P, const int* labels /*[Ny]*/, int G,
+                            const float* beta /*[Mx]*/, const float* shift /*[Mx] or NULL*/,
+                            const float* nx /*[Mx] = |x_i|^2*/, const float* ny /*[Ny] = |y_j|^2*/,
+                            long long diag_offset /* -1: none; else row i skips key j == i + diag_offset */,
+                            float* out /*[Mx, (G + 3) / 4 * 4] or NULL*/, float* mass /*[Mx] or NULL*/,
+                            float* sumsq /*[Mx] or NULL*/, int* top /*[Mx] or NULL*/, float* best /*[Mx] or NULL*/,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact t-SNE of an f32 cloud X [N,P] into a map Y [N,2] without the N x N matrix (clip_dplm_amd.manifold.tsne): what
  * the reference's Visualizer.plot_embeddings (tong/utils/visualization.py) takes from a host library.
  *
