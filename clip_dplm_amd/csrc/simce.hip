@@ -26,7 +26,7 @@ namespace {
 constexpr int QB = 32;          // queries per workgroup
 constexpr int KT = 32;          // keys per tile
 constexpr int PWMAX = 128;      // contraction slice per wave
-constexpr int MAXW = 8;         // P <= 1024
+constexpr int MAXW = 8;         // waves per workgroup; make_plan's LDS limit leaves P <= 960
 constexpr int MAXZ = 6;         // problems per batched launch
 
 enum { MODE_LSE = 0, MODE_GRAD = 1, MODE_LOGITS = 2 };
@@ -744,6 +744,9 @@ extern "C" int clipk_simce_grad_pairs(const float* E, int nmod, int B, int P, co
     return CLIPK_ERR_BAD_ARG;
   Plan pl;
   if (!make_plan(B, B, P, &pl)) return CLIPK_ERR_UNSUPPORTED;
+  // the first-generation gradient pass walks its P slice in blocks of 32 columns (clipk_simce_grad_scaled has the same
+  // rule and a tiled pass to send such P to; here the caller takes clipk_simce_grad_pairs_cls without ids)
+  if (pl.Pw % 32) return CLIPK_ERR_UNSUPPORTED;
   if (!aligned16(E) || !aligned16(dX) || !aligned16(workspace) || (((size_t)B * P * 4) & 15)) return CLIPK_ERR_BAD_ARG;
   const long z_slab = (long)pl.ksplit * B * P, z_dsc = (long)pl.ksplit * B;
   if (workspace_bytes < (size_t)npairs * (z_slab + z_dsc) * sizeof(float)) return CLIPK_ERR_BAD_ARG;

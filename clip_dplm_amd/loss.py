@@ -25,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from ._ffi import ClipkError
 
 # kernel namespace; tests of the rank bookkeeping (gloo, CPU) substitute a torch restatement here — the product
 # itself never does: ops.* raise on anything but device tensors.
@@ -298,10 +299,27 @@ def _tri_plain_lse(E, scale, ids6):
     return lse, pos, (lse,)
 
 
-_TRI_PLAIN = _TriVariant(
-    lse=_tri_plain_lse,
-    grad=lambda E, scale, stat, inv_b, ids6, g: _kernels.simce_grad_pairs(E, _TRI_PAIRS, scale, stat[0], 0.5, 0.5, inv_b),
-    folds=False)
+def _tri_plain_slice_ok(P: int) -> bool:
+    """clipk_simce_grad_pairs's rule (csrc/simce.hip: make_plan): its gradient pass walks each wave's slice of P - P
+    over 1, 2, 4 or 8 waves of at most 128 columns, rounded up to 8 - in blocks of 32 columns.
+    tests/test_simce_ref_host.py holds this to the restatement of make_plan in tests/simce_ref.py."""
+    nw = 1
+    while nw < 8 and -(-P // nw) > 128:
+        nw *= 2
+    return ((-(-P // nw) + 7) & ~7) % 32 == 0
+
+
+def _tri_plain_grad(E, scale, stat, inv_b, ids6, g):
+    """clipk_simce_grad_pairs; at a width it refuses (P = 36, 48, 160, ...) up to 512 the batched class-aware gradient
+    pass without ids and smoothing, from the same LSE vectors and with every same-class count 1: the same gradient, as
+    clipk_simce_grad_scaled sends such P to the tiled pass.  (Above 512 the entry's own refusal stands.)"""
+    P = E.shape[-1]
+    if _tri_plain_slice_ok(P) or P > 512:
+        return _kernels.simce_grad_pairs(E, _TRI_PAIRS, scale, stat[0], 0.5, 0.5, inv_b)
+    return _kernels.simce_grad_pairs_cls(E, _TRI_PAIRS, scale, stat[0], torch.ones_like(stat[0]), 0.5, 0.5, inv_b)
+
+
+_TRI_PLAIN = _TriVariant(lse=_tri_plain_lse, grad=_tri_plain_grad, folds=False)
 
 
 def _tri_class_aware(same_class: str, eps: float) -> _TriVariant:
@@ -395,7 +413,10 @@ def tri_modal_loss(cell_embed: torch.Tensor, pert_embed: torch.Tensor, protein_e
     class_ids, same_class, label_smoothing, hard_negative_beta: clip_loss's, applied to every pair.  class_ids is one
     integer tensor [B] used for all three pairs (a PerturbAtlas batch, whose perturbation and protein rows repeat, one
     per cell: class_ids=pert_id), or a mapping with keys among "cell_pert", "cell_protein", "pert_protein"; a pair
-    without ids is all distinct.  Defaults: exactly the plain loss and its kernels."""
+    without ids is all distinct.  Defaults: exactly the plain loss and its kernels, at every P % 4 == 0 up to 512
+    (at a width the plain batched gradient pass does not take, P = 36, 48, 160, ..., the backward runs the class-aware
+    gradient pass without ids: the same gradient); above 512 ClipkError unless the slice of P per wave, there P / 8
+    rounded up to 8, is a multiple of 32 (768)."""
     pairs = ((cell_embed, pert_embed), (cell_embed, protein_embed), (pert_embed, protein_embed))
     ids = []
     for (a, b), t in zip(pairs, _tri_class_ids(class_ids)):
@@ -415,6 +436,9 @@ def tri_modal_loss(cell_embed: torch.Tensor, pert_embed: torch.Tensor, protein_e
             cp, ce, pe = TriModalLossFn.apply(*args, _tri_hard_negative(beta), *ids)
         elif eps > 0.0 or any(t is not None for t in ids):
             cp, ce, pe = TriModalLossFn.apply(*args, _tri_class_aware(same_class, eps), *ids)
-        else:
+        elif cell_embed.shape[-1] <= 512 or cell_embed.shape[-1] % 4 or _tri_plain_slice_ok(cell_embed.shape[-1]):
             cp, ce, pe = TriModalLossFn.apply(*args)
+        else:                                              # no gradient pass takes it: say so before the forward pass
+            raise ClipkError(f"tri_modal_loss: unsupported projection width P = {cell_embed.shape[-1]}: above 512 the "
+                             f"gradient pass needs a slice of P per wave that is a multiple of 32, as P = 768 gives")
     return {"loss": cp + ce + pe, "cell_pert_loss": cp, "cell_protein_loss": ce, "pert_protein_loss": pe}

@@ -248,7 +248,10 @@ int clipk_simce_grad_hard(const float* X, int Mx, const float* Y, int Ny, const 
  *   lse_pairs : lse[i][b] = LSE_j scale <X_b, Y_j>, pos[i][b] = scale <X_b, Y_b>
  *   grad_pairs: dX[i] = complete gradient of (w_row CE_rows + w_col CE_cols)(X, Y) * inv_bg w.r.t. the rows of X,
  *               using lse[i] for the rows and lse[reverse[i]] (the problem with X and Y exchanged) for the keys.
- * E: f32 [nmod][B][P] contiguous; pairs / reverse: HOST int arrays; npairs <= 6. */
+ * E: f32 [nmod][B][P] contiguous; pairs / reverse: HOST int arrays; npairs <= 6.
+ * grad_pairs needs a P slice per wave (P over 1, 2, 4 or 8 waves of at most 128 columns, rounded up to 8) that is a
+ * multiple of 32, as P = 32, 64, 96, 128, 192, 256, 384, 512, 768 give: CLIPK_ERR_UNSUPPORTED otherwise
+ * (clipk_simce_grad_pairs_cls without ids, with cnt = 1, is the same gradient at every P % 4 == 0, P <= 512). */
 size_t clipk_simce_pairs_workspace(int npairs, int B, int P);
 int clipk_simce_lse_pairs(const float* E, int nmod, int B, int P, const int* pairs, int npairs, const float* scale,
                           float* lse /*[npairs][B]*/, float* pos /*[npairs][B]*/, void* workspace,

@@ -43,7 +43,8 @@ def _ids(pattern, n, dev, seed=0):
         ids = torch.full((n,), 5)
     elif pattern == "random":
         ids = torch.randint(0, max(1, n // 4), (n,), generator=g)
-    else:                                                     # runs of 100 that cross 64-key tiles and key splits
+    else:                           # runs of 100 that cross 64-key tiles; at these shapes a key split is one tile
+        #                             (splits of several tiles: tests/test_gpu_simce.py)
         ids = (torch.arange(n) + 30) // 100 + (1 << 40)
     return ids.to(torch.int64).to(dev)
 
