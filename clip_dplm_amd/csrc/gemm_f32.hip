@@ -500,16 +500,15 @@ extern "C" int clipk_gemm_wgrad_f32(const float* dY, int64_t lddy, const float* 
     else hipLaunchKernelGGL((wgrad_f32_small_kernel<2>), grid, dim3(256), 0, (hipStream_t)stream, p);
     return clipk_check_launch();
   }
-  // many rows: the tiled kernel (contraction-major operands) and the column reduce
+  // many rows: the tiled kernel (contraction-major operands) and the column reduce (which takes dense rows: refused
+  // BEFORE the product is launched, so that a refused call leaves dW as it was)
+  if (dbias && lddy != N) return CLIPK_ERR_UNSUPPORTED;
   if (dW) {
     const int rc = clipk_gemm_f32(dY, lddy, 1, X, ldx, 1, N, K, M, nullptr, nullptr, accumulate ? dW : nullptr, lddw, nullptr,
                                   dW, lddw, nullptr, 0, stream);
     if (rc != CLIPK_OK) return rc;
   }
-  if (dbias) {
-    if (lddy != N) return CLIPK_ERR_UNSUPPORTED;             // (the column reduce takes dense rows)
-    return clipk_colsum_f32(dY, M, N, dbias, accumulate, stream);
-  }
+  if (dbias) return clipk_colsum_f32(dY, M, N, dbias, accumulate, stream);
   return CLIPK_OK;
 }
 

@@ -587,7 +587,8 @@ int clipk_colreduce_batched(const int64_t* desc_dev, int n, int max_cols, void* 
  * RNARBPCLIPModel / ContrastiveModel, current/rna_clip_codes.ipynb:1911-1954) - the f32 sibling of clipk_gemm_wgrad.
  * dW or dbias may be NULL (not both).  accumulate != 0 adds into dW / dbias (a parameter's .grad).  M <= 64 (the models
  * sliced to the one position they pool: M = batch rows): ONE launch, one pass over dW with dbias from the same operand
- * registers; more rows: the tiled clipk_gemm_f32 (contraction-major operands) + clipk_colsum_f32 (needs lddy == N).
+ * registers; more rows (or dbias alone): the tiled clipk_gemm_f32 (contraction-major operands) + clipk_colsum_f32, which
+ * needs lddy == N: dbias with another lddy is CLIPK_ERR_UNSUPPORTED there, refused before anything is launched (dW untouched).
  * dW is bit-identical to clipk_gemm_f32(dY, transA = 1, X, transB = 1, addend = dW) either way. */
 int clipk_gemm_wgrad_f32(const float* dY, int64_t lddy, const float* X, int64_t ldx, float* dW, int64_t lddw,
                          float* dbias, int M, int N, int K, int accumulate, void* stream);
