@@ -8,10 +8,17 @@
 //   * transpose_scale_f32: out[C, R] = s * in[R, C]^T (operands of the exact-f32 products of SimLogitsFn.backward and
 //     of the ICNN's transposed weights).
 // All HBM-bound, f32, coalesced along the fastest dimension; no atomics.
+// A -inf logit (a masked pair) is a term exp(-inf) = 0 of its row and column: it adds nothing to the LSE, and a row or
+// column without any finite logit has lse = -inf (torch.logsumexp's answer).  NaN comes out only where NaN went in.
+// (+inf logits are outside the contract, as they are for torch's softmax.)
+// No problem dimension rides on a grid axis alone: the rows of ce_bwd and the row tiles of transpose_scale sit on
+// grid y (limit 65 535) and are walked with a grid-stride loop, so every int-sized M / rows is accepted.
 #include "common.h"
 #include <math.h>
 
 namespace {
+
+constexpr int GRID_Y_MAX = 65535;                             // HIP's limit of grid y / z
 
 // one wave per row i: lse[i] = logsumexp_j [S | S2][i, j], pos[i] = S[i, i + label_offset]
 __global__ __launch_bounds__(256) void ce_lse_row_kernel(const float* S, long ld, int M, int N, const float* S2, long ld2,
@@ -23,7 +30,7 @@ __global__ __launch_bounds__(256) void ce_lse_row_kernel(const float* S, long ld
   float m = -INFINITY, l = 0.f;
   auto upd = [&](float v) {
     if (v > m) { l = l * __expf(m - v) + 1.f; m = v; }
-    else l += __expf(v - m);
+    else if (v != -INFINITY) l += __expf(v - m);              // -inf under m = -inf would be exp(NaN); its term is 0
   };
   for (int j = lane; j < N; j += 64) upd(r[j]);
   if (S2) {
@@ -57,7 +64,7 @@ __global__ __launch_bounds__(256) void ce_lse_col_kernel(const float* S, long ld
     for (int i = sl_id; i < M; i += 4) {
       const float v = S[(long)i * ld + col];
       if (v > m) { l = l * __expf(m - v) + 1.f; m = v; }
-      else l += __expf(v - m);
+      else if (v != -INFINITY) l += __expf(v - m);            // as in the row kernel
     }
   }
   sm[sl_id][c] = m; sl[sl_id][c] = l;
@@ -84,20 +91,22 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* S, long ld, in
                                                      const float* lse_r, const float* lse_c, float wr, float wc,
                                                      int off_r, int off_c, const float* g, float* dS, long ldd,
                                                      float* dS2, long ldd2) {
-  const int row = blockIdx.y;
   const float gv = g[0];
-  const float lr = lse_r ? lse_r[row] : 0.f;
   const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j < N) {
-    const float v = S[(long)row * ld + j];
-    float d = 0.f;
-    if (lse_r) d += wr * (__expf(v - lr) - ((j == row + off_r) ? 1.f : 0.f));
-    if (lse_c) d += wc * (__expf(v - lse_c[j]) - ((row == j + off_c) ? 1.f : 0.f));
-    dS[(long)row * ldd + j] = gv * d;
-  }
-  if (S2 && dS2 && j < N2) {
-    const float v = S2[(long)row * ld2 + j];
-    dS2[(long)row * ldd2 + j] = lse_r ? gv * wr * __expf(v - lr) : 0.f;
+  const float lc = (lse_c && j < N) ? lse_c[j] : 0.f;
+  for (int row = blockIdx.y; row < M; row += gridDim.y) {    // grid y is capped at 65 535 rows
+    const float lr = lse_r ? lse_r[row] : 0.f;
+    if (j < N) {
+      const float v = S[(long)row * ld + j];
+      float d = 0.f;
+      if (lse_r) d += wr * (__expf(v - lr) - ((j == row + off_r) ? 1.f : 0.f));
+      if (lse_c) d += wc * (__expf(v - lc) - ((row == j + off_c) ? 1.f : 0.f));
+      dS[(long)row * ldd + j] = gv * d;
+    }
+    if (S2 && dS2 && j < N2) {
+      const float v = S2[(long)row * ld2 + j];
+      dS2[(long)row * ldd2 + j] = lse_r ? gv * wr * __expf(v - lr) : 0.f;
+    }
   }
 }
 
@@ -105,18 +114,23 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* S, long ld, in
 __global__ __launch_bounds__(256) void transpose_scale_kernel(const float* in, int R, int C, const float* s, float* out) {
   __shared__ float tile[32][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
-  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+  const int c0 = blockIdx.x * 32;
   const float sv = s ? s[0] : 1.f;
+  for (long r0 = blockIdx.y * 32L; r0 < R; r0 += gridDim.y * 32L) {   // grid y is capped at 65 535 row tiles
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int r = r0 + ty + 8 * k, c = c0 + tx;
-    tile[ty + 8 * k][tx] = (r < R && c < C) ? in[(long)r * C + c] : 0.f;
-  }
-  __syncthreads();
+    for (int k = 0; k < 4; ++k) {
+      const long r = r0 + ty + 8 * k;
+      const int c = c0 + tx;
+      tile[ty + 8 * k][tx] = (r < R && c < C) ? in[r * C + c] : 0.f;
+    }
+    __syncthreads();
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = c0 + ty + 8 * k, r = r0 + tx;
-    if (c < C && r < R) out[(long)c * R + r] = sv * tile[tx][ty + 8 * k];
+    for (int k = 0; k < 4; ++k) {
+      const int c = c0 + ty + 8 * k;
+      const long r = r0 + tx;
+      if (c < C && r < R) out[(long)c * R + r] = sv * tile[tx][ty + 8 * k];
+    }
+    __syncthreads();                                          // the tile is refilled on the next trip
   }
 }
 
@@ -142,16 +156,17 @@ extern "C" int clipk_ce_logits_bwd(const float* S, int64_t ld, int M, int N, con
                                    float* dS, int64_t ldd, float* dS2, int64_t ldd2, void* stream) {
   if (!S || !dS || !gscale || M <= 0 || N <= 0 || N2 < 0 || (N2 > 0 && (!S2 || !dS2))) return CLIPK_ERR_BAD_ARG;
   const int nmax = N > N2 ? N : N2;
-  hipLaunchKernelGGL(ce_bwd_kernel, dim3((nmax + 255) / 256, M), dim3(256), 0, (hipStream_t)stream, S, (long)ld, M, N,
-                     N2 > 0 ? S2 : nullptr, (long)ld2, N2, lse_row, lse_col, w_row, w_col, label_offset_row,
-                     label_offset_col, gscale, dS, (long)ldd, N2 > 0 ? dS2 : nullptr, (long)ldd2);
+  hipLaunchKernelGGL(ce_bwd_kernel, dim3((nmax + 255) / 256, M < GRID_Y_MAX ? M : GRID_Y_MAX), dim3(256), 0,
+                     (hipStream_t)stream, S, (long)ld, M, N, N2 > 0 ? S2 : nullptr, (long)ld2, N2, lse_row, lse_col, w_row,
+                     w_col, label_offset_row, label_offset_col, gscale, dS, (long)ldd, N2 > 0 ? dS2 : nullptr, (long)ldd2);
   return clipk_check_launch();
 }
 
 extern "C" int clipk_transpose_scale_f32(const float* in, int rows, int cols, const float* scale_dev, float* out,
                                          void* stream) {
   if (!in || !out || rows <= 0 || cols <= 0) return CLIPK_ERR_BAD_ARG;
-  hipLaunchKernelGGL(transpose_scale_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0, (hipStream_t)stream,
-                     in, rows, cols, scale_dev, out);
+  const int ty = (rows + 31) / 32;
+  hipLaunchKernelGGL(transpose_scale_kernel, dim3((cols + 31) / 32, ty < GRID_Y_MAX ? ty : GRID_Y_MAX), dim3(256), 0,
+                     (hipStream_t)stream, in, rows, cols, scale_dev, out);
   return clipk_check_launch();
 }

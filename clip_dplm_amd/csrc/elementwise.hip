@@ -347,62 +347,66 @@ __global__ __launch_bounds__(256) void embed_bwd_reduce_kernel(const float* part
 // (b, 64 columns) walks the L positions with 8 independent loads in flight (256-thread blocks with a plain serial
 // loop ran at 1.6 TB/s: 2 blocks per sequence, one load in flight per thread).
 __global__ void pool_fwd_kernel(const float* x, const uint8_t* mask, float* y, int B, int L, int d, int mode) {
-  const int b = blockIdx.y;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= d) return;
-  const float* xb = x + ((long)b * L) * d + c;
-  if (mode == 0) { y[(long)b * d + c] = xb[0]; return; }
-  const uint8_t* mb = mask ? mask + (long)b * L : nullptr;
-  float s = 0.f; int n = 0;
-  int l = 0;
-  for (; l + 8 <= L; l += 8) {
-    float v[8];
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {          // grid y is capped at 65 535 sequences
+    const float* xb = x + ((long)b * L) * d + c;
+    if (mode == 0) { y[(long)b * d + c] = xb[0]; continue; }
+    const uint8_t* mb = mask ? mask + (long)b * L : nullptr;
+    float s = 0.f; int n = 0;
+    int l = 0;
+    for (; l + 8 <= L; l += 8) {
+      float v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = xb[(long)(l + u) * d];
+      for (int u = 0; u < 8; ++u) v[u] = xb[(long)(l + u) * d];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const bool ok = mb ? mb[l + u] != 0 : true;
-      if (ok) { s += v[u]; ++n; }
+      for (int u = 0; u < 8; ++u) {
+        const bool ok = mb ? mb[l + u] != 0 : true;
+        if (ok) { s += v[u]; ++n; }
+      }
     }
+    for (; l < L; ++l) {
+      const bool ok = mb ? mb[l] != 0 : true;
+      if (ok) { s += xb[(long)l * d]; ++n; }
+    }
+    y[(long)b * d + c] = n > 0 ? s / (float)n : 0.f;
   }
-  for (; l < L; ++l) {
-    const bool ok = mb ? mb[l] != 0 : true;
-    if (ok) { s += xb[(long)l * d]; ++n; }
-  }
-  y[(long)b * d + c] = n > 0 ? s / (float)n : 0.f;
 }
 // packed variable-length batches: sequence b = rows [cu[b], cu[b+1]); mode 0 = its first row, 1 = mean over its rows
-__global__ void pool_varlen_fwd_kernel(const float* x, const int* cu, float* y, int d, int mode) {
-  const int b = blockIdx.y;
+// (grid y = sequences, capped at 65 535 and strided like pool_fwd_kernel's, in the forward and in the backward)
+__global__ void pool_varlen_fwd_kernel(const float* x, const int* cu, float* y, int B, int d, int mode) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= d) return;
-  const int r0 = cu[b], n = cu[b + 1] - r0;
-  const float* xb = x + (long)r0 * d + c;
-  if (mode == 0 || n <= 0) { y[(long)b * d + c] = n > 0 ? xb[0] : 0.f; return; }
-  float s = 0.f;
-  int l = 0;
-  for (; l + 8 <= n; l += 8) {
-    float v[8];
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int r0 = cu[b], n = cu[b + 1] - r0;
+    const float* xb = x + (long)r0 * d + c;
+    if (mode == 0 || n <= 0) { y[(long)b * d + c] = n > 0 ? xb[0] : 0.f; continue; }
+    float s = 0.f;
+    int l = 0;
+    for (; l + 8 <= n; l += 8) {
+      float v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = xb[(long)(l + u) * d];
+      for (int u = 0; u < 8; ++u) v[u] = xb[(long)(l + u) * d];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
+      for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; l < n; ++l) s += xb[(long)l * d];
+    y[(long)b * d + c] = s / (float)n;
   }
-  for (; l < n; ++l) s += xb[(long)l * d];
-  y[(long)b * d + c] = s / (float)n;
 }
 // one block row per sequence: dx[rows of b] = dy[b] / n (mode 1) or dy[b] on the first row only (mode 0)
-__global__ void pool_varlen_bwd_kernel(const float* dy, const int* cu, float* dx, int d, int mode) {
-  const int b = blockIdx.y;
-  const int r0 = cu[b], n = cu[b + 1] - r0;
+__global__ void pool_varlen_bwd_kernel(const float* dy, const int* cu, float* dx, int B, int d, int mode) {
   const int nch = d >> 2;
-  const long total = (long)n * nch;
-  const float inv = (mode == 1 && n > 0) ? 1.0f / (float)n : 1.0f;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int l = (int)(i / nch), c = (int)(i - (long)l * nch);
-    const float sc = (mode == 0) ? (l == 0 ? 1.f : 0.f) : inv;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(dy + (long)b * d + 4 * c);
-    *reinterpret_cast<f32x4*>(dx + ((long)r0 + l) * d + 4 * c) = v * sc;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int r0 = cu[b], n = cu[b + 1] - r0;
+    const long total = (long)n * nch;
+    const float inv = (mode == 1 && n > 0) ? 1.0f / (float)n : 1.0f;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+      const int l = (int)(i / nch), c = (int)(i - (long)l * nch);
+      const float sc = (mode == 0) ? (l == 0 ? 1.f : 0.f) : inv;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(dy + (long)b * d + 4 * c);
+      *reinterpret_cast<f32x4*>(dx + ((long)r0 + l) * d + 4 * c) = v * sc;
+    }
   }
 }
 __global__ void pool_bwd_kernel(const float* dy, const uint8_t* mask, float* dx, int B, int L, int d, int mode) {
@@ -498,6 +502,7 @@ extern "C" int clipk_cast_transpose(const float* w, void* w_bf16, void* wt_bf16,
                                     void* stream) {
   if (!w || rows <= 0 || cols <= 0 || (!w_bf16 && !wt_bf16)) return CLIPK_ERR_BAD_ARG;
   if (il_rows < 0 || il_rows > rows || (il_rows > 0 && (il_hd < 2 || (il_hd & 1) || il_rows % il_hd))) return CLIPK_ERR_BAD_ARG;
+  if ((rows + 63) / 64 > 65535) return CLIPK_ERR_UNSUPPORTED;   // row tiles sit on grid y; the batched entry strides over them
   hipLaunchKernelGGL(cast_transpose_kernel, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(256), 0, (hipStream_t)stream,
                      w, (unsigned short*)w_bf16, (unsigned short*)wt_bf16, rows, cols, il_rows ? il_hd : 2, il_rows);
   return clipk_check_launch();
@@ -600,7 +605,8 @@ extern "C" int clipk_embed_bwd(const int64_t* ids, const float* dx, const float*
 }
 extern "C" int clipk_pool_fwd(const float* x, const uint8_t* mask, float* y, int B, int L, int d, int mode, void* stream) {
   if (!x || !y || B <= 0 || L <= 0 || d <= 0) return CLIPK_ERR_BAD_ARG;
-  hipLaunchKernelGGL(pool_fwd_kernel, dim3((d + 63) / 64, B), dim3(64), 0, (hipStream_t)stream, x, mask, y, B, L, d, mode);
+  hipLaunchKernelGGL(pool_fwd_kernel, dim3((d + 63) / 64, B < 65535 ? B : 65535), dim3(64), 0, (hipStream_t)stream, x, mask,
+                     y, B, L, d, mode);
   return clipk_check_launch();
 }
 extern "C" int clipk_pool_bwd(const float* dy, const uint8_t* mask, float* dx, int B, int L, int d, int mode, void* stream) {
@@ -613,12 +619,15 @@ extern "C" int clipk_pool_bwd(const float* dy, const uint8_t* mask, float* dx, i
 
 extern "C" int clipk_pool_varlen_fwd(const float* x, const int* cu_seqlens, float* y, int B, int d, int mode, void* stream) {
   if (!x || !cu_seqlens || !y || B <= 0 || d <= 0) return CLIPK_ERR_BAD_ARG;
-  hipLaunchKernelGGL(pool_varlen_fwd_kernel, dim3((d + 63) / 64, B), dim3(64), 0, (hipStream_t)stream, x, cu_seqlens, y, d, mode);
+  hipLaunchKernelGGL(pool_varlen_fwd_kernel, dim3((d + 63) / 64, B < 65535 ? B : 65535), dim3(64), 0, (hipStream_t)stream, x,
+                     cu_seqlens, y, B, d, mode);
   return clipk_check_launch();
 }
 extern "C" int clipk_pool_varlen_bwd(const float* dy, const int* cu_seqlens, float* dx, int B, int d, int mode, void* stream) {
-  if (!dy || !cu_seqlens || !dx || B <= 0 || d <= 0 || (d & 3)) return CLIPK_ERR_BAD_ARG;
-  hipLaunchKernelGGL(pool_varlen_bwd_kernel, dim3(8, B), dim3(256), 0, (hipStream_t)stream, dy, cu_seqlens, dx, d, mode);
+  if (!dy || !cu_seqlens || !dx || B <= 0 || d <= 0) return CLIPK_ERR_BAD_ARG;
+  if (d & 3) return CLIPK_ERR_UNSUPPORTED;                    // float4 rows, as clipk_pool_bwd
+  hipLaunchKernelGGL(pool_varlen_bwd_kernel, dim3(8, B < 65535 ? B : 65535), dim3(256), 0, (hipStream_t)stream, dy, cu_seqlens,
+                     dx, B, d, mode);
   return clipk_check_launch();
 }
 

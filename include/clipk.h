@@ -458,7 +458,12 @@ int clipk_sim_rerank(const float* X, int Mx, const float* Y, int Ny, int P, floa
  *   bwd:  dS[i,j]  = g * ( w_row (exp(S_ij - lse_row[i]) - [j == i + off_row])
  *                        + w_col (exp(S_ij - lse_col[j]) - [i == j + off_col]) ),
  *         dS2[i,j] = g * w_row exp(S2_ij - lse_row[i]);   lse_row / lse_col may be NULL (direction unused);
- *         w_row / w_col carry the 1 / batch factors; g = device scalar (upstream gradient). */
+ *         w_row / w_col carry the 1 / batch factors; g = device scalar (upstream gradient).
+ * A label outside the matrix gives pos = 0 and no one-hot.  A -inf logit is a zero term: it adds nothing to lse, a row
+ * or column without a finite logit has lse = -inf (torch.logsumexp), and no NaN comes out unless one went in (the
+ * backward of an all--inf row is exp(-inf + inf): leave such rows out).  ld / ld2 / ldd / ldd2 are row strides in
+ * elements.  columns == 1 with N2 > 0 is CLIPK_ERR_UNSUPPORTED.  Every M, N, N2 that fits an int is accepted by both
+ * entry points: the backward walks its rows with a grid-stride loop over at most 65 535 grid rows. */
 int clipk_ce_logits_lse(const float* S, int64_t ld, int M, int N, const float* S2, int64_t ld2, int N2,
                         int columns, int label_offset, float* lse, float* pos, void* stream);
 int clipk_ce_logits_bwd(const float* S, int64_t ld, int M, int N, const float* S2, int64_t ld2, int N2,
@@ -542,7 +547,8 @@ int clipk_linear_ce_tiled_bwd(const float* X1, int K1, const float* X2, int K2, 
 
 /* out[cols, rows] = scale_dev[0] * in[rows, cols]^T (f32; scale_dev NULL = 1).  Operand preparation of the exact-f32
  * products that differentiate the materialised logits (d/dA = scale * dS · B, d/dB = scale * dS^T · A of
- * old/clip.py:67) and of the ICNN's transposed weights (triple_flow/2_icnn_core.py:181-211). */
+ * old/clip.py:67) and of the ICNN's transposed weights (triple_flow/2_icnn_core.py:181-211).  One f32 rounding per
+ * element (a copy without a scale); any rows / cols: the row tiles beyond grid y's 65 535 are walked by a loop. */
 int clipk_transpose_scale_f32(const float* in, int rows, int cols, const float* scale_dev, float* out, void* stream);
 
 /* Exact-f32 Linear for the ICNN transport maps (the reference forces f32 there: triple_flow/2_icnn_core.py:195):
@@ -658,7 +664,9 @@ int clipk_cast_bf16_to_f32(const void* x, float* y, int64_t n, void* stream);
 /* W f32 [rows,cols] -> bf16 copy and bf16 transposed copy [cols,rows] (either may be NULL).
  * il_rows > 0: rows [0, il_rows) of both copies are written in PAIR-INTERLEAVED head order for heads of il_hd rows - copy
  * row 2 j (+1) of a head holds W row j (+ il_hd / 2) of that head - the order in which clipk_gemm_nt's interleaved RoPE
- * epilogue (rope_interleaved) expects the q and k sections of ESM-2's fused qkv projection (modeling_esm.py:362-374). */
+ * epilogue (rope_interleaved) expects the q and k sections of ESM-2's fused qkv projection (modeling_esm.py:362-374).
+ * rows <= 64 * 65 535 (one 64-row tile per grid row), else CLIPK_ERR_UNSUPPORTED before any launch; the batched entry
+ * below has no such limit. */
 int clipk_cast_transpose(const float* w, void* w_bf16, void* wt_bf16, int rows, int cols, int il_hd, int il_rows, void* stream);
 /* The same for n weights in one launch (what `optimizer.step()` leaves to do before the next forward: the reference
  * re-reads its f32 nn.Linear weights under autocast every step, old/clip.py:11).  desc_dev: device array of n
@@ -753,12 +761,15 @@ int clipk_embed_bwd(const int64_t* ids, const float* dx, const float* row_scale,
                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* Pooling over the sequence: mode 0 = position 0 (rna_clip_codes.ipynb:1948), 1 = masked mean
- * (configuration_hybrid_clip.py:109 use_mean_pooling).  x f32 [B,L,d] -> y f32 [B,d]. */
+ * (configuration_hybrid_clip.py:109 use_mean_pooling).  x f32 [B,L,d] -> y f32 [B,d].  Any B (sequences beyond grid
+ * y's 65 535 are walked by a loop).  The backwards write float4 rows: d % 4 != 0 is CLIPK_ERR_UNSUPPORTED, in
+ * clipk_pool_bwd and in clipk_pool_varlen_bwd alike, before anything is launched. */
 int clipk_pool_fwd(const float* x, const uint8_t* mask, float* y, int B, int L, int d, int mode, void* stream);
 int clipk_pool_bwd(const float* dy, const uint8_t* mask, float* dx, int B, int L, int d, int mode, void* stream);
 
 /* Pooling over packed variable-length batches (sequence b = rows [cu[b], cu[b+1]) of x f32 [T, d]): mode 0 = the first
- * row, 1 = mean over the sequence's rows; backward writes every row of dx [T, d].  cu_seqlens: DEVICE int32 [B+1]. */
+ * row, 1 = mean over the sequence's rows; an empty sequence (cu[b] == cu[b+1]) gives y[b] = 0 and owns no dx row.  The
+ * backward writes rows [cu[0], cu[B]) of dx [T, d] and no other.  cu_seqlens: DEVICE int32 [B+1].  Any B. */
 int clipk_pool_varlen_fwd(const float* x, const int* cu_seqlens, float* y, int B, int d, int mode, void* stream);
 int clipk_pool_varlen_bwd(const float* dy, const int* cu_seqlens, float* dx, int B, int d, int mode, void* stream);
 

@@ -250,23 +250,35 @@ def transpose_scale_f32(x, scale=None):
     return (x.t() * (scale if scale is not None else 1.0)).contiguous()
 
 
+def _ce_label_mask(M, N, off, columns):
+    """The kernels' one-hot: rows [j == i + off], columns [i == j + off]; a label outside the matrix marks nothing."""
+    i, j = torch.arange(M)[:, None], torch.arange(N)[None, :]
+    return (i == j + off) if columns else (j == i + off)
+
+
 def ce_logits_lse(S, S2=None, columns=False, label_offset=0):
+    """include/clipk.h clipk_ce_logits_lse: pos has one entry per row (column), 0 where its label is outside S; -inf logits
+    are zero terms (torch.logsumexp: -inf for a row / column without a finite one)."""
+    if columns and S2 is not None and S2.shape[1] > 0:
+        raise ValueError("cache columns exist in the row direction only")
+    hot = _ce_label_mask(S.shape[0], S.shape[1], label_offset, columns)
+    picked = torch.where(hot, S, torch.zeros_like(S))                  # at most one label per row / column: the sum is a copy
     if columns:
-        return torch.logsumexp(S, 0), torch.diagonal(S, -label_offset).clone()
-    full = S if S2 is None else torch.cat([S, S2], 1)
-    return torch.logsumexp(full, 1), torch.diagonal(S, label_offset).clone()
+        return torch.logsumexp(S, 0), picked.sum(0)
+    full = S if S2 is None or S2.shape[1] == 0 else torch.cat([S, S2], 1)
+    return torch.logsumexp(full, 1), picked.sum(1)
 
 
 def ce_logits_bwd(S, S2, lse_row, lse_col, w_row, w_col, g, off_row=0, off_col=0):
-    eye = torch.eye(S.shape[0], S.shape[1], dtype=S.dtype)
+    M, N = S.shape
     d = torch.zeros_like(S)
     d2 = None
+    if S2 is not None and S2.shape[1] > 0:
+        d2 = g * w_row * torch.exp(S2 - lse_row[:, None]) if lse_row is not None else torch.zeros_like(S2)
     if lse_row is not None:
-        d = d + w_row * (torch.exp(S - lse_row[:, None]) - eye)
-        if S2 is not None:
-            d2 = g * w_row * torch.exp(S2 - lse_row[:, None])
+        d = d + w_row * (torch.exp(S - lse_row[:, None]) - _ce_label_mask(M, N, off_row, False).to(S.dtype))
     if lse_col is not None:
-        d = d + w_col * (torch.exp(S - lse_col[None, :]) - eye)
+        d = d + w_col * (torch.exp(S - lse_col[None, :]) - _ce_label_mask(M, N, off_col, True).to(S.dtype))
     return g * d, d2
 
 
