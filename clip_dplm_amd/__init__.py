@@ -42,7 +42,10 @@ from . import cluster
 from .manifold import TSNEResult, embed_spaces, knn_preservation, perplexity_bandwidths, tsne
 from . import manifold
 from .mixing import LabelMasses, integration_scores, label_masses, label_transfer, label_transfer_accuracy, lisi
+from .mixing import KBETResult, kbet, lisi_knn
 from . import mixing
+from .neighbors import KNNGraph, knn_graph
+from . import neighbors
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -67,4 +70,5 @@ __all__ = [
     "calinski_harabasz_score", "label_separation", "choose_n_clusters",
     "manifold", "tsne", "TSNEResult", "perplexity_bandwidths", "embed_spaces", "knn_preservation",
     "mixing", "lisi", "label_masses", "LabelMasses", "label_transfer", "label_transfer_accuracy", "integration_scores",
+    "kbet", "KBETResult", "lisi_knn", "neighbors", "knn_graph", "KNNGraph",
 ]

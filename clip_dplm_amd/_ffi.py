@@ -86,6 +86,9 @@ SIGNATURES = {
     "clipk_sim_logits": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i64, _vp]),
     "clipk_sim_topk_workspace": (_sz, [_i, _i, _i, _i]),
     "clipk_sim_topk": (_i, [_vp, _i, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_sim_knn_workspace": (_sz, [_i, _i, _i, _i]),
+    "clipk_sim_knn": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipk_pair_sqdist": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "clipk_sim_rank_workspace": (_sz, [_i, _i, _i]),
     "clipk_sim_rank": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "clipk_sim_rank_cls": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1,7 +1,9 @@
 // retrieval.hip — cross-modal retrieval over an embedding gallery without materialising the logits:
 //   clipk_sim_topk : the k best keys of every query,  S[i,j] = scale <X_i, Y_j>
 //   clipk_sim_rank : the 0-based rank of every query's labelled positive, and its score
-// Both walk the tiled exact-f32 similarity block of the fused softmax statistics (sim_tile.h: 64 queries per workgroup,
+//   clipk_sim_knn  : clipk_sim_topk with a key-side bias, one skipped key per row and a resume cursor (the KNN
+//                    instantiation of sim_topk_kernel; every addition sits under `if constexpr`)
+// All walk the tiled exact-f32 similarity block of the fused softmax statistics (sim_tile.h: 64 queries per workgroup,
 // 64-key tiles, keys on the MFMA rows, queries on the lanes, key-range splits on grid y) and replace its epilogue.
 //
 // Ordering contract: score descending, equal scores (IEEE: -0 == +0) by the lower key index.  It is a total order, so the
@@ -67,9 +69,16 @@ struct TKP {
   int P; float scale;
   float* part_s; int* part_i;            // [4 ksplit][Mx][KP]
   int tiles_per_split, ntiles;
+  // KNN instantiation only
+  const float* bias;                     // [Ny] or null
+  long long diag_offset;                 // row i skips key i + diag_offset; -1: no key skipped
+  const float* after_s; const int64_t* after_i;   // [Mx] cursor in the total order, or null
 };
 
-template <int KP>
+// KNN: z = fl(fl(scale s) + bias[key]) replaces the score and a key that is the row's own (key == q + diag_offset), at or
+// before the cursor (after_s, after_i)[q] in the total order, or past Ny counts as -inf: it then fails the tile-maximum
+// test and the insertion test like any weak key, so the common path stays one max and one compare per tile.
+template <int KP, bool KNN>
 __global__ __launch_bounds__(256, 2) void sim_topk_kernel(const TKP p) {
   __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * (RBK + 4)];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -86,18 +95,56 @@ __global__ __launch_bounds__(256, 2) void sim_topk_kernel(const TKP p) {
   for (int t = 0; t < KP; ++t) { s[t] = -INFINITY; ix[t] = EMPTY; }
   const int t_beg = ks * p.tiles_per_split;
   int t_end = t_beg + p.tiles_per_split; t_end = t_end < p.ntiles ? t_end : p.ntiles;
+  float cur_s = INFINITY;                                                 // KNN: the cursor and the skipped key of this
+  int cur_i = -1, skip = -1;                                              // lane's query (no cursor: every z < +inf)
+  // KNN: bias[j0 .. j0 + 64) of the tile goes through LDS, loaded one tile ahead by threads 0..63 so that the load is
+  // in flight under the K-loop at the price of one register.  Double-buffered: a buffer is rewritten two tiles after it
+  // was read, and s_tile's unconditional barriers lie between (and between a tile's write and its read).
+  __shared__ __attribute__((aligned(16))) float bl[KNN ? 2 : 1][KNN ? RK : 4];
+  const bool biased = KNN && p.bias != nullptr;
+  float bnext = 0.f;
+  if constexpr (KNN) {
+    if (biased && tid < RK) { const int key = t_beg * RK + tid; bnext = p.bias[key < Ny ? key : Ny - 1]; }
+    const int q = q0 + wn * 32 + li, qc = q < p.Mx ? q : p.Mx - 1;
+    if (p.after_s) cur_s = p.after_s[qc];
+    if (p.after_i) { const int64_t a = p.after_i[qc]; cur_i = a < 0 ? -1 : a > INT_MAX ? INT_MAX : (int)a; }
+    const long long d = p.diag_offset < 0 ? -1 : (long long)q + p.diag_offset;
+    skip = d < Ny ? (int)d : -1;
+  }
 
   for (int kt = t_beg; kt < t_end; ++kt) {
     const int j0 = kt * RK;
     const float* yrows[RBK / 16];
     key_rows(yrows, p.Y, Ny, P, j0, tid);
+    const int kb = j0 + wm * 32 + 4 * h;                                  // key of accumulator row r: kb + key_off(r)
+    if constexpr (KNN) {                                                  // this tile's biases to LDS, the next tile's in flight
+      if (biased && tid < RK) {
+        bl[kt & 1][tid] = bnext;
+        const int key = j0 + RK + tid;
+        bnext = p.bias[key < Ny ? key : Ny - 1];
+      }
+    }
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     s_tile<RBK>(acc, yrows, xrows, smem, P, tid, wm, wn, li, h);
-    const int kb = j0 + wm * 32 + 4 * h;                                  // key of accumulator row r: kb + key_off(r)
     float tmax = -INFINITY;
-    if (j0 + RK <= Ny) {
+    if constexpr (KNN) {                                                  // acc <- z, or -inf where not eligible
+      f32x4 bz[4];                                                        // bias of row r: bz[r >> 2][r & 3]
+      if (biased) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) bz[g] = *reinterpret_cast<const f32x4*>(&bl[kt & 1][wm * 32 + 4 * h + 8 * g]);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = kb + key_off(r);
+        float z = __fmul_rn(scale, acc[r]);
+        if (biased) z = __fadd_rn(z, bz[r >> 2][r & 3]);
+        const bool ok = (key < Ny) & (key != skip) & ((z < cur_s) | ((z == cur_s) & (key > cur_i)));
+        acc[r] = ok ? z : -INFINITY;
+        tmax = fmaxf(tmax, acc[r]);
+      }
+    } else if (j0 + RK <= Ny) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, scale * acc[r]);
     } else {
@@ -108,14 +155,14 @@ __global__ __launch_bounds__(256, 2) void sim_topk_kernel(const TKP p) {
       unsigned m = 0;
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (kb + key_off(r) < Ny && scale * acc[r] > s[KP - 1]) m |= 1u << r;
+        if (kb + key_off(r) < Ny && (KNN ? acc[r] : scale * acc[r]) > s[KP - 1]) m |= 1u << r;
       while (m) {                                                         // ascending r = ascending key
         const int r = __builtin_ctz(m);
         m &= m - 1;
         float a = acc[0];
 #pragma unroll
         for (int rr = 1; rr < 16; ++rr) a = (r == rr) ? acc[rr] : a;     // no dynamic register indexing
-        const float v = scale * a;
+        const float v = KNN ? a : scale * a;
         if (v > s[KP - 1]) list_insert<KP>(s, ix, v, kb + key_off(r));
       }
     }
@@ -172,7 +219,8 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* in_s, cons
       else { const long o = ((long)g * Mx + q) * KP + rank; out_s[o] = v; out_i[o] = j; }
     }
   }
-  for (int t = R + tid; t < kout; t += 256) {                             // fewer than k real keys: NaN inputs only
+  for (int t = R + tid; t < kout; t += 256) {                             // fewer than k real keys: NaN inputs, or
+                                                                          // clipk_sim_knn (Ny = 0 here: index -1)
     if (fin_s) { fin_s[(long)q * k + t] = -INFINITY; fin_i[(long)q * k + t] = t < Ny ? t : Ny - 1; }
     else { const long o = ((long)g * Mx + q) * KP + t; out_s[o] = -INFINITY; out_i[o] = EMPTY; }
   }
@@ -317,13 +365,18 @@ void plan(int Mx, int Ny, int qb, int* nqb, int* ksplit, int* tps, int* ntiles) 
 
 int kpad(int k) { return k <= 1 ? 1 : k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64; }
 
+// clipk_sim_knn leaves the 32-slot instance out: beyond 16 results the 64-slot one is the faster at every large shape
+// measured (clipk_sim_topk shows the same inversion and keeps its instances)
+int kpad_knn(int k) { return k <= 16 ? kpad(k) : 64; }
+
 bool shape_ok(int Mx, int Ny, int P) { return Mx > 0 && Ny > 0 && P > 0 && Ny <= INT_MAX - RK; }
 
-template <int KP>
+// KNN: p carries bias / diag_offset / after_*, and the unfilled result slots get index -1 (fill_Ny = 0)
+template <int KP, bool KNN = false>
 int topk_launch(const float* X, int Mx, const float* Y, int Ny, int P, float scale, int k, float* scores, int64_t* idx,
-                char* ws, hipStream_t st) {
-  TKP p;
+                char* ws, hipStream_t st, TKP p = TKP{}) {
   p.X = X; p.Mx = Mx; p.Y = Y; p.Ny = Ny; p.P = P; p.scale = scale;
+  const int fill_Ny = KNN ? 0 : Ny;
   int nqb, ksplit;
   plan(Mx, Ny, RQ, &nqb, &ksplit, &p.tiles_per_split, &p.ntiles);
   const int la = 4 * ksplit, lb = (la + MG - 1) / MG;
@@ -333,7 +386,7 @@ int topk_launch(const float* X, int Mx, const float* Y, int Ny, int P, float sca
   float* b_s = reinterpret_cast<float*>(a_i + la * per_list);
   int* b_i = reinterpret_cast<int*>(b_s + lb * per_list);
   p.part_s = a_s; p.part_i = a_i;
-  hipLaunchKernelGGL(sim_topk_kernel<KP>, dim3(nqb, ksplit), dim3(256), 0, st, p);
+  hipLaunchKernelGGL((sim_topk_kernel<KP, KNN>), dim3(nqb, ksplit), dim3(256), 0, st, p);
   int rc = clipk_check_launch();
   if (rc) return rc;
   const float* src_s = a_s; const int* src_i = a_i;
@@ -342,11 +395,11 @@ int topk_launch(const float* X, int Mx, const float* Y, int Ny, int P, float sca
     const int groups = (L + MG - 1) / MG;
     if (groups == 1) {
       hipLaunchKernelGGL(topk_merge_kernel<KP>, dim3(Mx, 1), dim3(256), 0, st, src_s, src_i, L, Mx,
-                         (float*)nullptr, (int*)nullptr, scores, idx, k, Ny);
+                         (float*)nullptr, (int*)nullptr, scores, idx, k, fill_Ny);
       return clipk_check_launch();
     }
     hipLaunchKernelGGL(topk_merge_kernel<KP>, dim3(Mx, groups), dim3(256), 0, st, src_s, src_i, L, Mx, dst_s, dst_i,
-                       (float*)nullptr, (int64_t*)nullptr, k, Ny);
+                       (float*)nullptr, (int64_t*)nullptr, k, fill_Ny);
     if ((rc = clipk_check_launch())) return rc;
     L = groups;
     float* ts = const_cast<float*>(src_s); int* ti = const_cast<int*>(src_i);  // ping-pong: A holds >= every later L
@@ -379,6 +432,35 @@ extern "C" int clipk_sim_topk(const float* X, int Mx, const float* Y, int Ny, in
     case 16: return topk_launch<16>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st);
     case 32: return topk_launch<32>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st);
     default: return topk_launch<64>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st);
+  }
+}
+
+extern "C" size_t clipk_sim_knn_workspace(int Mx, int Ny, int P, int k) {
+  if (!shape_ok(Mx, Ny, P) || P % 4 || k < 1 || k > 64) return 0;
+  int nqb, ksplit, tps, nt;
+  plan(Mx, Ny, RQ, &nqb, &ksplit, &tps, &nt);
+  const size_t la = 4 * (size_t)ksplit, lb = (la + MG - 1) / MG;
+  return (la + lb) * (size_t)Mx * kpad_knn(k) * (sizeof(float) + sizeof(int));
+}
+
+extern "C" int clipk_sim_knn(const float* X, int Mx, const float* Y, int Ny, int P, float scale, const float* bias,
+                             long long diag_offset, const float* after_s, const int64_t* after_i, int k, float* scores,
+                             int64_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!X || !Y || !scores || !idx || !workspace) return CLIPK_ERR_BAD_ARG;
+  if (Mx <= 0 || Ny <= 0 || P <= 0 || k <= 0 || diag_offset < -1) return CLIPK_ERR_BAD_ARG;
+  if ((after_s == nullptr) != (after_i == nullptr)) return CLIPK_ERR_BAD_ARG;
+  if (k > 64 || P % 4 || !shape_ok(Mx, Ny, P)) return CLIPK_ERR_UNSUPPORTED;
+  if (!aligned16(X) || !aligned16(Y)) return CLIPK_ERR_BAD_ARG;
+  if (workspace_bytes < clipk_sim_knn_workspace(Mx, Ny, P, k)) return CLIPK_ERR_BAD_ARG;
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  TKP p{};
+  p.bias = bias; p.diag_offset = diag_offset; p.after_s = after_s; p.after_i = after_i;
+  switch (kpad_knn(k)) {
+    case 1: return topk_launch<1, true>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st, p);
+    case 8: return topk_launch<8, true>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st, p);
+    case 16: return topk_launch<16, true>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st, p);
+    default: return topk_launch<64, true>(X, Mx, Y, Ny, P, scale, k, scores, idx, ws, st, p);
   }
 }
 

@@ -14,7 +14,8 @@ SQUARED distances (manifold.perplexity_bandwidths: beta_i, dmin_i),
 
 Every pair enters.  The published implementation truncates each neighbourhood to the 3 x perplexity nearest neighbours
 and puts UNSQUARED distances in the exponent; neither is done here, so values differ from that package's (tests/lisi_ref.py
-has the truncated variant; DESIGN.md 3.20 records how far truncation moves the median).
+has the truncated variant; DESIGN.md 3.20 records how far truncation moves the median).  lisi_knn below IS the published
+definition, on the exact k-nearest-neighbour graph of neighbors.knn_graph, for comparison against published tables.
 
     label_masses            the per-point label masses' statistics from one walk per 512 labels (ops.label_kernel_sums):
                             mass, sum of squares, the heaviest label and its share; the [N, G] shares only when asked for.
@@ -23,21 +24,26 @@ has the truncated variant; DESIGN.md 3.20 records how far truncation moves the m
     integration_scores      iLISI over the concatenated clouds with the cloud index as label; with annotations also cLISI
                             and the label-transfer accuracy, on the same bandwidths.
 
+    kbet                    the k-nearest-neighbour batch-effect test (Buettner et al. 2019): per row a chi-square test of its
+                            neighbours' batch counts against the global shares; the rejection rate.
+    lisi_knn                the published LISI: 3 x perplexity nearest neighbours, unsquared distances, its own bisection.
+
 The walk has no CPU fallback; the small reductions (median_score, scale_ilisi, scale_clisi, merge_label_blocks) are torch
 glue that also takes host tensors.
 """
 from __future__ import annotations
 
 import dataclasses
+import math
 from typing import Optional
 
 import torch
 
-from . import manifold, ops
+from . import manifold, neighbors, ops
 from .cluster import _labels_arg
 
 __all__ = ["LabelMasses", "label_masses", "lisi", "label_transfer", "label_transfer_accuracy", "integration_scores",
-           "median_score", "scale_ilisi", "scale_clisi", "merge_label_blocks"]
+           "median_score", "scale_ilisi", "scale_clisi", "merge_label_blocks", "KBETResult", "kbet", "lisi_knn"]
 
 MAX_LABELS = ops.LABEL_DIST_MAX_LABELS              # in blocks of ops.LABEL_DIST_MAX_G, one walk each
 BLOCK_BYTES = 256 << 20                             # the [rows, G] slab of one row block (default row_block)
@@ -261,3 +267,193 @@ def integration_scores(clouds, labels=None, perplexity: float = 30.0, metric: st
         out["clisi"], out["clisi_scaled"] = med, scale_clisi(med, m.num_labels)
         out["label_transfer_accuracy"] = float((m.predicted == labels.to(x.device)).double().mean())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ scores on the kNN graph
+@dataclasses.dataclass
+class KBETResult:
+    """stat, pvalue f64 [N]: each row's chi-square statistic and its upper-tail probability; rejection_rate, acceptance:
+    0-d f64 tensors, mean(pvalue < alpha) and 1 - that; expected_rejection_rate: the same under one random permutation of
+    the labels on the same graph (None without a generator); k: the neighbours used; dof: 0-d int64 tensor, the non-empty
+    labels - 1."""
+    stat: torch.Tensor
+    pvalue: torch.Tensor
+    rejection_rate: torch.Tensor
+    acceptance: torch.Tensor
+    expected_rejection_rate: Optional[torch.Tensor]
+    k: int
+    dof: torch.Tensor
+
+
+def _graph_labels(name, labels, num_labels, N):
+    """The labels as positions 0..G-1 (int64 [N]) and G; every argument error first."""
+    labels = _labels_arg(name, labels)
+    if labels.shape[0] != N:
+        raise ValueError(f"{name} has {labels.shape[0]} entries for {N} rows")
+    if num_labels is not None:
+        if isinstance(num_labels, bool) or not isinstance(num_labels, int) or num_labels < 1:
+            raise ValueError(f"num_labels must be None or a positive int, got {num_labels!r}")
+    return labels
+
+
+def _relabel(labels, num_labels):
+    if num_labels is not None:
+        return labels, num_labels
+    values, inv = torch.unique(labels, return_inverse=True)
+    return inv, values.shape[0]
+
+
+def _check_k(k, N):
+    kmax = min(neighbors.MAX_K, N - 1)
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= kmax):
+        raise ValueError(f"k must be None or an int in [1, min(1024, N - 1)] = [1, {kmax}], got {k!r}")
+
+
+def _graph_arg(x, graph, k, N):
+    """The graph's first k columns (all of them for k None); builds the graph when none is given."""
+    if graph is None:
+        return neighbors.knn_graph(x, k)
+    if k is not None and k > graph.k:
+        raise ValueError(f"k = {k} exceeds the graph's {graph.k} neighbours")
+    if k is None or k == graph.k:
+        return graph
+    return neighbors.KNNGraph(graph.indices[:, :k], graph.sqdist[:, :k])
+
+
+def _kbet_stat(graph, lab, G, k):
+    """(stat f64 [N], dof): sum over the non-empty labels of (n_ig - k f_g)^2 / (k f_g)."""
+    counts = graph.label_counts(lab, G).double()
+    share = torch.bincount(lab.clamp(0, G - 1), weights=((lab >= 0) & (lab < G)).double(), minlength=G) / lab.shape[0]
+    full = share > 0
+    expect = torch.where(full, k * share, torch.ones_like(share))
+    stat = torch.where(full, (counts - expect) ** 2 / expect, torch.zeros_like(expect)).sum(1)
+    return stat, full.sum() - 1
+
+
+def kbet(x, batch, k: Optional[int] = None, alpha: float = 0.05, graph=None, num_labels: Optional[int] = None,
+         generator=None) -> KBETResult:
+    """kBET over the cloud x [N, P] (f32, device, P % 4 == 0) with the batch labels `batch` [N]: KBETResult.
+
+    Per row, with n_ig the counts of the labels among its k nearest OTHER rows and f_g the global label shares:
+    stat_i = sum_g (n_ig - k f_g)^2 / (k f_g), pvalue_i = P(chi2_{G-1} > stat_i) = gammaincc((G - 1) / 2, stat_i / 2) in
+    f64; rejection_rate = mean(pvalue < alpha): 0 for batches mixed as in the whole cloud, 1 for separate ones.
+    k=None: kBET's default floor(mean batch size / 4), clipped to [10, min(1024, N - 1)]; the result reports it.
+    graph: a KNNGraph of the cloud against itself (neighbors.knn_graph(x, k)) to reuse; x is then not read (None is
+    allowed), host tensors work, and a smaller k takes the graph's first k columns.
+    num_labels=None relabels with torch.unique; num_labels=G: the labels are 0..G-1 already.  A label without points
+    leaves the sum and the degrees of freedom.  generator: also the rate under one random permutation of the labels on
+    the same graph (torch.randperm on the generator's device) - the rate a cloud without batch structure would show."""
+    if graph is None:
+        neighbors._check_cloud(x)
+        N = x.shape[0]
+        if N < 2:
+            raise ValueError("at least 2 rows")
+    else:
+        neighbors._check_graph(graph)
+        N = graph.indices.shape[0]
+    lab = _graph_labels("batch", batch, num_labels, N)
+    _check_k(k, N)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0 < alpha < 1:
+        raise ValueError(f"alpha must lie in (0, 1), got {alpha!r}")
+    if generator is not None and not isinstance(generator, torch.Generator):
+        raise ValueError("generator must be None or a torch.Generator")
+    if graph is None and not x.is_cuda:
+        raise ValueError("kbet needs a device cloud or graph= (there is no CPU fallback for the search)")
+    lab, G = _relabel(lab, num_labels)
+    if k is None and graph is None:
+        full = int((torch.bincount(lab.clamp(0, G - 1), minlength=G) > 0).sum())
+        k = min(max(10, N // max(full, 1) // 4), neighbors.MAX_K, N - 1)
+    graph = _graph_arg(x, graph, k, N)
+    k = graph.k
+    lab = lab.to(graph.indices.device)
+    stat, dof = _kbet_stat(graph, lab, G, k)
+    pvalue = torch.special.gammaincc(dof.double() / 2, stat / 2)
+    rate = (pvalue < alpha).double().mean()
+    expected = None
+    if generator is not None:
+        perm = torch.randperm(N, generator=generator, device=generator.device).to(lab.device)
+        stat_p, _ = _kbet_stat(graph, lab[perm], G, k)
+        expected = (torch.special.gammaincc(dof.double() / 2, stat_p / 2) < alpha).double().mean()
+    return KBETResult(stat, pvalue, rate, 1 - rate, expected, k, dof)
+
+
+LISI_KNN_TRIES = 50
+LISI_KNN_TOL = 1e-5
+
+
+def _check_lisi_knn(perplexity, k, N):
+    if isinstance(perplexity, bool) or not isinstance(perplexity, (int, float)) or not perplexity > 0:
+        raise ValueError(f"perplexity must be a positive number, got {perplexity!r}")
+    _check_k(k, N)
+    if k is None and not 1 <= int(3 * perplexity) - 1 <= min(neighbors.MAX_K, N - 1):
+        raise ValueError(f"3 * perplexity - 1 = {int(3 * perplexity) - 1} neighbours must lie in [1, min(1024, N - 1)] = "
+                         f"[1, {min(neighbors.MAX_K, N - 1)}]")
+
+
+def lisi_knn(x, labels, perplexity: float = 30.0, k: Optional[int] = None, graph=None,
+             num_labels: Optional[int] = None) -> torch.Tensor:
+    """f32 [N]: LISI as published (Korsunsky et al. 2019, compute_lisi) on the exact k-nearest-neighbour graph of the cloud
+    x [N, P] (f32, device, P % 4 == 0): k = 3 * perplexity - 1 other rows (k=None), UNSQUARED Euclidean distances d.
+
+    Per row: P = exp(-beta d) from beta = 1; H = log(sum P) + beta sum(d P) / sum P and P /= sum P (sum P == 0: H = 0,
+    P = 0); up to 50 bisection steps on beta (doubling / halving while a bound is infinite) while |H - log(perplexity)| >=
+    1e-5; Simpson = sum_g (sum of P over the neighbours of label g)^2, LISI = 1 / Simpson; a row with H == 0 has Simpson
+    -1 (LISI -1), as there.  Vectorised in f64 over [N, k] with 50 masked steps and no host read: with num_labels (labels
+    already 0..G-1 on the device) a call can be captured.  graph: a KNNGraph of the cloud against itself to reuse (x is
+    not read and may be None; host tensors work; a smaller k takes its first k columns).  iLISI / cLISI by the label."""
+    if graph is None:
+        neighbors._check_cloud(x)
+        N = x.shape[0]
+        if N < 2:
+            raise ValueError("at least 2 rows")
+    else:
+        neighbors._check_graph(graph)
+        N = graph.indices.shape[0]
+    lab = _graph_labels("labels", labels, num_labels, N)
+    _check_lisi_knn(perplexity, k, N)
+    if graph is None and not x.is_cuda:
+        raise ValueError("lisi_knn needs a device cloud or graph= (there is no CPU fallback for the search)")
+    if k is None and graph is None:
+        k = int(3 * perplexity) - 1
+    graph = _graph_arg(x, graph, k, N)
+    lab, G = _relabel(lab, num_labels)
+    idx = graph.indices
+    return _lisi_knn_f64(graph, lab.to(idx.device)[idx.clamp(min=0)], G, perplexity).float()
+
+
+def _lisi_knn_f64(graph, lab, G, perplexity):
+    """f64 [N]: lisi_knn's arithmetic; lab int64 [N, k]: the neighbours' labels as positions 0..G-1."""
+    d = graph.sqdist.double().sqrt()                                 # the root in f64: no second f32 rounding
+    target = math.log(perplexity)
+
+    def entropy(beta):
+        p = torch.exp(-beta[:, None] * d)
+        sp = p.sum(1)
+        empty = sp == 0
+        safe = torch.where(empty, torch.ones_like(sp), sp)
+        h = torch.where(empty, torch.zeros_like(sp), torch.log(safe) + beta * (d * p).sum(1) / safe)
+        return h, torch.where(empty[:, None], torch.zeros_like(p), p / safe[:, None])
+
+    beta = torch.ones(d.shape[0], dtype=torch.float64, device=d.device)
+    lo, hi = torch.full_like(beta, -math.inf), torch.full_like(beta, math.inf)
+    h, p = entropy(beta)
+    for _ in range(LISI_KNN_TRIES):
+        diff = h - target
+        active = diff.abs() >= LISI_KNN_TOL
+        up = diff > 0
+        lo = torch.where(active & up, beta, lo)
+        hi = torch.where(active & ~up, beta, hi)
+        nb = torch.where(up, torch.where(torch.isinf(hi), beta * 2, (beta + hi) / 2),
+                         torch.where(torch.isinf(lo), beta / 2, (beta + lo) / 2))
+        beta = torch.where(active, nb, beta)
+        h2, p2 = entropy(beta)
+        h, p = torch.where(active, h2, h), torch.where(active[:, None], p2, p)
+    # sum_g (sum_{t: label_t = g} P_t)^2 = sum_{t, u: label_t = label_u} P_t P_u, in row chunks of about 128 MiB: a fixed
+    # order whatever G is (a float scatter_add_ on the device is atomic, so its bits change from run to run)
+    p = torch.where((lab >= 0) & (lab < G), p, torch.zeros_like(p))
+    k = d.shape[1]
+    rows = max(1, (1 << 24) // (k * k))
+    same = [((p[r:r + rows, :, None] * p[r:r + rows, None, :])
+             * (lab[r:r + rows, :, None] == lab[r:r + rows, None, :])).sum((1, 2)) for r in range(0, d.shape[0], rows)]
+    simpson = torch.where(h == 0, torch.full_like(h, -1.0), torch.cat(same))
+    return 1.0 / simpson

@@ -727,6 +727,50 @@ def sim_topk(x, y, k: int, scale: Optional[float] = None):
     return scores, idx
 
 
+def sim_knn(x, y, k: int, scale: Optional[float] = None, bias=None, diag_offset: int = -1, after=None):
+    """(scores f32 [Mx, k], idx int64 [Mx, k]): the k best ELIGIBLE keys of z = scale * x y^T + bias[None, :] per row in
+    the order of sim_topk (include/clipk.h: clipk_sim_knn).  bias: device f32 [Ny] or None; diag_offset >= 0: row i skips
+    key i + diag_offset (-1: none); after = (scores f32 [Mx], idx int64 [Mx]): a cursor in the order - only keys strictly
+    after it are eligible.  1 <= k <= 64; with fewer than k eligible keys the trailing slots are (-inf, -1)."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 64:
+        raise ValueError(f"k must be an int in [1, 64], got {k!r}")
+    if isinstance(diag_offset, bool) or not isinstance(diag_offset, int) or diag_offset < -1:
+        raise ValueError(f"diag_offset must be -1 or a non-negative int, got {diag_offset!r}")
+    if bias is not None and (bias.dtype != torch.float32 or bias.shape != (Ny,) or not bias.is_contiguous()):
+        raise ValueError(f"bias must be a contiguous float32 tensor of shape ({Ny},)")
+    after_s = after_i = None
+    if after is not None:
+        if not isinstance(after, (tuple, list)) or len(after) != 2:
+            raise ValueError("after must be a (scores, idx) pair")
+        after_s, after_i = after
+        if after_s.dtype != torch.float32 or after_s.shape != (Mx,) or not after_s.is_contiguous() \
+                or after_i.dtype != torch.int64 or after_i.shape != (Mx,) or not after_i.is_contiguous():
+            raise ValueError(f"after must be contiguous (float32, int64) tensors of shape ({Mx},)")
+    _need_cuda(x, y, bias, after_s, after_i)
+    scores = torch.empty((Mx, k), dtype=torch.float32, device=x.device)
+    idx = torch.empty((Mx, k), dtype=torch.int64, device=x.device)
+    lib = _lib()
+    ws = workspace(lib.clipk_sim_knn_workspace(Mx, Ny, P, k), x.device, "retrieval")
+    check(lib.clipk_sim_knn(x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale), ptr(bias),
+                            diag_offset, ptr(after_s), ptr(after_i), k, scores.data_ptr(), idx.data_ptr(), ws.data_ptr(),
+                            ws.numel(), _stream()), "clipk_sim_knn")
+    return scores, idx
+
+
+def pair_sqdist(x, y, idx):
+    """f32 [Mx, k]: |x_i - y_{idx[i, t]}|^2 summed from the differences in a fixed order (include/clipk.h:
+    clipk_pair_sqdist); idx int64 [Mx, k], an entry outside [0, Ny) gives +inf."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != Mx or idx.shape[1] == 0 or not idx.is_contiguous():
+        raise ValueError(f"idx must be a contiguous int64 tensor of shape ({Mx}, k), k >= 1")
+    _need_cuda(x, y, idx)
+    d2 = torch.empty(idx.shape, dtype=torch.float32, device=x.device)
+    check(_lib().clipk_pair_sqdist(x.data_ptr(), Mx, y.data_ptr(), Ny, P, idx.data_ptr(), idx.shape[1], d2.data_ptr(),
+                                   _stream()), "clipk_pair_sqdist")
+    return d2
+
+
 def plane_pitch(P: int) -> int:
     """Row pitch (bf16 elements) of the planes clipk_split_bf16 writes: P rounded up to 32, pads zero."""
     return (int(P) + 31) // 32 * 32

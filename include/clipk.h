@@ -1156,6 +1156,45 @@ int clipk_tsne_update(const float* rows /*[N,ncomp]*/, int N, int ncomp /* 5 or 
                       float* z /* device scalar */, float* kl /* device scalar or NULL */,
                       float* gnorm /* device scalar or NULL */, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Exact k-nearest-neighbour graph of f32 clouds without the Mx x Ny matrix (clip_dplm_amd.neighbors.knn_graph): the
+ * neighbours that kBET and the published (kNN-truncated) LISI are made of - the batch-mixing scores the metric list
+ * of the reference's tong/experiments/evaluate.py (:39-47, compute_all_metrics / BiologicalMetrics) lacks, and the
+ * local view beside the KMeans + ARI of its analyze_embedding_alignment (tong/tests/losses/test_contrastive.py:11-16).
+ *
+ * clipk_sim_knn: the walk, register lists and merge tree of clipk_sim_topk with three additions:
+ *     z_ij = fl(fl(scale * s_ij) + bias[j])      s_ij: the accumulator bits of clipk_sim_topk; two separate roundings (no
+ *                                                fma); bias [Ny] device f32, NULL: the add is skipped
+ *     eligible(i, j):  j != i + diag_offset                                   (diag_offset = -1: no key skipped)
+ *                 and  (after_s == NULL  or  z_ij < after_s[i]  or  (z_ij == after_s[i] and j > after_i[i]))
+ *     scores[i, 0..k) / idx[i, 0..k) = the k best eligible (z_ij, j) of row i in the order of clipk_sim_topk (z descending,
+ *     equal z by the lower j), 1 <= k <= 64; with fewer than k eligible keys the trailing slots are (-inf, -1).
+ *   (after_s, after_i) [Mx] (both or neither) is a CURSOR: a position in the total order, after which the row resumes.  Fed
+ *   the last column of the previous call it returns the next k keys, so k is not bound by the 64 list registers.  It holds
+ *   the index as well as the score because a run of keys with equal z may straddle the boundary between two calls: a
+ *   score threshold alone would return the rest of the run twice (<=) or never (<).  A cursor (-inf, -1) - the tail of a
+ *   short list - leaves no key eligible.
+ *   Euclidean neighbours: scale = 1, bias[j] = -|Y_j|^2 / 2; z descending is |X_i - Y_j|^2 = |X_i|^2 - 2 z ascending.
+ *   With bias, cursor and diag_offset absent the results are the bits of clipk_sim_topk.
+ *   An ineligible key counts as -inf in the per-tile maximum test, so the common path stays one max and one compare per
+ *   tile.  A tile's 64 biases reach the lanes through LDS, loaded one tile ahead.  List sizes 1 / 8 / 16 / 64 (the 32-slot
+ *   instance measured slower than the 64-slot one at large shapes; results do not depend on the list size).  Contract of clipk_sim_topk: finite inputs, P % 4 == 0, X / Y 16-byte aligned, results bitwise independent of
+ *   the split plan (option retrieval_splits), never allocates, never synchronises, capturable, no float atomics; bad
+ *   shapes return CLIPK_ERR_* before any launch and the workspace helper returns 0.
+ *
+ * clipk_pair_sqdist: d2[i, t] = sum_p (X[i,p] - Y[idx[i,t], p])^2 in f32 from the differences (|x|^2 + |y|^2 - 2 <x, y>
+ *   cancels exactly where neighbours are closest).  Order: four running sums over the columns p = c mod 4, ascending p,
+ *   a_c = fma(d, d, a_c) with d = fl(x - y); d2 = fl(fl(a_0 + a_1) + fl(a_2 + a_3)).  |d2 - exact| <= (P / 4 + 5) 2^-24
+ *   exact (to first order).  An index outside [0, Ny) gives +inf.  The graph's order is that of z; these are the accurate distances of
+ *   those pairs and may therefore be out of order by rounding-sized amounts.  P % 4 == 0, X / Y 16-byte aligned. */
+size_t clipk_sim_knn_workspace(int Mx, int Ny, int P, int k);
+int clipk_sim_knn(const float* X, int Mx, const float* Y, int Ny, int P, float scale, const float* bias /*[Ny] or NULL*/,
+                  long long diag_offset, const float* after_s /*[Mx] or NULL*/, const int64_t* after_i /*[Mx] or NULL*/,
+                  int k, float* scores /*[Mx,k]*/, int64_t* idx /*[Mx,k]*/, void* workspace, size_t workspace_bytes,
+                  void* stream);
+int clipk_pair_sqdist(const float* X, int Mx, const float* Y, int Ny, int P, const int64_t* idx /*[Mx,k]*/, int k,
+                      float* d2 /*[Mx,k]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
