@@ -46,6 +46,8 @@ from .mixing import KBETResult, kbet, lisi_knn
 from . import mixing
 from .neighbors import KNNGraph, knn_graph
 from . import neighbors
+from .diffusion import DiffusionMap, SymGraph, connectivities, diffusion_map, dpt, pseudotime, pseudotime_preservation
+from . import diffusion
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -71,4 +73,5 @@ __all__ = [
     "manifold", "tsne", "TSNEResult", "perplexity_bandwidths", "embed_spaces", "knn_preservation",
     "mixing", "lisi", "label_masses", "LabelMasses", "label_transfer", "label_transfer_accuracy", "integration_scores",
     "kbet", "KBETResult", "lisi_knn", "neighbors", "knn_graph", "KNNGraph",
+    "diffusion", "connectivities", "diffusion_map", "pseudotime", "dpt", "pseudotime_preservation", "SymGraph", "DiffusionMap",
 ]

@@ -771,6 +771,52 @@ def pair_sqdist(x, y, idx):
     return d2
 
 
+SPMM_CHUNK = 64              # CLIPK_SPMM_CHUNK: entries of one chunk sum
+SPMM_MAX_M = 64              # CLIPK_SPMM_MAX_M
+
+
+def _csr_spmm_args(indptr, indices, w, x, s, b, c, out):
+    """(N, nnz, m) after every argument check of csr_spmm that needs no device."""
+    for name, t, dt in (("indptr", indptr, torch.int64), ("indices", indices, torch.int32), ("w", w, torch.float64),
+                        ("x", x, torch.float64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor")
+    if x.dim() != 2 or x.shape[0] == 0 or not 1 <= x.shape[1] <= SPMM_MAX_M:
+        raise ValueError(f"x must be [N, m] with N >= 1 and 1 <= m <= {SPMM_MAX_M}, got shape {tuple(x.shape)}")
+    N, m = x.shape
+    if indptr.shape != (N + 1,):
+        raise ValueError(f"indptr must have shape ({N + 1},), got {tuple(indptr.shape)}")
+    if indices.dim() != 1 or w.shape != indices.shape:
+        raise ValueError("indices and w must be 1-D tensors of one length")
+    if s is not None and (not isinstance(s, torch.Tensor) or s.dtype != torch.float64 or s.shape != (N,)
+                          or not s.is_contiguous()):
+        raise ValueError(f"s must be a contiguous float64 tensor of shape ({N},)")
+    for name, t in (("b", b), ("c", c), ("out", out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.shape != x.shape
+                              or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float64 tensor of shape {tuple(x.shape)}")
+    if out is not None and out.data_ptr() == x.data_ptr():
+        raise ValueError("out may be b or c but never x: rows of x are gathered while rows of out are written")
+    return N, indices.shape[0], m
+
+
+def csr_spmm(indptr, indices, w, x, s=None, alpha: float = 1.0, b=None, beta: float = 0.0, c=None, gamma: float = 0.0,
+             out=None):
+    """f64 [N, m]: alpha * diag(s) W diag(s) x + beta * b + gamma * c for a CSR matrix W (indptr int64 [N + 1], indices
+    int32 [nnz], w f64 [nnz]) on a block x f64 [N, m], 1 <= m <= 64; s f64 [N] or None (ones); b, c f64 [N, m] or None.
+    out: where to write (may be b or c, never x); None allocates.  The arithmetic is fixed and stated in include/clipk.h
+    (clipk_csr_spmm_f64): a numpy restatement gives the same bits.  No host read."""
+    N, nnz, m = _csr_spmm_args(indptr, indices, w, x, s, b, c, out)
+    _need_cuda(indptr, indices, w, x, s, b, c, out)
+    y = torch.empty_like(x) if out is None else out
+    lib = _lib()
+    ws = workspace(lib.clipk_csr_spmm_workspace(nnz, m), x.device, "spmm")
+    check(lib.clipk_csr_spmm_f64(indptr.data_ptr(), indices.data_ptr(), w.data_ptr(), ptr(s), N, nnz, m, x.data_ptr(),
+                                 float(alpha), ptr(b), float(beta), ptr(c), float(gamma), y.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), _stream()), "clipk_csr_spmm_f64")
+    return y
+
+
 def plane_pitch(P: int) -> int:
     """Row pitch (bf16 elements) of the planes clipk_split_bf16 writes: P rounded up to 32, pads zero."""
     return (int(P) + 31) // 32 * 32

@@ -1195,6 +1195,39 @@ int clipk_sim_knn(const float* X, int Mx, const float* Y, int Ny, int P, float s
 int clipk_pair_sqdist(const float* X, int Mx, const float* Y, int Ny, int P, const int64_t* idx /*[Mx,k]*/, int k,
                       float* d2 /*[Mx,k]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sparse symmetric operator on a block of f64 vectors (clip_dplm_amd.diffusion: the diffusion map's T = S W S, never
+ * materialised; the reference gets X_diffmap / dpt_pseudotime from scanpy on the host - run1/full.py:108,
+ * tong/utils/data.py:27-54).  One entry serves the plain operator, a Chebyshev three-term step
+ * Y = a (T X - c X) - b X_prev (alpha = a, B = X, beta = -a c, C = X_prev, gamma = -b) and a Lanczos step.
+ *
+ *   Y[i, c] = alpha * s_i * sum_{e in row i} (w_e * s_{col_e}) * X[col_e, c]  +  beta * B[i, c]  +  gamma * C[i, c]
+ *
+ * CSR: indptr int64 [N + 1] (indptr[0] = 0, ascending, indptr[N] = nnz), indices int32 [nnz], w f64 [nnz]; s f64 [N] or
+ * NULL (all ones); X, B, C, Y f64 [N, m] row-major, 1 <= m <= CLIPK_SPMM_MAX_M (else CLIPK_ERR_UNSUPPORTED); B and C may
+ * be NULL.  Y may be B or C (each element is read before it is written, by the same lane); Y may not overlap X
+ * (CLIPK_ERR_BAD_ARG).  workspace: clipk_csr_spmm_workspace(nnz, m) bytes (0 for nnz <= CLIPK_SPMM_CHUNK).
+ *
+ * THE ARITHMETIC (f64, every operation rounded once, to nearest; no fma; independent of the launch shape, of the
+ * alignment of the operands and of the device's occupancy - a numpy restatement reproduces every bit):
+ *   coef_e = s ? fl(w_e * s[col_e]) : w_e
+ *   row i's entries e = indptr[i] .. indptr[i + 1] - 1 are cut into chunks of CLIPK_SPMM_CHUNK, counted from the row's start;
+ *   chunk sum   p_q = (((+0 + fl(coef_e X[col_e, c])) + fl(coef_e' X[col_e', c])) + ...)   in ascending e
+ *   row sum     t   = ((p_0 + p_1) + p_2) + ...                  in chunk order; an empty row has t = +0
+ *   r = s ? fl(s_i * t) : t;   y = fl(alpha * r);   B: y = fl(y + fl(beta * B[i, c]));   C: y = fl(y + fl(gamma * C[i, c]))
+ *   (a NULL B or C is skipped, not multiplied by zero; alpha = 0 still multiplies: a non-finite r stays non-finite).
+ *   An entry whose column lies outside [0, N) is skipped.  Repeated columns and zero weights are ordinary entries.
+ * A group of lanes owns a (row, chunk); chunks q >= 1 are summed by a first launch into the workspace and added by the
+ * row's group: a hub row costs its group one chunk plus one partial per further chunk.  No float atomics; never
+ * allocates, never synchronises, capturable. */
+#define CLIPK_SPMM_CHUNK 64
+#define CLIPK_SPMM_MAX_M 64
+size_t clipk_csr_spmm_workspace(long long nnz, int m);
+int clipk_csr_spmm_f64(const int64_t* indptr /*[N+1]*/, const int32_t* indices /*[nnz]*/, const double* w /*[nnz]*/,
+                       const double* s /*[N] or NULL*/, int N, long long nnz, int m, const double* X /*[N,m]*/,
+                       double alpha, const double* B /*[N,m] or NULL*/, double beta, const double* C /*[N,m] or NULL*/,
+                       double gamma, double* Y /*[N,m]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
