@@ -27,7 +27,7 @@ from typing import Optional
 
 import torch
 
-from . import ops
+from . import _args, ops
 
 __all__ = ["kmeans", "KMeansResult", "init_centroids", "contingency", "adjusted_rand_index", "normalized_mutual_info",
            "cluster_agreement", "silhouette_samples", "silhouette_score", "silhouette_by_label", "davies_bouldin_score",
@@ -38,15 +38,6 @@ INITS = ("k-means++", "random")
 
 
 # ------------------------------------------------------------------------------------------------ seeding
-def _generator_for(generator, device):
-    """A generator on `device`: the one given, or one seeded by a draw from it when it lives elsewhere (a host
-    generator with a device cloud) - a host-side draw, nothing is read back from the device."""
-    if generator is None or generator.device.type == torch.device(device).type:
-        return generator
-    seed = int(torch.randint(2 ** 62, (1,), generator=generator, device=generator.device))
-    return torch.Generator(device=device).manual_seed(seed)
-
-
 def init_centroids(x, n_clusters: int, init="k-means++", generator=None):
     """n_clusters distinct rows of x [N, P] (any device) as the initial centroids [K, P].
 
@@ -57,7 +48,7 @@ def init_centroids(x, n_clusters: int, init="k-means++", generator=None):
     if init not in INITS:
         raise ValueError(f"init must be one of {INITS} or a tensor, got {init!r}")
     N = x.shape[0]
-    gen = _generator_for(generator, x.device)
+    gen = _args.generator_for(generator, x.device)
     if init == "random":
         return x[torch.randperm(N, generator=gen, device=x.device)[:n_clusters]].clone()
     idx = torch.randint(N, (1,), generator=gen, device=x.device)
@@ -90,10 +81,12 @@ class KMeansResult:
     def predict(self, x):
         """The nearest centroid of every row of x [M, P] (f32, device): int64 [M], the assignment `labels` came from."""
         _check_cloud(x)
-        return _assign(_prepare(x, self.metric), self.centroids, self.metric)[0].long()
+        return _assign(_args.prepare(x, self.metric, half=False), self.centroids, self.metric)[0].long()
 
 
 def _check_cloud(x, n_clusters: Optional[int] = None):
+    """The k-means limits.  Its own wording, not _args.check_cloud's: a non-tensor and a wrong dtype are TypeErrors here,
+    and an empty cloud is reported with the dimension."""
     if not isinstance(x, torch.Tensor):
         raise TypeError("x must be a tensor")
     if x.dtype != torch.float32:
@@ -105,7 +98,7 @@ def _check_cloud(x, n_clusters: Optional[int] = None):
         raise ValueError(f"the width must be a multiple of 4 and at most {ops.KMEANS_MAX_P}, got {P}")
     if x.shape[0] > ops.KMEANS_MAX_N:
         raise ValueError(f"at most {ops.KMEANS_MAX_N} rows, got {x.shape[0]}")
-    if n_clusters is not None:
+    if n_clusters is not None:                                     # (inline: the message goes on after the value)
         if isinstance(n_clusters, bool) or not isinstance(n_clusters, int):
             raise TypeError(f"n_clusters must be an int, got {n_clusters!r}")
         if not 1 <= n_clusters <= min(x.shape[0], ops.KMEANS_MAX_K):
@@ -115,8 +108,7 @@ def _check_cloud(x, n_clusters: Optional[int] = None):
 def _check_args(x, n_clusters, init, n_init, max_iter, tol, check_every, metric):
     """Every argument error of kmeans(), raised before anything is launched."""
     _check_cloud(x, n_clusters)
-    if metric not in METRICS:
-        raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
+    _args.check_metric(metric, METRICS)
     if isinstance(init, torch.Tensor):
         if init.dtype != torch.float32:
             raise TypeError(f"init must be float32, got {init.dtype}")
@@ -125,19 +117,10 @@ def _check_args(x, n_clusters, init, n_init, max_iter, tol, check_every, metric)
     elif init is not None and init not in INITS:
         raise ValueError(f"init must be one of {INITS} or a tensor, got {init!r}")
     for name, v, lo in (("n_init", n_init, 1), ("max_iter", max_iter, 0), ("check_every", check_every, 1)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise TypeError(f"{name} must be an int, got {v!r}")
-        if v < lo:
-            raise ValueError(f"{name} must be at least {lo}, got {v}")
+        _args.int_in(name, v, lo, what=f"at least {lo}", type_error=True)
     if tol is not None and not float(tol) >= 0:
         raise ValueError(f"tol must be None or a non-negative number, got {tol!r}")
-    if not x.is_cuda or (isinstance(init, torch.Tensor) and not init.is_cuda):
-        raise ValueError("kmeans needs device tensors (there is no CPU fallback)")
-
-
-def _prepare(x, metric):
-    x = x.detach().contiguous()
-    return torch.nn.functional.normalize(x, dim=1) if metric == "cosine" else x
+    _args.need_device("kmeans needs", x, init if isinstance(init, torch.Tensor) else None)
 
 
 def _norms(c, metric):
@@ -210,7 +193,7 @@ def kmeans(x, n_clusters: int, *, init=None, n_init: int = 1, max_iter: int = 30
     _check_args(x, n_clusters, init, n_init, max_iter, tol, check_every, metric)
     if init is None:
         init = "k-means++" if n_clusters <= ops.KMEANS_MAX_K_FUSED else "random"
-    x = _prepare(x, metric)
+    x = _args.prepare(x, metric, half=False)
     best = None
     for _ in range(1 if isinstance(init, torch.Tensor) else n_init):
         c = init.detach().contiguous() if isinstance(init, torch.Tensor) else init_centroids(x, n_clusters, init, generator)
@@ -229,18 +212,10 @@ def kmeans(x, n_clusters: int, *, init=None, n_init: int = 1, max_iter: int = 30
 
 
 # ------------------------------------------------------------------------------------------------ agreement of two labelings
-def _labels_arg(name, t):
-    if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
-        raise TypeError(f"{name} must be an integer tensor")
-    if t.dim() != 1:
-        raise ValueError(f"{name} must be 1-D, got shape {tuple(t.shape)}")
-    return t.long()
-
-
 def contingency(labels_a, labels_b):
     """int64 [Ga, Gb]: entry (g, h) counts the points with labels_a == g and labels_b == h (non-negative integer labels
     [n], device or host; Ga, Gb = the largest label + 1).  One torch.bincount over the pair index."""
-    a, b = _labels_arg("labels_a", labels_a), _labels_arg("labels_b", labels_b)
+    a, b = _args.labels_arg("labels_a", labels_a), _args.labels_arg("labels_b", labels_b)
     if a.shape != b.shape:
         raise ValueError(f"the labelings have {a.shape[0]} and {b.shape[0]} entries")
     if a.device != b.device:
@@ -302,9 +277,7 @@ def cluster_agreement(a, b, n_clusters: int = 10, labels=None, silhouette: bool 
     if a.shape[0] != b.shape[0]:
         raise ValueError(f"the clouds are paired row by row, got {a.shape[0]} and {b.shape[0]} rows")
     if labels is not None:
-        labels = _labels_arg("labels", labels)
-        if labels.shape[0] != a.shape[0]:
-            raise ValueError(f"labels has {labels.shape[0]} entries for {a.shape[0]} rows")
+        labels = _args.labels_arg("labels", labels, a.shape[0])
     la, lb = kmeans(a, n_clusters, **kmeans_kw).labels, kmeans(b, n_clusters, **kmeans_kw).labels
     out = {"ari": adjusted_rand_index(la, lb), "nmi": normalized_mutual_info(la, lb)}
     metric = kmeans_kw.get("metric", "euclidean")
@@ -329,10 +302,8 @@ CRITERIA = ("silhouette", "calinski_harabasz", "davies_bouldin")
 def _relabel(x, labels):
     """(label values [G] ascending, positions int64 [N] in 0..G-1, counts int64 [G]) of an annotation of x's rows; the
     ValueError of every score here unless 2 <= G <= N - 1.  torch.unique: the one host read (G is a shape)."""
-    labels = _labels_arg("labels", labels)
     N = x.shape[0]
-    if labels.shape[0] != N:
-        raise ValueError(f"labels has {labels.shape[0]} entries for {N} rows")
+    labels = _args.labels_arg("labels", labels, N)
     values, inv, counts = torch.unique(labels, return_inverse=True, return_counts=True)
     G = values.shape[0]
     if not 2 <= G <= N - 1:
@@ -343,17 +314,14 @@ def _relabel(x, labels):
 def _silhouette(x, labels, metric, row_block):
     """(s f32 [N], values, inv, counts): every argument error first, then the row-block walks."""
     _check_cloud(x)
-    if metric not in SILHOUETTE_METRICS:
-        raise ValueError(f"metric must be one of {SILHOUETTE_METRICS}, got {metric!r}")
-    if row_block is not None and (isinstance(row_block, bool) or not isinstance(row_block, int) or row_block < 1):
-        raise ValueError(f"row_block must be None or a positive int, got {row_block!r}")
+    _args.check_metric(metric, SILHOUETTE_METRICS)
+    _args.int_in("row_block", row_block, 1, optional=True)
     values, inv, counts = _relabel(x, labels)
-    if not x.is_cuda:
-        raise ValueError("the silhouette needs device tensors (there is no CPU fallback)")
+    _args.need_device("the silhouette needs", x)
     G, N = values.shape[0], x.shape[0]
     if G > ops.LABEL_DIST_MAX_LABELS:
         raise ValueError(f"at most {ops.LABEL_DIST_MAX_LABELS} distinct labels, got {G}")
-    x = _prepare(x, metric)
+    x = _args.prepare(x, metric, half=False)
     inv, counts = inv.to(x.device), counts.to(x.device)
     lab32 = inv.int()
     nx = None if metric == "cosine" else (x * x).sum(1)
@@ -393,11 +361,8 @@ def _subset(x, labels, sample_size, generator):
         return x, labels
     _check_cloud(x)
     N = x.shape[0]
-    if isinstance(sample_size, bool) or not isinstance(sample_size, int) or not 1 <= sample_size <= N:
-        raise ValueError(f"sample_size must be None or an int in [1, N], got {sample_size!r}")
-    labels = _labels_arg("labels", labels)
-    if labels.shape[0] != N:
-        raise ValueError(f"labels has {labels.shape[0]} entries for {N} rows")
+    _args.int_in("sample_size", sample_size, 1, N, what="None or an int in [1, N]")
+    labels = _args.labels_arg("labels", labels, N)
     gdev = generator.device if generator is not None else "cpu"
     idx = torch.randperm(N, generator=generator, device=gdev)[:sample_size]
     return x[idx.to(x.device)], labels[idx.to(labels.device)]

@@ -29,7 +29,7 @@ from typing import Optional
 
 import torch
 
-from . import neighbors, ops
+from . import _args, neighbors, ops
 from .neighbors import KNNGraph
 
 __all__ = ["SymGraph", "DiffusionMap", "connectivities", "diffusion_map", "pseudotime", "dpt",
@@ -137,7 +137,7 @@ def _smooth_knn(d: torch.Tensor):
 
 
 def _check_self_graph(graph):
-    neighbors._check_graph(graph)
+    neighbors.check_graph(graph)
     N, k = graph.indices.shape
     if N < 2 or k > N - 1:
         raise ValueError(f"graph must be a cloud's graph against itself (neighbors.knn_graph(x, k)): {N} rows with {k} "
@@ -194,20 +194,17 @@ def _check_map_args(x_or_graph, n_comps, n_neighbors, metric, tol, max_outer, ge
         _check_self_graph(x_or_graph)
         N = x_or_graph.indices.shape[0]
     else:
-        neighbors._check_cloud(x_or_graph)
+        _args.check_cloud(x_or_graph)
         N = x_or_graph.shape[0]
-        if metric not in neighbors.METRICS:
-            raise ValueError(f"metric must be one of {neighbors.METRICS}, got {metric!r}")
-        if isinstance(n_neighbors, bool) or not isinstance(n_neighbors, int) \
-                or not 2 <= n_neighbors <= min(neighbors.MAX_K + 1, N):
-            raise ValueError(f"n_neighbors (the point itself included) must be an int in [2, min(1025, N)] = "
-                             f"[2, {min(neighbors.MAX_K + 1, N)}], got {n_neighbors!r}")
-    if isinstance(n_comps, bool) or not isinstance(n_comps, int) or not 1 <= n_comps <= min(MAX_COMPS, N):
-        raise ValueError(f"n_comps must be an int in [1, min({MAX_COMPS}, N)] = [1, {min(MAX_COMPS, N)}], got {n_comps!r}")
+        _args.check_metric(metric, neighbors.METRICS)
+        kmax = min(neighbors.MAX_K + 1, N)
+        _args.int_in("n_neighbors (the point itself included)", n_neighbors, 2, kmax,
+                     what=f"an int in [2, min(1025, N)] = [2, {kmax}]")
+    _args.int_in("n_comps", n_comps, 1, min(MAX_COMPS, N),
+                 what=f"an int in [1, min({MAX_COMPS}, N)] = [1, {min(MAX_COMPS, N)}]")
     if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not tol > 0:
         raise ValueError(f"tol must be a positive number, got {tol!r}")
-    if isinstance(max_outer, bool) or not isinstance(max_outer, int) or max_outer < 1:
-        raise ValueError(f"max_outer must be a positive int, got {max_outer!r}")
+    _args.int_in("max_outer", max_outer, 1)
     if generator is not None and not isinstance(generator, torch.Generator):
         raise ValueError("generator must be None or a torch.Generator")
     dev = x_or_graph.weights if isinstance(x_or_graph, SymGraph) else \
@@ -322,8 +319,7 @@ def _check_dm(dm, n_dcs):
             or not isinstance(dm.eigenvectors, torch.Tensor) or dm.eigenvectors.dim() != 2 \
             or dm.eigenvalues.shape != dm.eigenvectors.shape[1:]:
         raise ValueError("dm must be a DiffusionMap (diffusion.diffusion_map)")
-    if isinstance(n_dcs, bool) or not isinstance(n_dcs, int) or n_dcs < 1:
-        raise ValueError(f"n_dcs must be a positive int, got {n_dcs!r}")
+    _args.int_in("n_dcs", n_dcs, 1)
 
 
 @torch.no_grad()

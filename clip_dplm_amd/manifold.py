@@ -25,7 +25,7 @@ from typing import Optional, Union
 
 import torch
 
-from . import ops, retrieval
+from . import _args, ops, retrieval
 
 __all__ = ["perplexity_bandwidths", "tsne", "TSNEResult", "embed_spaces", "knn_preservation", "auto_learning_rate"]
 
@@ -36,42 +36,17 @@ CANDIDATES = 8                                           # per row and walk: ops
 BRACKET_OCTAVES = 20.0                                   # the first bracket: +- this many octaves around 1 / mean(d - m)
 
 
-# ------------------------------------------------------------------------------------------------ argument checks
-def _check_cloud(x):
-    if not isinstance(x, torch.Tensor):
-        raise ValueError("x must be a float32 device tensor")
-    if x.dtype != torch.float32:
-        raise ValueError(f"x must be float32, got {x.dtype}")
-    if x.dim() != 2:
-        raise ValueError(f"x must be a 2-D tensor, got shape {tuple(x.shape)}")
-    N, P = x.shape
-    if N < ops.TSNE_MIN_N:
-        raise ValueError(f"at least {ops.TSNE_MIN_N} rows, got {N}")
-    if P == 0 or P % 4 or P > ops.TSNE_MAX_P:
-        raise ValueError(f"the width must be a multiple of 4 and at most {ops.TSNE_MAX_P}, got {P}")
-
-
-def _check_device(*ts):
-    if not all(t.is_cuda for t in ts):
-        raise ValueError("t-SNE needs device tensors (there is no CPU fallback)")
-
-
-def _check_perplexity(perplexity, N):
+def check_cloud(x, perplexity, metric) -> int:
+    """The argument errors of a cloud to calibrate, in this order: the walks' limits on x, 0 < perplexity < N - 1, the
+    metric.  Returns N."""
+    _args.check_cloud(x, min_rows=ops.TSNE_MIN_N, max_width=ops.TSNE_MAX_P)
+    N = x.shape[0]
     if isinstance(perplexity, bool) or not isinstance(perplexity, (int, float)):
         raise ValueError(f"perplexity must be a number, got {perplexity!r}")
     if not 0 < perplexity < N - 1:
         raise ValueError(f"perplexity must lie in (0, N - 1) = (0, {N - 1}), got {perplexity}")
-
-
-def _check_metric(metric):
-    if metric not in METRICS:
-        raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
-
-
-def _prepare(x, metric):
-    """Rows whose squared distances are the metric: unit rows scaled by 1 / sqrt 2 have d = 1 - cos."""
-    x = x.detach().contiguous()
-    return torch.nn.functional.normalize(x, dim=1) * math.sqrt(0.5) if metric == "cosine" else x
+    _args.check_metric(metric, METRICS)
+    return N
 
 
 def auto_learning_rate(N: int, early_exaggeration: float = 12.0) -> float:
@@ -84,7 +59,7 @@ def _entropy(beta, s0, s1):
     return torch.log(s0) + beta * s1 / s0
 
 
-def _bandwidths(x, nx, perplexity, passes):
+def calibrate(x, nx, perplexity, passes):
     """(beta, dmin, log_s0, entropy) of the prepared cloud.  The bracket [lo, hi] on log2 beta is held in f64: 40 / 9^8
     octaves is below the f32 spacing at 20."""
     N = x.shape[0]
@@ -119,14 +94,11 @@ def perplexity_bandwidths(x, perplexity: float, passes: int = 8, metric: str = "
     target), one walk at the chosen beta: passes + 2 walks, no host read.  Eight passes leave 40 / 9^8 octaves.
     A row whose nearest neighbour is repeated more often than the perplexity cannot reach the target: it ends at the
     upper end of its bracket, with finite values."""
-    _check_cloud(x)
-    _check_perplexity(perplexity, x.shape[0])
-    _check_metric(metric)
-    if isinstance(passes, bool) or not isinstance(passes, int) or passes < 1:
-        raise ValueError(f"passes must be a positive int, got {passes!r}")
-    _check_device(x)
-    x = _prepare(x, metric)
-    return _bandwidths(x, (x * x).sum(1), perplexity, passes)
+    check_cloud(x, perplexity, metric)
+    _args.int_in("passes", passes, 1)
+    _args.need_device("t-SNE needs", x)
+    x = _args.prepare(x, metric)
+    return calibrate(x, (x * x).sum(1), perplexity, passes)
 
 
 # ------------------------------------------------------------------------------------------------ the descent
@@ -141,13 +113,6 @@ class TSNEResult:
     entropy: torch.Tensor
     n_iter: int
     learning_rate: float
-
-
-def _generator_for(generator, device):
-    if generator is None or generator.device.type == torch.device(device).type:
-        return generator
-    seed = int(torch.randint(2 ** 62, (1,), generator=generator, device=generator.device))
-    return torch.Generator(device=device).manual_seed(seed)
 
 
 def pca_init(x):
@@ -166,7 +131,8 @@ def _initial_map(x, init, generator):
         return init.detach().clone().contiguous()
     if init == "pca":
         return pca_init(x)
-    return 1e-4 * torch.randn((N, 2), generator=_generator_for(generator, x.device), dtype=torch.float32, device=x.device)
+    return 1e-4 * torch.randn((N, 2), generator=_args.generator_for(generator, x.device), dtype=torch.float32,
+                              device=x.device)
 
 
 def tsne(x, perplexity: float = 30.0, n_iter: int = 1000, early_exaggeration: float = 12.0, exaggeration_iters: int = 250,
@@ -181,15 +147,10 @@ def tsne(x, perplexity: float = 30.0, n_iter: int = 1000, early_exaggeration: fl
     [N, 2].  metric "cosine": d = 1 - cos.  Every iteration is one walk over all pairs and one elementwise step; the count
     is fixed and nothing is read back, so the call can be captured in a graph (with a tensor or "random" init).
     kl_every=k also evaluates the KL value before iterations k, 2k, ...; the value of the returned map always is."""
-    _check_cloud(x)
-    N = x.shape[0]
-    _check_perplexity(perplexity, N)
-    _check_metric(metric)
-    for name, v, lo in (("n_iter", n_iter, 0), ("exaggeration_iters", exaggeration_iters, 0)):
-        if isinstance(v, bool) or not isinstance(v, int) or v < lo:
-            raise ValueError(f"{name} must be an int >= {lo}, got {v!r}")
-    if kl_every is not None and (isinstance(kl_every, bool) or not isinstance(kl_every, int) or kl_every < 1):
-        raise ValueError(f"kl_every must be None or a positive int, got {kl_every!r}")
+    N = check_cloud(x, perplexity, metric)
+    _args.int_in("n_iter", n_iter, 0)
+    _args.int_in("exaggeration_iters", exaggeration_iters, 0)
+    _args.int_in("kl_every", kl_every, 1, optional=True)
     if not float(early_exaggeration) >= 1.0:
         raise ValueError(f"early_exaggeration must be at least 1, got {early_exaggeration!r}")
     if isinstance(learning_rate, str):
@@ -205,11 +166,11 @@ def tsne(x, perplexity: float = 30.0, n_iter: int = 1000, early_exaggeration: fl
             raise ValueError(f"init must be a float32 tensor of shape ({N}, 2)")
     elif init not in INITS:
         raise ValueError(f"init must be one of {INITS} or a tensor, got {init!r}")
-    _check_device(x, *([init] if isinstance(init, torch.Tensor) else []))
+    _args.need_device("t-SNE needs", x, init if isinstance(init, torch.Tensor) else None)
 
-    x = _prepare(x, metric)
+    x = _args.prepare(x, metric)
     nx = (x * x).sum(1)
-    beta, dmin, log_s0, entropy = _bandwidths(x, nx, perplexity, 8)
+    beta, dmin, log_s0, entropy = calibrate(x, nx, perplexity, 8)
     y = _initial_map(x, init, generator)
     update, gains = torch.zeros_like(y), torch.ones_like(y)
     z = torch.empty((), dtype=torch.float32, device=x.device)
@@ -263,8 +224,7 @@ def knn_preservation(x, y2, k: int = 10, row_block: int = 4096) -> torch.Tensor:
         raise ValueError("x and y2 must be 2-D tensors")
     if x.shape[0] != y2.shape[0]:
         raise ValueError(f"x has {x.shape[0]} rows, y2 {y2.shape[0]}")
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min(63, x.shape[0] - 2):
-        raise ValueError(f"k must be an int in [1, min(63, N - 2)], got {k!r}")
+    _args.int_in("k", k, 1, min(63, x.shape[0] - 2), what="an int in [1, min(63, N - 2)]")
     if x.dtype != torch.float32 or y2.dtype != torch.float32 or not (x.is_cuda and y2.is_cuda):
         raise ValueError("x and y2 must be float32 device tensors")
     a, b = _knn(x.detach(), k), _knn(y2.detach(), k)

@@ -39,8 +39,7 @@ from typing import Optional
 
 import torch
 
-from . import manifold, neighbors, ops
-from .cluster import _labels_arg
+from . import _args, manifold, neighbors, ops
 
 __all__ = ["LabelMasses", "label_masses", "lisi", "label_transfer", "label_transfer_accuracy", "integration_scores",
            "median_score", "scale_ilisi", "scale_clisi", "merge_label_blocks", "KBETResult", "kbet", "lisi_knn"]
@@ -111,18 +110,10 @@ def scale_clisi(median: float, num_labels: int) -> float:
 # ------------------------------------------------------------------------------------------------ argument checks
 def _check_args(x, labels, perplexity, metric, bandwidths, num_labels, row_block, return_matrix):
     """Every argument error, before any device work; the labels as an int64 vector."""
-    manifold._check_cloud(x)
-    N = x.shape[0]
-    manifold._check_perplexity(perplexity, N)
-    manifold._check_metric(metric)
-    labels = _labels_arg("labels", labels)
-    if labels.shape[0] != N:
-        raise ValueError(f"labels has {labels.shape[0]} entries for {N} rows")
-    if num_labels is not None:
-        if isinstance(num_labels, bool) or not isinstance(num_labels, int) or not 1 <= num_labels <= MAX_LABELS:
-            raise ValueError(f"num_labels must be None or an int in [1, {MAX_LABELS}], got {num_labels!r}")
-    if row_block is not None and (isinstance(row_block, bool) or not isinstance(row_block, int) or row_block < 1):
-        raise ValueError(f"row_block must be None or a positive int, got {row_block!r}")
+    N = manifold.check_cloud(x, perplexity, metric)
+    labels = _args.labels_arg("labels", labels, N)
+    _args.int_in("num_labels", num_labels, 1, MAX_LABELS, optional=True)
+    _args.int_in("row_block", row_block, 1, optional=True)
     if not isinstance(return_matrix, bool):
         raise ValueError(f"return_matrix must be a bool, got {return_matrix!r}")
     if bandwidths is not None:
@@ -131,9 +122,7 @@ def _check_args(x, labels, perplexity, metric, bandwidths, num_labels, row_block
         for name, t in zip(("beta", "dmin", "log_s0", "entropy"), bandwidths):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (N,):
                 raise ValueError(f"bandwidths: {name} must be a float32 tensor of shape ({N},)")
-    ts = [x] + (list(bandwidths) if bandwidths is not None else []) + ([labels] if num_labels is not None else [])
-    if not all(t.is_cuda for t in ts):
-        raise ValueError("LISI needs device tensors (there is no CPU fallback)")
+    _args.need_device("LISI needs", x, *(bandwidths or ()), labels if num_labels is not None else None)
     return labels
 
 
@@ -166,9 +155,9 @@ def label_masses(x, labels, perplexity: float = 30.0, metric: str = "sqeuclidean
             raise ValueError(f"at most {MAX_LABELS} distinct labels, got {G}")
     else:
         values, inv, G = None, labels, num_labels
-    x = manifold._prepare(x, metric)
+    x = _args.prepare(x, metric)
     nx = (x * x).sum(1)
-    beta, dmin, _, entropy = bandwidths if bandwidths is not None else manifold._bandwidths(x, nx, perplexity, 8)
+    beta, dmin, _, entropy = bandwidths if bandwidths is not None else manifold.calibrate(x, nx, perplexity, 8)
     beta, dmin = beta.contiguous(), dmin.contiguous()
     lab32 = inv.to(x.device).int()
     GB = ops.LABEL_DIST_MAX_G
@@ -209,7 +198,7 @@ def label_transfer(x, labels, **kw):
 def label_transfer_accuracy(x, labels, **kw) -> torch.Tensor:
     """The mean agreement of label_transfer's prediction with `labels`: a 0-d f32 device tensor."""
     predicted, _ = label_transfer(x, labels, **kw)
-    return (predicted == _labels_arg("labels", labels).to(predicted.device)).float().mean()
+    return (predicted == _args.labels_arg("labels", labels).to(predicted.device)).float().mean()
 
 
 # ------------------------------------------------------------------------------------------------ the scores of a model
@@ -247,15 +236,12 @@ def integration_scores(clouds, labels=None, perplexity: float = 30.0, metric: st
         "label_transfer_accuracy"                                the leave-one-out kernel vote against the annotation."""
     clouds = _cloud_list(clouds)
     x = torch.cat([c.detach() for c in clouds]).contiguous()
-    manifold._check_cloud(x)
-    N, G = x.shape[0], len(clouds)
-    manifold._check_perplexity(perplexity, N)
-    manifold._check_metric(metric)
+    N, G = manifold.check_cloud(x, perplexity, metric), len(clouds)
     if labels is not None:
-        labels = _labels_arg("labels", labels)
+        labels = _args.labels_arg("labels", labels)
         if labels.shape[0] != N:
             raise ValueError(f"labels has {labels.shape[0]} entries for {N} rows of the concatenated clouds")
-    manifold._check_device(x)
+    _args.need_device("t-SNE needs", x)
     modality = torch.repeat_interleave(torch.arange(G, device=x.device),
                                        torch.tensor([c.shape[0] for c in clouds], device=x.device), output_size=N)
     bw = manifold.perplexity_bandwidths(x, perplexity, metric=metric)
@@ -285,18 +271,26 @@ class KBETResult:
     dof: torch.Tensor
 
 
+def _graph_rows(x, graph):
+    """N of the cloud x, or of the graph given in its place; the argument errors of either."""
+    if graph is not None:
+        neighbors.check_graph(graph)
+        return graph.indices.shape[0]
+    _args.check_cloud(x)
+    if x.shape[0] < 2:
+        raise ValueError("at least 2 rows")
+    return x.shape[0]
+
+
 def _graph_labels(name, labels, num_labels, N):
     """The labels as positions 0..G-1 (int64 [N]) and G; every argument error first."""
-    labels = _labels_arg(name, labels)
-    if labels.shape[0] != N:
-        raise ValueError(f"{name} has {labels.shape[0]} entries for {N} rows")
-    if num_labels is not None:
-        if isinstance(num_labels, bool) or not isinstance(num_labels, int) or num_labels < 1:
-            raise ValueError(f"num_labels must be None or a positive int, got {num_labels!r}")
+    labels = _args.labels_arg(name, labels, N)
+    _args.int_in("num_labels", num_labels, 1, optional=True)
     return labels
 
 
-def _relabel(labels, num_labels):
+def _label_positions(labels, num_labels):
+    """(the labels as positions 0..G-1, G): as they came with num_labels, else by torch.unique."""
     if num_labels is not None:
         return labels, num_labels
     values, inv = torch.unique(labels, return_inverse=True)
@@ -305,8 +299,7 @@ def _relabel(labels, num_labels):
 
 def _check_k(k, N):
     kmax = min(neighbors.MAX_K, N - 1)
-    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= kmax):
-        raise ValueError(f"k must be None or an int in [1, min(1024, N - 1)] = [1, {kmax}], got {k!r}")
+    _args.int_in("k", k, 1, kmax, what=f"None or an int in [1, min(1024, N - 1)] = [1, {kmax}]", optional=True)
 
 
 def _graph_arg(x, graph, k, N):
@@ -343,14 +336,7 @@ def kbet(x, batch, k: Optional[int] = None, alpha: float = 0.05, graph=None, num
     num_labels=None relabels with torch.unique; num_labels=G: the labels are 0..G-1 already.  A label without points
     leaves the sum and the degrees of freedom.  generator: also the rate under one random permutation of the labels on
     the same graph (torch.randperm on the generator's device) - the rate a cloud without batch structure would show."""
-    if graph is None:
-        neighbors._check_cloud(x)
-        N = x.shape[0]
-        if N < 2:
-            raise ValueError("at least 2 rows")
-    else:
-        neighbors._check_graph(graph)
-        N = graph.indices.shape[0]
+    N = _graph_rows(x, graph)
     lab = _graph_labels("batch", batch, num_labels, N)
     _check_k(k, N)
     if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0 < alpha < 1:
@@ -359,7 +345,7 @@ def kbet(x, batch, k: Optional[int] = None, alpha: float = 0.05, graph=None, num
         raise ValueError("generator must be None or a torch.Generator")
     if graph is None and not x.is_cuda:
         raise ValueError("kbet needs a device cloud or graph= (there is no CPU fallback for the search)")
-    lab, G = _relabel(lab, num_labels)
+    lab, G = _label_positions(lab, num_labels)
     if k is None and graph is None:
         full = int((torch.bincount(lab.clamp(0, G - 1), minlength=G) > 0).sum())
         k = min(max(10, N // max(full, 1) // 4), neighbors.MAX_K, N - 1)
@@ -401,14 +387,7 @@ def lisi_knn(x, labels, perplexity: float = 30.0, k: Optional[int] = None, graph
     -1 (LISI -1), as there.  Vectorised in f64 over [N, k] with 50 masked steps and no host read: with num_labels (labels
     already 0..G-1 on the device) a call can be captured.  graph: a KNNGraph of the cloud against itself to reuse (x is
     not read and may be None; host tensors work; a smaller k takes its first k columns).  iLISI / cLISI by the label."""
-    if graph is None:
-        neighbors._check_cloud(x)
-        N = x.shape[0]
-        if N < 2:
-            raise ValueError("at least 2 rows")
-    else:
-        neighbors._check_graph(graph)
-        N = graph.indices.shape[0]
+    N = _graph_rows(x, graph)
     lab = _graph_labels("labels", labels, num_labels, N)
     _check_lisi_knn(perplexity, k, N)
     if graph is None and not x.is_cuda:
@@ -416,7 +395,7 @@ def lisi_knn(x, labels, perplexity: float = 30.0, k: Optional[int] = None, graph
     if k is None and graph is None:
         k = int(3 * perplexity) - 1
     graph = _graph_arg(x, graph, k, N)
-    lab, G = _relabel(lab, num_labels)
+    lab, G = _label_positions(lab, num_labels)
     idx = graph.indices
     return _lisi_knn_f64(graph, lab.to(idx.device)[idx.clamp(min=0)], G, perplexity).float()
 

@@ -23,12 +23,11 @@ There is no CPU fallback; KNNGraph's own methods are torch glue that also takes 
 from __future__ import annotations
 
 import dataclasses
-import math
 from typing import Optional
 
 import torch
 
-from . import ops
+from . import _args, ops
 
 __all__ = ["KNNGraph", "knn_graph", "MAX_K", "ROUND_K"]
 
@@ -60,8 +59,7 @@ class KNNGraph:
         if not isinstance(labels, torch.Tensor) or labels.is_floating_point() or labels.dtype == torch.bool \
                 or labels.dim() != 1:
             raise TypeError("labels must be a 1-D integer tensor")
-        if isinstance(num_labels, bool) or not isinstance(num_labels, int) or num_labels < 1:
-            raise ValueError(f"num_labels must be a positive int, got {num_labels!r}")
+        _args.int_in("num_labels", num_labels, 1)
         idx = self.indices
         lab = labels.long().to(idx.device)[idx.clamp(min=0)]
         ok = (idx >= 0) & (lab >= 0) & (lab < num_labels)
@@ -69,7 +67,7 @@ class KNNGraph:
         return out.scatter_add_(1, lab.clamp(0, num_labels - 1), ok.long())
 
 
-def _check_graph(graph, rows=None):
+def check_graph(graph):
     if not isinstance(graph, KNNGraph) or not isinstance(graph.indices, torch.Tensor) \
             or not isinstance(graph.sqdist, torch.Tensor):
         raise ValueError("graph must be a KNNGraph (neighbors.knn_graph)")
@@ -77,47 +75,23 @@ def _check_graph(graph, rows=None):
     if i.dtype != torch.int64 or i.dim() != 2 or i.shape[1] == 0 or d.shape != i.shape or not d.is_floating_point() \
             or d.device != i.device:
         raise ValueError("graph must hold int64 indices [M, k] and floating sqdist [M, k] on one device")
-    if rows is not None and i.shape[0] != rows:
-        raise ValueError(f"graph has {i.shape[0]} rows for {rows} labels")
-
-
-def _check_cloud(t, name="x"):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a float32 device tensor")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32, got {t.dtype}")
-    if t.dim() != 2:
-        raise ValueError(f"{name} must be a 2-D tensor, got shape {tuple(t.shape)}")
-    if t.shape[0] == 0 or t.shape[1] == 0 or t.shape[1] % 4:
-        raise ValueError(f"{name} must be non-empty with a width that is a multiple of 4, got shape {tuple(t.shape)}")
 
 
 def _check_args(x, k, y, metric, row_block):
     """Every argument error, before any device work."""
-    _check_cloud(x)
+    _args.check_cloud(x)
     if y is not None:
-        _check_cloud(y, "y")
+        _args.check_cloud(y, "y")
     if y is not None and y.shape[1] != x.shape[1]:
         raise ValueError(f"x has {x.shape[1]} columns, y {y.shape[1]}")
-    if metric not in METRICS:
-        raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
+    _args.check_metric(metric, METRICS)
     Ny = x.shape[0] if y is None else y.shape[0]
     kmax = min(MAX_K, Ny - 1 if y is None else Ny)
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= kmax:
-        what = "min(1024, N - 1)" if y is None else "min(1024, Ny)"
-        raise ValueError(f"k must be an int in [1, {what}] = [1, {kmax}], got {k!r}")
-    if isinstance(row_block, bool) or not isinstance(row_block, int) or row_block < 1:
-        raise ValueError(f"row_block must be a positive int, got {row_block!r}")
-    if not all(t.is_cuda for t in (x, y) if t is not None):
-        raise ValueError("knn_graph needs device tensors (there is no CPU fallback)")
+    _args.int_in("k", k, 1, kmax, what=f"an int in [1, min(1024, {'N - 1' if y is None else 'Ny'})] = [1, {kmax}]")
+    _args.int_in("row_block", row_block, 1)
+    _args.need_device("knn_graph needs", x, y)
     if y is not None and y.device != x.device:
         raise ValueError(f"x is on {x.device}, y on {y.device}")
-
-
-def _prepare(t, metric):
-    """Rows whose squared distances are the metric: unit rows scaled by 1 / sqrt 2 have d = 1 - cos (manifold._prepare)."""
-    t = t.detach().contiguous()
-    return torch.nn.functional.normalize(t, dim=1) * math.sqrt(0.5) if metric == "cosine" else t
 
 
 @torch.no_grad()
@@ -131,8 +105,8 @@ def knn_graph(x, k: int, y=None, metric: str = "euclidean", row_block: int = 655
     Equally near keys (equal z = <x_i, y_j> - |y_j|^2 / 2 in f32) come in ascending index.  Rows go through in blocks of
     row_block against all of y; the result does not depend on it.  ceil(k / 64) walks; no host read - capturable."""
     _check_args(x, k, y, metric, row_block)
-    xs = _prepare(x, metric)
-    ys = xs if y is None else _prepare(y, metric)
+    xs = _args.prepare(x, metric)
+    ys = xs if y is None else _args.prepare(y, metric)
     idx = _rounds(xs, ys, k, y is None, row_block)
     return KNNGraph(idx, ops.pair_sqdist(xs, ys, idx))
 

@@ -10,7 +10,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import _ffi
+from . import _args, _ffi
 from ._ffi import ACT, BF16, F32, U8, GemmArgs, check, ptr
 
 _WS: dict = {}
@@ -708,6 +708,64 @@ def _retrieval_args(x, y):
     return Mx, Ny, P
 
 
+# ---- the shared pieces of the embedding-cloud wrappers below (sim_topk .. tsne_update)
+def _check_width(P, max_p):
+    if P <= 0 or P % 4 or P > max_p:
+        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {max_p})")
+
+
+def _cloud_args(x, y, max_p):
+    """(Mx, Ny, P) of a pair of clouds: _retrieval_args and the kernel's width limit."""
+    Mx, Ny, P = _retrieval_args(x, y)
+    _check_width(P, max_p)
+    return Mx, Ny, P
+
+
+def _device_args(who, *ts):
+    """The tensors given (None: an optional one left out) are on the current device; who: the subject and verb of the
+    ValueError a host tensor raises."""
+    _args.need_device(who, *ts)
+    _need_cuda(*ts)
+
+
+def _sq_norms(x, y, nx, ny, wanted=True):
+    """(nx, ny): the squared norms of the rows of x and y where the caller gave none; one product for a cloud with
+    itself.  wanted=False (a metric that reads no norms) leaves them as they came."""
+    if wanted:
+        if nx is None:
+            nx = (x * x).sum(1)
+        if ny is None:
+            ny = nx if y is x else (y * y).sum(1)
+    return nx, ny
+
+
+def _diag_offset(diag_offset) -> int:
+    diag_offset = int(diag_offset)
+    if diag_offset < -1:
+        raise ValueError(f"diag_offset must be -1 (nothing skipped) or >= 0, got {diag_offset}")
+    return diag_offset
+
+
+def _key_split_plan(entry, rows, Ny):
+    """(query blocks, key-range splits) that `entry`, a clipk_*_plan function, reports for these sizes."""
+    nqb, ks = C.c_int(0), C.c_int(0)
+    check(getattr(_lib(), entry)(int(rows), int(Ny), C.byref(nqb), C.byref(ks)), entry)
+    return nqb.value, ks.value
+
+
+def _launch(name, work, args, ws=None, entry=None):
+    """Enqueue clipk_<name>(*args[, workspace, its bytes], stream) on torch's current stream, timed as `name` with the
+    algorithmic `work`, and check its status.  ws = (device, tag, *the arguments of clipk_<name>_workspace): the
+    kernel's scratch, from the grow-only buffer `tag`.  entry: the function where it is not clipk_<name>."""
+    lib = _lib()
+    stream = _stream()
+    if ws is not None:
+        buf = workspace(getattr(lib, f"clipk_{name}_workspace")(*ws[2:]), ws[0], ws[1], stream)
+        args = (*args, buf.data_ptr(), buf.numel())
+    entry = "clipk_" + (entry or name)
+    check(_timed(name, work, lambda: getattr(lib, entry)(*args, stream)), entry)
+
+
 def sim_topk(x, y, k: int, scale: Optional[float] = None):
     """(scores f32 [Mx, k], idx int64 [Mx, k]): the k best keys of S = scale * x y^T per row, score descending, equal
     scores by the lower index (include/clipk.h: clipk_sim_topk).  scale: host number, None = 1."""
@@ -720,10 +778,9 @@ def sim_topk(x, y, k: int, scale: Optional[float] = None):
     _need_cuda(x, y)
     scores = torch.empty((Mx, k), dtype=torch.float32, device=x.device)
     idx = torch.empty((Mx, k), dtype=torch.int64, device=x.device)
-    lib = _lib()
-    ws = workspace(lib.clipk_sim_topk_workspace(Mx, Ny, P, k), x.device, "retrieval")
-    check(lib.clipk_sim_topk(x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale), k,
-                             scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipk_sim_topk")
+    _launch("sim_topk", 2.0 * Mx * Ny * P,
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale), k, scores.data_ptr(),
+             idx.data_ptr()), (x.device, "retrieval", Mx, Ny, P, k))
     return scores, idx
 
 
@@ -733,10 +790,8 @@ def sim_knn(x, y, k: int, scale: Optional[float] = None, bias=None, diag_offset:
     key i + diag_offset (-1: none); after = (scores f32 [Mx], idx int64 [Mx]): a cursor in the order - only keys strictly
     after it are eligible.  1 <= k <= 64; with fewer than k eligible keys the trailing slots are (-inf, -1)."""
     Mx, Ny, P = _retrieval_args(x, y)
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 64:
-        raise ValueError(f"k must be an int in [1, 64], got {k!r}")
-    if isinstance(diag_offset, bool) or not isinstance(diag_offset, int) or diag_offset < -1:
-        raise ValueError(f"diag_offset must be -1 or a non-negative int, got {diag_offset!r}")
+    _args.int_in("k", k, 1, 64)
+    _args.int_in("diag_offset", diag_offset, -1, what="-1 or a non-negative int")     # (no bool, unlike _diag_offset)
     if bias is not None and (bias.dtype != torch.float32 or bias.shape != (Ny,) or not bias.is_contiguous()):
         raise ValueError(f"bias must be a contiguous float32 tensor of shape ({Ny},)")
     after_s = after_i = None
@@ -750,11 +805,9 @@ def sim_knn(x, y, k: int, scale: Optional[float] = None, bias=None, diag_offset:
     _need_cuda(x, y, bias, after_s, after_i)
     scores = torch.empty((Mx, k), dtype=torch.float32, device=x.device)
     idx = torch.empty((Mx, k), dtype=torch.int64, device=x.device)
-    lib = _lib()
-    ws = workspace(lib.clipk_sim_knn_workspace(Mx, Ny, P, k), x.device, "retrieval")
-    check(lib.clipk_sim_knn(x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale), ptr(bias),
-                            diag_offset, ptr(after_s), ptr(after_i), k, scores.data_ptr(), idx.data_ptr(), ws.data_ptr(),
-                            ws.numel(), _stream()), "clipk_sim_knn")
+    _launch("sim_knn", 2.0 * Mx * Ny * P,
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale), ptr(bias), diag_offset,
+             ptr(after_s), ptr(after_i), k, scores.data_ptr(), idx.data_ptr()), (x.device, "retrieval", Mx, Ny, P, k))
     return scores, idx
 
 
@@ -766,8 +819,8 @@ def pair_sqdist(x, y, idx):
         raise ValueError(f"idx must be a contiguous int64 tensor of shape ({Mx}, k), k >= 1")
     _need_cuda(x, y, idx)
     d2 = torch.empty(idx.shape, dtype=torch.float32, device=x.device)
-    check(_lib().clipk_pair_sqdist(x.data_ptr(), Mx, y.data_ptr(), Ny, P, idx.data_ptr(), idx.shape[1], d2.data_ptr(),
-                                   _stream()), "clipk_pair_sqdist")
+    _launch("pair_sqdist", 3.0 * idx.numel() * P,
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, idx.data_ptr(), idx.shape[1], d2.data_ptr()))
     return d2
 
 
@@ -809,11 +862,9 @@ def csr_spmm(indptr, indices, w, x, s=None, alpha: float = 1.0, b=None, beta: fl
     N, nnz, m = _csr_spmm_args(indptr, indices, w, x, s, b, c, out)
     _need_cuda(indptr, indices, w, x, s, b, c, out)
     y = torch.empty_like(x) if out is None else out
-    lib = _lib()
-    ws = workspace(lib.clipk_csr_spmm_workspace(nnz, m), x.device, "spmm")
-    check(lib.clipk_csr_spmm_f64(indptr.data_ptr(), indices.data_ptr(), w.data_ptr(), ptr(s), N, nnz, m, x.data_ptr(),
-                                 float(alpha), ptr(b), float(beta), ptr(c), float(gamma), y.data_ptr(), ws.data_ptr(),
-                                 ws.numel(), _stream()), "clipk_csr_spmm_f64")
+    _launch("csr_spmm", 2.0 * nnz * m,
+            (indptr.data_ptr(), indices.data_ptr(), w.data_ptr(), ptr(s), N, nnz, m, x.data_ptr(), float(alpha), ptr(b),
+             float(beta), ptr(c), float(gamma), y.data_ptr()), (x.device, "spmm", nnz, m), entry="csr_spmm_f64")
     return y
 
 
@@ -836,8 +887,7 @@ def split_bf16(x, hi, lo=None, norm_max=None):
     _need_cuda(x, hi, lo, norm_max)
     if n == 0:
         return
-    check(_lib().clipk_split_bf16(x.data_ptr(), n, P, hi.data_ptr(), ptr(lo), ptr(norm_max), _stream()),
-          "clipk_split_bf16")
+    _launch("split_bf16", 0.0, (x.data_ptr(), n, P, hi.data_ptr(), ptr(lo), ptr(norm_max)))
 
 
 def sim_topk_cand(x, yhi, ylo, Ny: int, P: int, kc: int, scale: Optional[float] = None):
@@ -860,11 +910,9 @@ def sim_topk_cand(x, yhi, ylo, Ny: int, P: int, kc: int, scale: Optional[float] 
     _need_cuda(x, yhi, ylo)
     scores = torch.empty((Mx, kc), dtype=torch.float32, device=x.device)
     idx = torch.empty((Mx, kc), dtype=torch.int64, device=x.device)
-    lib = _lib()
-    ws = workspace(lib.clipk_sim_topk_cand_workspace(Mx, Ny, P, kc, 1 if ylo is None else 2), x.device, "retrieval")
-    check(lib.clipk_sim_topk_cand(x.data_ptr(), Mx, yhi.data_ptr(), ptr(ylo), Ny, P, 1.0 if scale is None else float(scale),
-                                  kc, scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-          "clipk_sim_topk_cand")
+    _launch("sim_topk_cand", 2.0 * Mx * Ny * plane_pitch(P) * (1 if ylo is None else 3),
+            (x.data_ptr(), Mx, yhi.data_ptr(), ptr(ylo), Ny, P, 1.0 if scale is None else float(scale), kc,
+             scores.data_ptr(), idx.data_ptr()), (x.device, "retrieval", Mx, Ny, P, kc, 1 if ylo is None else 2))
     return scores, idx
 
 
@@ -885,10 +933,10 @@ def sim_rerank(x, y, cand_scores, cand_idx, k: int, eps_rel: float, y_norm_max, 
     scores = torch.empty((Mx, k), dtype=torch.float32, device=x.device)
     idx = torch.empty((Mx, k), dtype=torch.int64, device=x.device)
     cert = torch.empty(Mx, dtype=torch.int32, device=x.device)
-    check(_lib().clipk_sim_rerank(x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale),
-                                  cand_idx.data_ptr(), cand_scores.data_ptr(), kc, k, float(eps_rel),
-                                  y_norm_max.data_ptr(), scores.data_ptr(), idx.data_ptr(), cert.data_ptr(), _stream()),
-          "clipk_sim_rerank")
+    _launch("sim_rerank", 2.0 * Mx * kc * P,
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale), cand_idx.data_ptr(),
+             cand_scores.data_ptr(), kc, k, float(eps_rel), y_norm_max.data_ptr(), scores.data_ptr(), idx.data_ptr(),
+             cert.data_ptr()))
     return scores, idx, cert
 
 
@@ -909,16 +957,11 @@ def sim_rank(x, y, labels=None, label_offset: int = 0, scale: Optional[float] = 
     _need_cuda(x, y, labels, class_ids)
     rank = torch.empty(Mx, dtype=torch.int64, device=x.device)
     pos = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    lib = _lib()
-    ws = workspace(lib.clipk_sim_rank_workspace(Mx, Ny, P), x.device, "retrieval")
-    sc = 1.0 if scale is None else float(scale)
-    if class_ids is None:
-        check(lib.clipk_sim_rank(x.data_ptr(), Mx, y.data_ptr(), Ny, P, sc, ptr(labels), int(label_offset),
-                                 rank.data_ptr(), pos.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipk_sim_rank")
-    else:
-        check(lib.clipk_sim_rank_cls(x.data_ptr(), Mx, y.data_ptr(), Ny, P, sc, ptr(labels), int(label_offset),
-                                     class_ids.data_ptr(), rank.data_ptr(), pos.data_ptr(), ws.data_ptr(), ws.numel(),
-                                     _stream()), "clipk_sim_rank_cls")
+    cls = () if class_ids is None else (class_ids.data_ptr(),)
+    _launch("sim_rank", 2.0 * Mx * Ny * P,
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, 1.0 if scale is None else float(scale), ptr(labels), int(label_offset),
+             *cls, rank.data_ptr(), pos.data_ptr()), (x.device, "retrieval", Mx, Ny, P),
+            entry="sim_rank_cls" if cls else None)
     return rank, pos
 
 
@@ -968,11 +1011,9 @@ def sim_stats(x, y, *, scale: float = 1.0, labels=None, label_offset: int = 0, c
     i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)
     f64 = lambda: torch.empty(Mx, dtype=torch.float64, device=dev)
     out = SimStats(f32(), f32(), i64(Mx), f32(), i64(Mx), f32(), f64(), f64(), i64(nbins + 2), i64(nbins + 2))
-    lib = _lib()
-    ws = workspace(lib.clipk_sim_stats_workspace(Mx, Ny, P, nbins), dev, "retrieval")
-    check(lib.clipk_sim_stats(x.data_ptr(), Mx, y.data_ptr(), Ny, P, sc, ptr(labels), int(label_offset), ptr(cls_x),
-                              ptr(cls_y), nbins, lo32, hi32, *(t.data_ptr() for t in out), ws.data_ptr(), ws.numel(),
-                              _stream()), "clipk_sim_stats")
+    _launch("sim_stats", 2.0 * Mx * Ny * P,
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, sc, ptr(labels), int(label_offset), ptr(cls_x), ptr(cls_y), nbins, lo32,
+             hi32, *(t.data_ptr() for t in out)), (dev, "retrieval", Mx, Ny, P, nbins))
     return out
 
 
@@ -993,24 +1034,21 @@ def _f32_vectors(vectors):
 
 def _sinkhorn_args(x, y, scale, max_p, vectors=()):
     """Operand checks of the two Sinkhorn entries, before any launch.  vectors: (name, tensor or None, length)."""
-    Mx, Ny, P = _retrieval_args(x, y)
-    if P > max_p:
-        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {max_p})")
-    if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or scale.numel() != 1:
-        raise TypeError("scale must be a one-element float32 device tensor")
+    Mx, Ny, P = _cloud_args(x, y, max_p)
+    _device_scalar("scale", scale)
     _f32_vectors(vectors)
-    for t in (x, y, scale, *(v[1] for v in vectors)):
-        if t is not None and not t.is_cuda:
-            raise ValueError("the Sinkhorn kernels need device tensors (there is no CPU fallback)")
-    _need_cuda(x, y, scale, *(v[1] for v in vectors))
+    _device_args("the Sinkhorn kernels need", x, y, scale, *(v[1] for v in vectors))
     return Mx, Ny, P
+
+
+def _device_scalar(name, t):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1:
+        raise TypeError(f"{name} must be a one-element float32 device tensor")
 
 
 def sim_lse_bias_plan(Mx: int, Ny: int):
     """(64-query blocks, key-range splits) of the grid clipk_sim_lse_bias launches for these sizes."""
-    nqb, ks = C.c_int(0), C.c_int(0)
-    check(_lib().clipk_sim_lse_bias_plan(int(Mx), int(Ny), C.byref(nqb), C.byref(ks)), "clipk_sim_lse_bias_plan")
-    return nqb.value, ks.value
+    return _key_split_plan("clipk_sim_lse_bias_plan", Mx, Ny)
 
 
 def sim_lse_bias(x, y, scale, bias=None, logw=None, prev=None, average=False, out=None, err=None):
@@ -1025,21 +1063,15 @@ def sim_lse_bias(x, y, scale, bias=None, logw=None, prev=None, average=False, ou
         raise ValueError("average=True and err need prev")
     if out is None:
         out = torch.empty(Mx, dtype=torch.float32, device=x.device)
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_sim_lse_bias_workspace(Mx, Ny, P), x.device, "sinkhorn", stream)
-    check(_timed("sim_lse_bias", 2.0 * Mx * Ny * P,
-                 lambda: lib.clipk_sim_lse_bias(x.data_ptr(), Mx, y.data_ptr(), Ny, P, scale.data_ptr(), ptr(bias), ptr(logw),
-                                                ptr(prev), int(bool(average)), out.data_ptr(), ptr(err), ws.data_ptr(),
-                                                ws.numel(), stream)), "clipk_sim_lse_bias")
+    _launch("sim_lse_bias", 2.0 * Mx * Ny * P,
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, scale.data_ptr(), ptr(bias), ptr(logw), ptr(prev), int(bool(average)),
+             out.data_ptr(), ptr(err)), (x.device, "sinkhorn", Mx, Ny, P))
     return out
 
 
 def sim_lse_bias_x3_plan(Mx: int, Ny: int):
     """(128-query blocks, key-range splits) of the grid clipk_sim_lse_bias_x3 launches for these sizes."""
-    nqb, ks = C.c_int(0), C.c_int(0)
-    check(_lib().clipk_sim_lse_bias_x3_plan(int(Mx), int(Ny), C.byref(nqb), C.byref(ks)), "clipk_sim_lse_bias_x3_plan")
-    return nqb.value, ks.value
+    return _key_split_plan("clipk_sim_lse_bias_x3_plan", Mx, Ny)
 
 
 def sim_lse_bias_x3(xhi, xlo, yhi, ylo, P: int, scale, bias=None, logw=None, prev=None, average=False, out=None, err=None):
@@ -1048,8 +1080,7 @@ def sim_lse_bias_x3(xhi, xlo, yhi, ylo, P: int, scale, bias=None, logw=None, pre
     yhi / ylo [Ny, plane_pitch(P)]: the planes split_bf16 writes for the two clouds of width P.  Everything else as in
     sim_lse_bias; |nv - sim_lse_bias's| <= |scale| max|x| max|y| retrieval.prefilter_eps_rel(P, "bf16x3") + eps_abs."""
     P = int(P)
-    if P <= 0 or P % 4 or P > SIM_LSE_BIAS_MAX_P:
-        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {SIM_LSE_BIAS_MAX_P})")
+    _check_width(P, SIM_LSE_BIAS_MAX_P)
     for name, t in (("xhi", xhi), ("xlo", xlo), ("yhi", yhi), ("ylo", ylo)):
         if not isinstance(t, torch.Tensor) or t.element_size() != 2:
             raise TypeError(f"{name} must be a 2-byte (bf16) plane tensor")
@@ -1059,28 +1090,18 @@ def sim_lse_bias_x3(xhi, xlo, yhi, ylo, P: int, scale, bias=None, logw=None, pre
     if xlo.shape != xhi.shape or ylo.shape != yhi.shape:
         raise ValueError("the hi and lo planes of a cloud must have one shape")
     Mx, Ny = xhi.shape[0], yhi.shape[0]
-    if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or scale.numel() != 1:
-        raise TypeError("scale must be a one-element float32 device tensor")
+    _device_scalar("scale", scale)
     vectors = (("bias", bias, Ny), ("logw", logw, Mx), ("prev", prev, Mx), ("out", out, Mx),
                ("err", None if err is None else err.reshape(-1), 1))
     _f32_vectors(vectors)
     if (average or err is not None) and prev is None:
         raise ValueError("average=True and err need prev")
-    tensors = (xhi, xlo, yhi, ylo, scale, *(v[1] for v in vectors))
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise ValueError("the Sinkhorn kernels need device tensors (there is no CPU fallback)")
-    _need_cuda(*tensors)
+    _device_args("the Sinkhorn kernels need", xhi, xlo, yhi, ylo, scale, *(v[1] for v in vectors))
     if out is None:
         out = torch.empty(Mx, dtype=torch.float32, device=xhi.device)
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_sim_lse_bias_x3_workspace(Mx, Ny, P), xhi.device, "sinkhorn", stream)
-    check(_timed("sim_lse_bias_x3", 6.0 * Mx * Ny * plane_pitch(P),
-                 lambda: lib.clipk_sim_lse_bias_x3(xhi.data_ptr(), xlo.data_ptr(), Mx, yhi.data_ptr(), ylo.data_ptr(), Ny, P,
-                                                   scale.data_ptr(), ptr(bias), ptr(logw), ptr(prev), int(bool(average)),
-                                                   out.data_ptr(), ptr(err), ws.data_ptr(), ws.numel(), stream)),
-          "clipk_sim_lse_bias_x3")
+    _launch("sim_lse_bias_x3", 6.0 * Mx * Ny * plane_pitch(P),
+            (xhi.data_ptr(), xlo.data_ptr(), Mx, yhi.data_ptr(), ylo.data_ptr(), Ny, P, scale.data_ptr(), ptr(bias),
+             ptr(logw), ptr(prev), int(bool(average)), out.data_ptr(), ptr(err)), (xhi.device, "sinkhorn", Mx, Ny, P))
     return out
 
 
@@ -1100,13 +1121,9 @@ def sinkhorn_apply(x, y, scale, u, v, nx=None, ny=None, want_mass=True, want_bar
     mass = torch.empty(Mx, dtype=torch.float32, device=dev) if want_mass else None
     bary = torch.empty((Mx, P), dtype=torch.float32, device=dev) if want_bary else None
     cost = torch.empty(Mx, dtype=torch.float32, device=dev) if want_cost else None
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_sinkhorn_apply_workspace(Mx, Ny, P), dev, "sinkhorn", stream)
-    check(_timed("sinkhorn_apply", 2.0 * Mx * Ny * P * (2 if want_bary else 1),
-                 lambda: lib.clipk_sinkhorn_apply(x.data_ptr(), Mx, y.data_ptr(), Ny, P, scale.data_ptr(), u.data_ptr(),
-                                                  v.data_ptr(), ptr(nx), ptr(ny), ptr(mass), ptr(bary), ptr(cost),
-                                                  ws.data_ptr(), ws.numel(), stream)), "clipk_sinkhorn_apply")
+    _launch("sinkhorn_apply", 2.0 * Mx * Ny * P * (2 if want_bary else 1),
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, scale.data_ptr(), u.data_ptr(), v.data_ptr(), ptr(nx), ptr(ny),
+             ptr(mass), ptr(bary), ptr(cost)), (dev, "sinkhorn", Mx, Ny, P))
     return mass, bary, cost
 
 
@@ -1137,19 +1154,13 @@ def sim_sample(x, y, scale, bias=None, seed=0, stream_offset=0, want_score=False
     _seed_offset(seed, stream_offset)
     Mx, Ny, P = _sinkhorn_args(x, y, scale, SIM_LSE_BIAS_MAX_P, (("bias", bias, y.shape[0]),))
     if isinstance(seed, torch.Tensor):
-        if not seed.is_cuda:
-            raise ValueError("the Sinkhorn kernels need device tensors (there is no CPU fallback)")
-        _need_cuda(x, seed)
+        _device_args("the Sinkhorn kernels need", x, seed)
     so = _seed_offset(seed, stream_offset, x.device)
     idx = torch.empty(Mx, dtype=torch.int64, device=x.device)
     score = torch.empty(Mx, dtype=torch.float32, device=x.device) if want_score else None
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_sim_sample_workspace(Mx, Ny, P), x.device, "sinkhorn", stream)
-    check(_timed("sim_sample", 2.0 * Mx * Ny * P,
-                 lambda: lib.clipk_sim_sample(x.data_ptr(), Mx, y.data_ptr(), Ny, P, scale.data_ptr(), ptr(bias),
-                                              so.data_ptr(), idx.data_ptr(), ptr(score), ws.data_ptr(), ws.numel(),
-                                              stream)), "clipk_sim_sample")
+    _launch("sim_sample", 2.0 * Mx * Ny * P,
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, scale.data_ptr(), ptr(bias), so.data_ptr(), idx.data_ptr(), ptr(score)),
+            (x.device, "sinkhorn", Mx, Ny, P))
     return (idx, score) if want_score else idx
 
 
@@ -1167,9 +1178,7 @@ def _int32_vector(name, t, n, device):
 
 def sim_top2_bias_plan(Mr: int, Ny: int):
     """(64-query blocks, key-range splits) of the grid clipk_sim_top2_bias launches for Mr listed rows and Ny keys."""
-    nqb, ks = C.c_int(0), C.c_int(0)
-    check(_lib().clipk_sim_top2_bias_plan(int(Mr), int(Ny), C.byref(nqb), C.byref(ks)), "clipk_sim_top2_bias_plan")
-    return nqb.value, ks.value
+    return _key_split_plan("clipk_sim_top2_bias_plan", Mr, Ny)
 
 
 def sim_top2_bias(x, y, scale, bias=None, rows=None, n_active=None, want_best=True, want_gap=True, out=None):
@@ -1202,14 +1211,9 @@ def sim_top2_bias(x, y, scale, bias=None, rows=None, n_active=None, want_best=Tr
         idx = torch.empty(Mr, dtype=torch.int32, device=dev)
         best = torch.empty(Mr, dtype=torch.float32, device=dev) if want_best else None
         gap = torch.empty(Mr, dtype=torch.float32, device=dev) if want_gap else None
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_sim_top2_bias_workspace(Mr, Ny, P), dev, "sinkhorn", stream)
-    check(_timed("sim_top2_bias", 2.0 * Mr * Ny * P,
-                 lambda: lib.clipk_sim_top2_bias(x.data_ptr(), Mx, ptr(rows), Mr, ptr(n_active), y.data_ptr(), Ny, P,
-                                                 scale.data_ptr(), ptr(bias), idx.data_ptr(),
-                                                 ptr(best) if want_best else None, ptr(gap) if want_gap else None,
-                                                 ws.data_ptr(), ws.numel(), stream)), "clipk_sim_top2_bias")
+    _launch("sim_top2_bias", 2.0 * Mr * Ny * P,
+            (x.data_ptr(), Mx, ptr(rows), Mr, ptr(n_active), y.data_ptr(), Ny, P, scale.data_ptr(), ptr(bias), idx.data_ptr(),
+             ptr(best) if want_best else None, ptr(gap) if want_gap else None), (dev, "sinkhorn", Mr, Ny, P))
     return idx, (best if want_best else None), (gap if want_gap else None)
 
 
@@ -1219,10 +1223,8 @@ def auction_rounds(x, y, bias, eps, assigned, owner, n_unassigned, stalled, n_ro
     owner [N] int32 (key -> row or -1) are updated in place; eps: one-element f32 device tensor; n_unassigned, stalled:
     one-element int32 device tensors - the count after the last round, and a flag set (never cleared) when an offer left
     a price unchanged.  n_rounds = 0 only counts.  Returns None."""
-    if isinstance(n_rounds, bool) or not isinstance(n_rounds, int) or n_rounds < 0:
-        raise ValueError(f"n_rounds must be a non-negative int, got {n_rounds!r}")
-    if not isinstance(eps, torch.Tensor) or eps.dtype != torch.float32 or eps.numel() != 1:
-        raise TypeError("eps must be a one-element float32 device tensor")
+    _args.int_in("n_rounds", n_rounds, 0, what="a non-negative int")
+    _device_scalar("eps", eps)
     N, Ny, P = _retrieval_args(x, y)
     if bias is None:
         raise ValueError("bias is needed")
@@ -1233,14 +1235,9 @@ def auction_rounds(x, y, bias, eps, assigned, owner, n_unassigned, stalled, n_ro
     for name, t, n in (("assigned", assigned, N), ("owner", owner, N), ("n_unassigned", n_unassigned, 1), ("stalled", stalled, 1)):
         _int32_vector(name, t, n, x.device)
     _sinkhorn_args(x, y, eps, SIM_LSE_BIAS_MAX_P, (("bias", bias, N),))
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_auction_rounds_workspace(N, P), x.device, "sinkhorn", stream)
-    check(_timed("auction_rounds", 2.0 * N * N * P,
-                 lambda: lib.clipk_auction_rounds(x.data_ptr(), y.data_ptr(), N, P, bias.data_ptr(), eps.data_ptr(),
-                                                  assigned.data_ptr(), owner.data_ptr(), n_unassigned.data_ptr(),
-                                                  stalled.data_ptr(), n_rounds, ws.data_ptr(), ws.numel(), stream)),
-          "clipk_auction_rounds")
+    _launch("auction_rounds", 2.0 * N * N * P,
+            (x.data_ptr(), y.data_ptr(), N, P, bias.data_ptr(), eps.data_ptr(), assigned.data_ptr(), owner.data_ptr(),
+             n_unassigned.data_ptr(), stalled.data_ptr(), n_rounds), (x.device, "sinkhorn", N, P))
 
 
 KERNEL_SUMS_MAX_P = 512        # clipk_kernel_sums
@@ -1258,9 +1255,7 @@ def kernel_sums(x, y, gammas, weights, nx=None, ny=None, diag_offset=-1, want_su
     for an output not wanted.  gammas, weights: f32 device vectors of B <= 8 entries, read by the kernel.  nx, ny: the
     squared norms, computed here when not given.  diag_offset >= 0: row i skips key i + diag_offset (0 for a cloud with
     itself); -1: nothing is skipped."""
-    Mx, Ny, P = _retrieval_args(x, y)
-    if P > KERNEL_SUMS_MAX_P:
-        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {KERNEL_SUMS_MAX_P})")
+    Mx, Ny, P = _cloud_args(x, y, KERNEL_SUMS_MAX_P)
     for name, t in (("gammas", gammas), ("weights", weights)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
             raise TypeError(f"{name} must be a float32 device tensor")
@@ -1271,29 +1266,17 @@ def kernel_sums(x, y, gammas, weights, nx=None, ny=None, diag_offset=-1, want_su
         raise ValueError(f"gammas and weights must have the same 1..{KERNEL_SUMS_MAX_B} entries, got {B} and "
                          f"{weights.shape[0]}")
     _f32_vectors((("nx", nx, Mx), ("ny", ny, Ny)))
-    diag_offset = int(diag_offset)
-    if diag_offset < -1:
-        raise ValueError(f"diag_offset must be -1 (nothing skipped) or >= 0, got {diag_offset}")
+    diag_offset = _diag_offset(diag_offset)
     if not (want_sum or want_bary):
         raise ValueError("no output wanted")
-    for t in (x, y, gammas, weights, nx, ny):
-        if t is not None and not t.is_cuda:
-            raise ValueError("the kernel-sum kernel needs device tensors (there is no CPU fallback)")
-    _need_cuda(x, y, gammas, weights, nx, ny)
-    if nx is None:
-        nx = (x * x).sum(1)
-    if ny is None:
-        ny = nx if y is x else (y * y).sum(1)
+    _device_args("the kernel-sum kernel needs", x, y, gammas, weights, nx, ny)
+    nx, ny = _sq_norms(x, y, nx, ny)
     dev = x.device
     ksum = torch.empty(Mx, dtype=torch.float32, device=dev) if want_sum else None
     kbary = torch.empty((Mx, P), dtype=torch.float32, device=dev) if want_bary else None
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_kernel_sums_workspace(Mx, Ny, P, B), dev, "kernel_sums", stream)
-    check(_timed("kernel_sums", 2.0 * Mx * Ny * P * (2 if want_bary else 1),
-                 lambda: lib.clipk_kernel_sums(x.data_ptr(), Mx, y.data_ptr(), Ny, P, gammas.data_ptr(), weights.data_ptr(),
-                                               B, nx.data_ptr(), ny.data_ptr(), diag_offset, ptr(ksum), ptr(kbary),
-                                               ws.data_ptr(), ws.numel(), stream)), "clipk_kernel_sums")
+    _launch("kernel_sums", 2.0 * Mx * Ny * P * (2 if want_bary else 1),
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, gammas.data_ptr(), weights.data_ptr(), B, nx.data_ptr(), ny.data_ptr(),
+             diag_offset, ptr(ksum), ptr(kbary)), (dev, "kernel_sums", Mx, Ny, P, B))
     return ksum, kbary
 
 
@@ -1315,9 +1298,7 @@ def kmeans_step(x, c, nc=None, labels=None):
     zeros for the cosine form).  labels=None (K <= 64): labels[i] = argmax_c 2 <x_i, c_c> - nc[c] with equal scores to
     the lower c, best[i] = that maximum, sums / counts of those labels - one launch.  labels int32 [N] (K <= 65536): sums
     and counts of the given labels; the labels are returned as they came and best is None."""
-    N, K, P = _retrieval_args(x, c)
-    if P > KMEANS_MAX_P:
-        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {KMEANS_MAX_P})")
+    N, K, P = _cloud_args(x, c, KMEANS_MAX_P)
     if N > KMEANS_MAX_N:
         raise ValueError(f"N = {N} is outside the kernel's limit (N <= {KMEANS_MAX_N})")
     kmax = KMEANS_MAX_K_FUSED if labels is None else KMEANS_MAX_K
@@ -1327,10 +1308,7 @@ def kmeans_step(x, c, nc=None, labels=None):
     _f32_vectors((("nc", nc, K),))
     if labels is not None:
         _int32_vector("labels", labels, N, x.device)
-    for t in (x, c, nc, labels):
-        if t is not None and not t.is_cuda:
-            raise ValueError("the k-means kernel needs device tensors (there is no CPU fallback)")
-    _need_cuda(x, c, nc, labels)
+    _device_args("the k-means kernel needs", x, c, nc, labels)
     dev = x.device
     fused = labels is None
     if fused:
@@ -1342,14 +1320,9 @@ def kmeans_step(x, c, nc=None, labels=None):
         best = None
     sums = torch.empty((K, P), dtype=torch.float32, device=dev)
     counts = torch.empty(K, dtype=torch.float32, device=dev)
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_kmeans_step_workspace(N, K, P), dev, "kmeans", stream)
-    check(_timed("kmeans_step", 2.0 * N * min(K, 64) * P * (2 if fused else 1),
-                 lambda: lib.clipk_kmeans_step(x.data_ptr(), N, c.data_ptr(), K, P, ptr(nc) if fused else None,
-                                               None if fused else labels.data_ptr(), labels.data_ptr() if fused else None,
-                                               ptr(best), sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               stream)), "clipk_kmeans_step")
+    _launch("kmeans_step", 2.0 * N * min(K, 64) * P * (2 if fused else 1),
+            (x.data_ptr(), N, c.data_ptr(), K, P, ptr(nc) if fused else None, None if fused else labels.data_ptr(),
+             labels.data_ptr() if fused else None, ptr(best), sums.data_ptr(), counts.data_ptr()), (dev, "kmeans", N, K, P))
     return labels, best, sums, counts
 
 
@@ -1372,46 +1345,25 @@ def label_dist_sums(x, y, labels, n_labels, metric="euclidean", nx=None, ny=None
     the squared norms, computed here when not given.  diag_offset >= 0: row i skips key i + diag_offset (0 for a cloud
     with itself, r0 for its rows [r0, r1) against the whole cloud); -1: nothing is skipped.
     n_labels > 512 (up to 65536) runs in 512-label blocks, and EACH BLOCK IS A FULL WALK over the Mx x Ny tiles."""
-    Mx, Ny, P = _retrieval_args(x, y)
-    if P > LABEL_DIST_MAX_P:
-        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {LABEL_DIST_MAX_P})")
-    if metric not in LABEL_DIST_METRICS:
-        raise ValueError(f"metric must be one of {LABEL_DIST_METRICS}, got {metric!r}")
-    if isinstance(n_labels, bool) or not isinstance(n_labels, int):
-        raise TypeError(f"n_labels must be an int, got {n_labels!r}")
-    if not 1 <= n_labels <= LABEL_DIST_MAX_LABELS:
-        raise ValueError(f"n_labels must be in [1, {LABEL_DIST_MAX_LABELS}], got {n_labels}")
-    if not isinstance(labels, torch.Tensor):
-        raise TypeError("labels must be an int32 tensor")
+    Mx, Ny, P = _cloud_args(x, y, LABEL_DIST_MAX_P)
+    _args.check_metric(metric, LABEL_DIST_METRICS)
+    _args.int_in("n_labels", n_labels, 1, LABEL_DIST_MAX_LABELS, what=f"in [1, {LABEL_DIST_MAX_LABELS}]", type_error=True)
     _int32_vector("labels", labels, Ny, x.device)
     _f32_vectors((("nx", nx, Mx), ("ny", ny, Ny)))
-    diag_offset = int(diag_offset)
-    if diag_offset < -1:
-        raise ValueError(f"diag_offset must be -1 (nothing skipped) or >= 0, got {diag_offset}")
-    for t in (x, y, labels, nx, ny):
-        if t is not None and not t.is_cuda:
-            raise ValueError("the label-distance kernel needs device tensors (there is no CPU fallback)")
-    _need_cuda(x, y, labels, nx, ny)
+    diag_offset = _diag_offset(diag_offset)
+    _device_args("the label-distance kernel needs", x, y, labels, nx, ny)
     mode = LABEL_DIST_METRICS.index(metric)
-    if metric != "cosine":
-        if nx is None:
-            nx = (x * x).sum(1)
-        if ny is None:
-            ny = nx if y is x else (y * y).sum(1)
+    nx, ny = _sq_norms(x, y, nx, ny, wanted=metric != "cosine")
     dev = x.device
-    lib = _lib()
-    stream = _stream()
     blocks = []
     for g0 in range(0, n_labels, LABEL_DIST_MAX_G):
         G = min(LABEL_DIST_MAX_G, n_labels - g0)
         Gp = (G + 3) // 4 * 4
         lab = labels if g0 == 0 else labels - g0                 # the block's labels as its columns 0 .. G - 1
         out = torch.empty((Mx, Gp), dtype=torch.float32, device=dev)
-        ws = workspace(lib.clipk_label_dist_sums_workspace(Mx, Ny, P, G), dev, "label_dist", stream)
-        check(_timed("label_dist_sums", 2.0 * Mx * Ny * (P + Gp),
-                     lambda: lib.clipk_label_dist_sums(x.data_ptr(), Mx, y.data_ptr(), Ny, P, lab.data_ptr(), G, mode,
-                                                       ptr(nx), ptr(ny), diag_offset, out.data_ptr(), ws.data_ptr(),
-                                                       ws.numel(), stream)), "clipk_label_dist_sums")
+        _launch("label_dist_sums", 2.0 * Mx * Ny * (P + Gp),
+                (x.data_ptr(), Mx, y.data_ptr(), Ny, P, lab.data_ptr(), G, mode, ptr(nx), ptr(ny), diag_offset,
+                 out.data_ptr()), (dev, "label_dist", Mx, Ny, P, G))
         blocks.append(out if Gp == G else out[:, :G])
     return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
 
@@ -1426,43 +1378,26 @@ def label_kernel_sums(x, y, labels, n_labels, beta, shift=None, nx=None, ny=None
     outside [0, n_labels) belongs to no column), n_labels <= 512: ONE walk - a caller with more labels walks once per
     512 and merges.  beta f32 [Mx] > 0 per row, shift f32 [Mx] or None (zeros); nx, ny: the squared norms, computed here
     when not given.  diag_offset as in label_dist_sums.  ops.cond_entropy_sums_plan reports the grid for Mx = Ny."""
-    Mx, Ny, P = _retrieval_args(x, y)
-    if P > LABEL_DIST_MAX_P:
-        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {LABEL_DIST_MAX_P})")
-    if isinstance(n_labels, bool) or not isinstance(n_labels, int):
-        raise TypeError(f"n_labels must be an int, got {n_labels!r}")
-    if not 1 <= n_labels <= LABEL_DIST_MAX_G:
-        raise ValueError(f"n_labels must be in [1, {LABEL_DIST_MAX_G}], got {n_labels}")
+    Mx, Ny, P = _cloud_args(x, y, LABEL_DIST_MAX_P)
+    _args.int_in("n_labels", n_labels, 1, LABEL_DIST_MAX_G, what=f"in [1, {LABEL_DIST_MAX_G}]", type_error=True)
     if not (want_out or want_stats):
         raise ValueError("neither out nor the row statistics wanted")
-    if not isinstance(labels, torch.Tensor):
-        raise TypeError("labels must be an int32 tensor")
     _int32_vector("labels", labels, Ny, x.device)
     if beta is None:
         raise TypeError("beta must be a float32 device tensor")
     _f32_vectors((("beta", beta, Mx), ("shift", shift, Mx), ("nx", nx, Mx), ("ny", ny, Ny)))
     diag_offset = _diag_offset(diag_offset)
-    for t in (x, y, labels, beta, shift, nx, ny):
-        if t is not None and not t.is_cuda:
-            raise ValueError("the label-kernel walk needs device tensors (there is no CPU fallback)")
-    _need_cuda(x, y, labels, beta, shift, nx, ny)
-    if nx is None:
-        nx = (x * x).sum(1)
-    if ny is None:
-        ny = nx if y is x else (y * y).sum(1)
+    _device_args("the label-kernel walk needs", x, y, labels, beta, shift, nx, ny)
+    nx, ny = _sq_norms(x, y, nx, ny)
     dev = x.device
     G, Gp = n_labels, (n_labels + 3) // 4 * 4
     out = torch.empty((Mx, Gp), dtype=torch.float32, device=dev) if want_out else None
     mass, sumsq, best = (torch.empty(Mx, dtype=torch.float32, device=dev) if want_stats else None for _ in range(3))
     top = torch.empty(Mx, dtype=torch.int32, device=dev) if want_stats else None
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_label_kernel_sums_workspace(Mx, Ny, P, G), dev, "label_dist", stream)
-    check(_timed("label_kernel_sums", 2.0 * Mx * Ny * (P + Gp),
-                 lambda: lib.clipk_label_kernel_sums(x.data_ptr(), Mx, y.data_ptr(), Ny, P, labels.data_ptr(), G,
-                                                     beta.data_ptr(), ptr(shift), nx.data_ptr(), ny.data_ptr(), diag_offset,
-                                                     ptr(out), ptr(mass), ptr(sumsq), ptr(top), ptr(best), ws.data_ptr(),
-                                                     ws.numel(), stream)), "clipk_label_kernel_sums")
+    _launch("label_kernel_sums", 2.0 * Mx * Ny * (P + Gp),
+            (x.data_ptr(), Mx, y.data_ptr(), Ny, P, labels.data_ptr(), G, beta.data_ptr(), ptr(shift), nx.data_ptr(),
+             ny.data_ptr(), diag_offset, ptr(out), ptr(mass), ptr(sumsq), ptr(top), ptr(best)),
+            (dev, "label_dist", Mx, Ny, P, G))
     if want_out and Gp != G:
         out = out[:, :G]
     return out, mass, sumsq, top, best
@@ -1485,17 +1420,11 @@ def tsne_grad_plan(N: int):
 
 def _tsne_cloud(x, vectors, others=()):
     """Operand checks of the t-SNE walks, before any launch.  vectors: (name, tensor or None, length)."""
-    N, _, P = _retrieval_args(x, x)
-    if P > TSNE_MAX_P:
-        raise ValueError(f"P = {P} is outside the kernel's limit (P % 4 == 0, P <= {TSNE_MAX_P})")
+    N, _, P = _cloud_args(x, x, TSNE_MAX_P)
     if N < TSNE_MIN_N:
         raise ValueError(f"N = {N} is outside the kernel's limit (N >= {TSNE_MIN_N})")
     _f32_vectors(vectors)
-    ts = (x, *(v[1] for v in vectors), *others)
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise ValueError("the t-SNE kernels need device tensors (there is no CPU fallback)")
-    _need_cuda(*ts)
+    _device_args("the t-SNE kernels need", x, *(v[1] for v in vectors), *others)
     return N, P
 
 
@@ -1504,13 +1433,6 @@ def _f32_matrix(name, t, shape):
         raise TypeError(f"{name} must be a float32 device tensor")
     if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"{name} must be a contiguous tensor of shape {tuple(shape)}, got {tuple(t.shape)}")
-
-
-def _diag_offset(diag_offset) -> int:
-    diag_offset = int(diag_offset)
-    if diag_offset < -1:
-        raise ValueError(f"diag_offset must be -1 (nothing skipped) or >= 0, got {diag_offset}")
-    return diag_offset
 
 
 def cond_entropy_sums(x, betas=None, shift=None, nx=None, diag_offset=0, want_min=False, want_s0=True, want_s1=True):
@@ -1533,19 +1455,14 @@ def cond_entropy_sums(x, betas=None, shift=None, nx=None, diag_offset=0, want_mi
             raise ValueError("betas given but neither s0 nor s1 wanted")
     N, P = _tsne_cloud(x, (("shift", shift, x.shape[0]), ("nx", nx, x.shape[0])), (betas,))
     diag_offset = _diag_offset(diag_offset)
-    if nx is None:
-        nx = (x * x).sum(1)
+    nx = _sq_norms(x, x, nx, nx)[0]
     dev = x.device
     dmin = torch.empty(N, dtype=torch.float32, device=dev) if want_min else None
     s0 = torch.empty((N, B), dtype=torch.float32, device=dev) if want_s0 else None
     s1 = torch.empty((N, B), dtype=torch.float32, device=dev) if want_s1 else None
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_cond_entropy_sums_workspace(N, P, B), dev, "tsne", stream)
-    check(_timed("cond_entropy_sums", 2.0 * N * N * P,
-                 lambda: lib.clipk_cond_entropy_sums(x.data_ptr(), N, P, nx.data_ptr(), ptr(betas), B, ptr(shift),
-                                                     diag_offset, ptr(dmin), ptr(s0), ptr(s1), ws.data_ptr(), ws.numel(),
-                                                     stream)), "clipk_cond_entropy_sums")
+    _launch("cond_entropy_sums", 2.0 * N * N * P,
+            (x.data_ptr(), N, P, nx.data_ptr(), ptr(betas), B, ptr(shift), diag_offset, ptr(dmin), ptr(s0), ptr(s1)),
+            (dev, "tsne", N, P, B))
     return dmin, s0, s1
 
 
@@ -1563,16 +1480,11 @@ def tsne_grad(x, y, beta, dmin, log_s0, nx=None, diag_offset=0, want_kl=False, o
     if out is not None:
         _f32_matrix("out", out, (N, nc))
     diag_offset = _diag_offset(diag_offset)
-    if nx is None:
-        nx = (x * x).sum(1)
+    nx = _sq_norms(x, x, nx, nx)[0]
     rows = torch.empty((N, nc), dtype=torch.float32, device=x.device) if out is None else out
-    lib = _lib()
-    stream = _stream()
-    ws = workspace(lib.clipk_tsne_grad_workspace(N, P, int(want_kl)), x.device, "tsne", stream)
-    check(_timed("tsne_grad", 2.0 * N * N * P,
-                 lambda: lib.clipk_tsne_grad(x.data_ptr(), N, P, nx.data_ptr(), beta.data_ptr(), dmin.data_ptr(),
-                                             log_s0.data_ptr(), y.data_ptr(), diag_offset, int(want_kl), rows.data_ptr(),
-                                             ws.data_ptr(), ws.numel(), stream)), "clipk_tsne_grad")
+    _launch("tsne_grad", 2.0 * N * N * P,
+            (x.data_ptr(), N, P, nx.data_ptr(), beta.data_ptr(), dmin.data_ptr(), log_s0.data_ptr(), y.data_ptr(),
+             diag_offset, int(want_kl), rows.data_ptr()), (x.device, "tsne", N, P, int(want_kl)))
     return rows
 
 
@@ -1594,22 +1506,16 @@ def tsne_update(rows, y=None, update=None, gains=None, alpha=1.0, momentum=0.8, 
     if any(t is not None for t in state):
         for name, t in zip(("y", "update", "gains"), state):
             _f32_matrix(name, t, (N, 2))
-    for t in (rows, *state, z):
-        if t is not None and not t.is_cuda:
-            raise ValueError("the t-SNE kernels need device tensors (there is no CPU fallback)")
-    _need_cuda(rows, *state, z)
+    _device_args("the t-SNE kernels need", rows, *state, z)
     dev = rows.device
     if z is None:
         z = torch.empty((), dtype=torch.float32, device=dev)
-    elif z.dtype != torch.float32 or z.numel() != 1:
-        raise TypeError("z must be a one-element float32 device tensor")
+    else:
+        _device_scalar("z", z)
     kl = torch.empty((), dtype=torch.float32, device=dev) if want_kl else None
     gnorm = torch.empty((), dtype=torch.float32, device=dev) if want_gnorm else None
-    lib = _lib()
-    check(_timed("tsne_update", 0.0,
-                 lambda: lib.clipk_tsne_update(rows.data_ptr(), N, nc, float(alpha), float(momentum), float(lr), ptr(y),
-                                               ptr(update), ptr(gains), z.data_ptr(), ptr(kl), ptr(gnorm), _stream())),
-          "clipk_tsne_update")
+    _launch("tsne_update", 0.0, (rows.data_ptr(), N, nc, float(alpha), float(momentum), float(lr), ptr(y), ptr(update),
+                                 ptr(gains), z.data_ptr(), ptr(kl), ptr(gnorm)))
     return z, kl, gnorm
 
 
