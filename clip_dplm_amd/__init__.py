@@ -48,6 +48,8 @@ from .neighbors import KNNGraph, knn_graph
 from . import neighbors
 from .diffusion import DiffusionMap, SymGraph, connectivities, diffusion_map, dpt, pseudotime, pseudotime_preservation
 from . import diffusion
+from .paga import PAGAPreservation, PAGAResult, connectivities_tree, group_edge_counts, modularity, paga_preservation
+from . import paga              # the module: its function of the same name is paga.paga
 
 __all__ = [
     "HybridCLIPConfig", "ModelArchitectureConfig", "TrainingConfig", "SubConfig",
@@ -74,4 +76,5 @@ __all__ = [
     "mixing", "lisi", "label_masses", "LabelMasses", "label_transfer", "label_transfer_accuracy", "integration_scores",
     "kbet", "KBETResult", "lisi_knn", "neighbors", "knn_graph", "KNNGraph",
     "diffusion", "connectivities", "diffusion_map", "pseudotime", "dpt", "pseudotime_preservation", "SymGraph", "DiffusionMap",
+    "paga", "group_edge_counts", "connectivities_tree", "modularity", "paga_preservation", "PAGAResult", "PAGAPreservation",
 ]

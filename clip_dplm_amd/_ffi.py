@@ -92,6 +92,7 @@ SIGNATURES = {
     "clipk_csr_spmm_workspace": (_sz, [C.c_longlong, _i]),
     "clipk_csr_spmm_f64": (_i, [_vp, _vp, _vp, _vp, _i, C.c_longlong, _i, _vp, C.c_double, _vp, C.c_double, _vp, C.c_double,
                                 _vp, _vp, _sz, _vp]),
+    "clipk_knn_label_pairs": (_i, [_vp, C.c_longlong, _i, _vp, _vp, C.c_longlong, _i, _vp, _vp]),
     "clipk_sim_rank_workspace": (_sz, [_i, _i, _i]),
     "clipk_sim_rank": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "clipk_sim_rank_cls": (_i, [_vp, _i, _vp, _i, _i, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -868,6 +868,45 @@ def csr_spmm(indptr, indices, w, x, s=None, alpha: float = 1.0, b=None, beta: fl
     return y
 
 
+LABEL_PAIRS_MAX_G = 1024      # CLIPK_LABEL_PAIRS_MAX_G: an int64 table of at most 8 MB
+LABEL_PAIRS_MAX_K = 1024
+
+
+def _knn_label_pairs_args(idx, row_labels, num_groups, key_labels, out):
+    """(M, k, Ny, G) after every argument check of knn_label_pairs that needs no device."""
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] == 0 \
+            or not 1 <= idx.shape[1] <= LABEL_PAIRS_MAX_K or not idx.is_contiguous():
+        raise ValueError(f"idx must be a contiguous int64 tensor of shape (M, k), M >= 1, 1 <= k <= {LABEL_PAIRS_MAX_K}")
+    _args.int_in("num_groups", num_groups, 1, LABEL_PAIRS_MAX_G)
+    M, k = idx.shape
+    for name, t, n in (("row_labels", row_labels, M), ("key_labels", key_labels, None)):
+        if name == "key_labels" and t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] == 0 \
+                or (n is not None and t.shape[0] != n) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({'Ny' if n is None else n},)")
+    G = num_groups
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or out.shape != (G, G)
+                            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous int64 tensor of shape ({G}, {G})")
+    return M, k, (M if key_labels is None else key_labels.shape[0]), G
+
+
+def knn_label_pairs(idx, row_labels, num_groups: int, key_labels=None, out=None):
+    """int64 [G, G]: counts[a, b] = how many entries idx[i, t] have row_labels[i] = a and key_labels[idx[i, t]] = b, in one
+    pass over the indices (include/clipk.h: clipk_knn_label_pairs).  idx int64 [M, k], k <= 1024; row_labels int32 [M];
+    key_labels int32 [Ny] or None (the row labels: a graph of a cloud against itself); 1 <= num_groups <= 1024.  A label
+    outside [0, G) and an index outside [0, Ny) count nowhere.  out: an int64 [G, G] table that is ADDED into; None
+    allocates zeros.  Exact integer counts; no host read."""
+    M, k, Ny, G = _knn_label_pairs_args(idx, row_labels, num_groups, key_labels, out)
+    _need_cuda(idx, row_labels, key_labels, out)
+    counts = torch.zeros((G, G), dtype=torch.int64, device=idx.device) if out is None else out
+    keys = row_labels if key_labels is None else key_labels
+    _launch("knn_label_pairs", float(idx.numel()),
+            (idx.data_ptr(), M, k, row_labels.data_ptr(), keys.data_ptr(), Ny, G, counts.data_ptr()))
+    return counts
+
+
 def plane_pitch(P: int) -> int:
     """Row pitch (bf16 elements) of the planes clipk_split_bf16 writes: P rounded up to 32, pads zero."""
     return (int(P) + 31) // 32 * 32

@@ -1228,6 +1228,30 @@ int clipk_csr_spmm_f64(const int64_t* indptr /*[N+1]*/, const int32_t* indices /
                        double alpha, const double* B /*[N,m] or NULL*/, double beta, const double* C /*[N,m] or NULL*/,
                        double gamma, double* Y /*[N,m]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Edges of a kNN graph counted by (label of the row, label of the neighbour): the G x G table that PAGA's cluster graph
+ * (clip_dplm_amd.paga; the reference runs sc.tl.paga on the host before its diffusion map - tong/utils/data.py:47) and
+ * a kNN label-transfer confusion matrix are made of, in one pass over the [M, k] indices, with no intermediate that
+ * grows with M x G.
+ *
+ *   counts[a, b] += #{(i, t) : row_labels[i] = a, 0 <= idx[i, t] < Ny, key_labels[idx[i, t]] = b}     a, b in [0, G)
+ *
+ * idx int64 [M, k] (clipk_sim_knn's output; a graph of a cloud against itself has key_labels = row_labels, Ny = M);
+ * row_labels int32 [M], key_labels int32 [Ny]; counts int64 [G, G] row-major is ADDED into: the caller zeroes it.
+ * A row label outside [0, G), an index outside [0, Ny) (the -1 of a missing result) and a key label outside [0, G)
+ * each count nowhere.  M >= 1, Ny >= 1, 1 <= k <= 1024 (else CLIPK_ERR_BAD_ARG), 1 <= G <= CLIPK_LABEL_PAIRS_MAX_G
+ * (G < 1: CLIPK_ERR_BAD_ARG, larger: CLIPK_ERR_UNSUPPORTED; the table is at most 8 MB).  Pointers need only their
+ * types' alignment.
+ * Integer arithmetic: the result is exact and does not depend on the launch shape, on the order of the atomics or on
+ * which path ran.  G <= 128: every workgroup keeps the table as int32 bins in LDS, walks a contiguous range of rows
+ * (fewer than 2^31 entries, so no bin overflows) and adds its non-zero bins to counts once, with 64-bit atomics.
+ * Larger G: a wave merges the equal (a, b) among its lanes and adds once per distinct pair.  No workspace, no host
+ * read, never allocates, never synchronises, capturable. */
+#define CLIPK_LABEL_PAIRS_MAX_G 1024
+int clipk_knn_label_pairs(const int64_t* idx /*[M,k]*/, long long M, int k, const int32_t* row_labels /*[M]*/,
+                          const int32_t* key_labels /*[Ny]*/, long long Ny, int G, long long* counts /*[G,G]*/,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
